@@ -18,6 +18,8 @@ Rank 0 prints ONE JSON line; besides the contract keys it carries
                  the north star asks for (`forward.frac`, target 0.40) and a per-class breakdown.
   cpu_baseline : the oracle (fp32 PyTorch restatement of the reference path) timed on this box's
                  host cores on a bounded sample; a reported baseline, not the optimisation target.
+
+`--dump-outputs DIR` writes the samples of the last timed step as DIR/<field>.npy (`dump_outputs`), for comparing two builds on the same inputs.
 """
 import argparse
 import json
@@ -99,6 +101,28 @@ def cpu_baseline(budget_s=150.0):
     return dict(value=round(1.0 / est, 5), unit="denoise-steps/sec", cores=cores, kind="port", measured=False,
                 sample=f"1 fp32 oracle forward at 256^2 ({t256:.2f} s measured) EXTRAPOLATED x5.5 (measured time ratio 4.3-4.8) to 1024^2 "
                        f"(estimate {est:.0f} s > budget {budget_s:.0f} s)")
+
+
+DUMP_BUDGET_BYTES = 64 * 10**6   # `--dump-outputs` writes at most this much in all
+DUMP_FIELDS = ("timesteps", "all_latents", "latent_index_map", "log_probs", "log_prob_index_map", "image")
+
+
+def dump_outputs(out_dir, samples):
+    """`--dump-outputs`: what `inference()` returned in the last timed step, as `<out_dir>/<field>.npy` (float32, batch first) -- the fields a
+    rollout produces, not the prompt embeddings handed in.  The weights, the prompts and the RNG seeds are fixed, so two builds run with
+    the same arguments can be compared file by file.  The budget goes to the smallest arrays first; one that does not fit into an even share
+    of what is left is written as a sample of its flattened elements at fixed seeded positions (the same positions for the same shape)."""
+    import numpy as np
+    stacked = type(samples[0]).stack(samples)
+    arrays = {k: stacked[k].detach().float().cpu().numpy() for k in DUMP_FIELDS if isinstance(stacked.get(k), torch.Tensor)}
+    os.makedirs(out_dir, exist_ok=True)
+    left = DUMP_BUDGET_BYTES
+    for n, (name, a) in enumerate(sorted(arrays.items(), key=lambda kv: kv[1].size)):
+        share = (left // (len(arrays) - n) - 1024) // 4    # float32 elements, the .npy header left room for
+        if a.size > share:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).integers(0, a.size, share))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes + 1024
 
 
 def _free_port():
@@ -258,7 +282,14 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher self-test without a GPU: gloo backend, the rollout replaced by a fixed sleep per micro-batch "
                          "(tests/test_dist_gloo.py); the JSON line is marked \"data\": \"dry-run\" and is NOT a measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them returned (rank 0's samples) as DIR/<field>.npy, float32, at most "
+                         "64 MB in all: the same arguments give the same inputs, so two builds can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.dry_run:
+        ap.error("--dump-outputs: a dry run computes nothing")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args.gpus))
@@ -393,6 +424,8 @@ def main():
         per_rank = [float(x.item()) for x in allt]
         elapsed = max(per_rank)                      # MAX over ranks
     assert len(samples) == B and samples[0].all_latents.shape[0] == len(traj) and torch.isfinite(samples[0].log_probs).all()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, samples)
 
     n_cfg = 2 if cfg_on else 1
     lat = args.size // 8

@@ -61,3 +61,41 @@ def test_default_bench_line_carries_the_cpu_baseline_and_the_round_4_objects():
     fam = d["families"]
     for leg in ("flux1_dev_b8_1024", "wan21_t2v_1p3b_b2_cfg_480x832x49", "qwen_image_b2_cfg_1328"):
         assert fam[leg]["finite"] is True and 0.3 < fam[leg]["forward_frac"] < 1.0, leg
+
+
+def test_dump_outputs_writes_the_rollout_fields_within_its_budget(tmp_path):
+    """`bench.py --dump-outputs DIR`: float32 `.npy` files of what the rollout returned (not of the prompt embeddings handed in), whole when they
+    fit, and otherwise the same seeded sample of elements on every call, 64 MB in all at most."""
+    import numpy as np
+    import torch
+
+    import bench
+    from mi355_flow.samples import SD3_5Sample
+
+    def samples(batch, positions):
+        g = torch.Generator().manual_seed(5)
+        return [SD3_5Sample(timesteps=torch.arange(28.0), all_latents=torch.randn(positions, 16, 128, 128, generator=g).half(),
+                            latent_index_map=torch.arange(29), log_probs=torch.randn(1, generator=g), log_prob_index_map=torch.arange(29),
+                            prompt_embeds=torch.randn(3, 8, generator=g).bfloat16(), pooled_prompt_embeds=torch.randn(8, generator=g),
+                            height=1024, width=1024) for _ in range(batch)]
+
+    def load(d):
+        return {f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))}
+
+    small = samples(2, 2)
+    bench.dump_outputs(str(tmp_path / "small"), small)
+    got = load(tmp_path / "small")
+    assert sorted(got) == ["all_latents", "latent_index_map", "log_prob_index_map", "log_probs", "timesteps"]
+    assert all(a.dtype == np.float32 for a in got.values())
+    np.testing.assert_array_equal(got["all_latents"], torch.stack([s.all_latents for s in small]).float().numpy())
+    np.testing.assert_array_equal(got["log_probs"], torch.stack([s.log_probs for s in small]).numpy())
+    np.testing.assert_array_equal(got["latent_index_map"], np.arange(29, dtype=np.float32))
+
+    big = samples(40, 2)                                 # 84 MB of latents as float32
+    for d in ("big_a", "big_b"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    a, b = load(tmp_path / "big_a"), load(tmp_path / "big_b")
+    assert sum(os.path.getsize(tmp_path / "big_a" / f) for f in os.listdir(tmp_path / "big_a")) <= 64 * 10**6
+    assert a["all_latents"].ndim == 1 and a["all_latents"].size > 10**7 and a["log_probs"].shape == (40, 1)
+    for k in a:
+        np.testing.assert_array_equal(a[k], b[k])
