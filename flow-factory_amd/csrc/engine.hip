@@ -12,20 +12,12 @@
 #include <vector>
 
 #include "../../include/mi355_flow.h"
-#include "kernels.h"
+#include "engine_common.h"
+#include "train_common.h"
 
 using namespace mi355;
 
 static thread_local std::string g_err;
-static int fail(const char* fmt, ...) {
-    char buf[1024];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return 1;
-}
 namespace mi355 {
 int errorf(const char* fmt, ...) {
     char buf[1024];
@@ -37,16 +29,6 @@ int errorf(const char* fmt, ...) {
     return 1;
 }
 }  // namespace mi355
-#define HIPCHK(x)                                                                          \
-    do {                                                                                   \
-        hipError_t _e = (x);                                                               \
-        if (_e != hipSuccess) return fail("%s failed: %s (%s:%d)", #x, hipGetErrorString(_e), __FILE__, __LINE__); \
-    } while (0)
-#define CHK(x)                 \
-    do {                       \
-        int _r = (x);          \
-        if (_r) return _r;     \
-    } while (0)
 
 // ------------------------------------------------------------------------ kernel-class timing
 // Optional hipEvent brackets around every launch of a kernel class, recorded on the launch stream
@@ -101,7 +83,7 @@ extern "C" int mi355_profile_collect(double* ms_out, int64_t* count_out) {
         float ms = 0.f;
         hipError_t e = hipEventSynchronize(g_prof.ev[2 * i + 1]);
         if (e == hipSuccess) e = hipEventElapsedTime(&ms, g_prof.ev[2 * i], g_prof.ev[2 * i + 1]);
-        if (e != hipSuccess) return fail("mi355_profile_collect: %s", hipGetErrorString(e));
+        if (e != hipSuccess) return errorf("mi355_profile_collect: %s", hipGetErrorString(e));
         g_prof.ms[g_prof.cls[i]] += ms;
         g_prof.count[g_prof.cls[i]] += 1;
     }
@@ -125,17 +107,13 @@ static int g_wgrad_tn = 1;           // key 39: weight gradients of whole-tile s
 static int g_fuse_colsum = 1;        // key 38: bias-gradient column-sum finish inside the weight gradient's split-K reduction launch (engine_train.inc: wgrad)
 struct mi355_engine;
 struct mi355_plan;
+struct TrainEngineState;
+struct mi355_train;
 static void train_release(mi355_plan* p);
 static void train_release_engine(mi355_engine* e);
 static void train_mark_dirty(mi355_engine* e);
 
 // ------------------------------------------------------------------------------------ engine
-struct Slot {
-    void* dst;      // device destination (bf16_t* or float*)
-    int dst_dt;     // DT_BF16 / DT_F32
-    int64_t numel;  // elements expected
-    bool bound;
-};
 
 struct BlockW {
     bool dual, last;
@@ -146,44 +124,16 @@ struct BlockW {
     float bound_joint = 0.f, bound_dual = 0.f;   // proven |score| bounds of the two attentions (update_score_bounds)
 };
 
-struct mi355_engine {
+struct mi355_engine : ParamTable {
     mi355_model_cfg cfg;
     int D, F, L, KP;  // model dim, ff inner, layers, patch K
     int mod_cols, mod_out;
-    char* arena16 = nullptr;
-    char* arena32 = nullptr;
-    size_t used16 = 0, used32 = 0, cap16 = 0, cap32 = 0;
     bf16_t *w_patch, *pos_embed, *w_t1, *w_t2, *w_p1, *w_p2, *w_ctx, *w_mod, *w_proj;
     float *b_patch, *b_t1, *b_t2, *b_p1, *b_p2, *b_ctx, *b_mod, *b_proj;
     std::vector<BlockW> blk;
-    std::map<std::string, Slot> slots;
-    std::vector<std::string> names;
     bool bounds_dirty = true;   // a norm weight was (re)bound since the last update_score_bounds
     int bounds_ver = 0;
-
-    bf16_t* a16(int64_t n) {
-        size_t bytes = ((size_t)n * 2 + 255) & ~(size_t)255;
-        char* p = arena16 ? arena16 + used16 : nullptr;
-        used16 += bytes;
-        return (bf16_t*)p;
-    }
-    float* a32(int64_t n) {
-        size_t bytes = ((size_t)n * 4 + 255) & ~(size_t)255;
-        char* p = arena32 ? arena32 + used32 : nullptr;
-        used32 += bytes;
-        return (float*)p;
-    }
-    void reg(const std::string& name, void* dst, int dt, int64_t numel) {
-        if (arena16) {
-            slots[name] = Slot{dst, dt, numel, false};
-            names.push_back(name);
-        }
-    }
-    // linear: weight [out][in] bf16 at w (row offset allowed by caller), bias fp32
-    void lin(const std::string& name, bf16_t* w, float* b, int out_f, int in_f) {
-        reg(name + ".weight", w, DT_BF16, (int64_t)out_f * in_f);
-        reg(name + ".bias", b, DT_F32, out_f);
-    }
+    TrainEngineState* train = nullptr;   // training-mode state (engine_train.inc), created on first use
     void layout();  // called twice: sizing pass (arena null), then real pass
 };
 
@@ -266,13 +216,13 @@ extern "C" int mi355_version(void) { return MI355_FLOW_VERSION; }
 extern "C" const char* mi355_last_error(void) { return g_err.c_str(); }
 
 extern "C" int mi355_engine_create(const mi355_model_cfg* cfg, mi355_engine** out) {
-    if (!cfg || !out) return fail("mi355_engine_create: null argument");
-    if (cfg->head_dim != 64) return fail("mi355_engine_create: head_dim must be 64 (got %d)", cfg->head_dim);
-    if (cfg->num_layers < 1 || cfg->num_layers > 64) return fail("mi355_engine_create: num_layers out of range");
+    if (!cfg || !out) return errorf("mi355_engine_create: null argument");
+    if (cfg->head_dim != 64) return errorf("mi355_engine_create: head_dim must be 64 (got %d)", cfg->head_dim);
+    if (cfg->num_layers < 1 || cfg->num_layers > 64) return errorf("mi355_engine_create: num_layers out of range");
     const int KP = cfg->in_channels * cfg->patch_size * cfg->patch_size;
     if (KP % 64 || cfg->joint_attention_dim % 64 || cfg->pooled_projection_dim % 64 || cfg->time_proj_dim % 64)
-        return fail("mi355_engine_create: every GEMM K dim must be a multiple of 64");
-    if ((cfg->patch_size * cfg->patch_size * cfg->out_channels) % 4) return fail("proj_out width must be a multiple of 4");
+        return errorf("mi355_engine_create: every GEMM K dim must be a multiple of 64");
+    if ((cfg->patch_size * cfg->patch_size * cfg->out_channels) % 4) return errorf("proj_out width must be a multiple of 4");
     mi355_engine* e = new mi355_engine();
     e->cfg = *cfg;
     e->D = cfg->num_heads * cfg->head_dim;
@@ -280,17 +230,7 @@ extern "C" int mi355_engine_create(const mi355_model_cfg* cfg, mi355_engine** ou
     e->L = cfg->num_layers;
     e->KP = KP;
     e->layout();  // sizing pass
-    e->cap16 = e->used16;
-    e->cap32 = e->used32;
-    hipError_t e1 = hipMalloc((void**)&e->arena16, e->cap16);
-    hipError_t e2 = hipMalloc((void**)&e->arena32, e->cap32);
-    if (e1 != hipSuccess || e2 != hipSuccess) {
-        int r = fail("mi355_engine_create: hipMalloc of %zu + %zu bytes failed (%s)", e->cap16, e->cap32, hipGetErrorString(e1 != hipSuccess ? e1 : e2));
-        if (e->arena16) (void)hipFree(e->arena16);
-        if (e->arena32) (void)hipFree(e->arena32);
-        delete e;
-        return r;
-    }
+    if (e->alloc("mi355_engine_create") != 0) { delete e; return 1; }
     e->layout();  // real pass
     *out = e;
     return 0;
@@ -299,42 +239,24 @@ extern "C" int mi355_engine_create(const mi355_model_cfg* cfg, mi355_engine** ou
 extern "C" int mi355_engine_destroy(mi355_engine* e) {
     if (!e) return 0;
     train_release_engine(e);
-    if (e->arena16) (void)hipFree(e->arena16);
-    if (e->arena32) (void)hipFree(e->arena32);
+    e->release();
     delete e;
     return 0;
 }
 
 extern "C" int mi355_engine_num_params(mi355_engine* e) { return e ? (int)e->names.size() : 0; }
-extern "C" const char* mi355_engine_param_name(mi355_engine* e, int i) {
-    if (!e || i < 0 || i >= (int)e->names.size()) return nullptr;
-    return e->names[i].c_str();
-}
+extern "C" const char* mi355_engine_param_name(mi355_engine* e, int i) { return e ? e->param_name(i) : nullptr; }
 
 extern "C" int mi355_engine_bind_weight(mi355_engine* e, const char* name, const void* src, int dtype, int ndim,
                                         const int64_t* shape, void* stream) {
-    if (!e || !name || !src) return fail("mi355_engine_bind_weight: null argument");
-    auto it = e->slots.find(name);
-    if (it == e->slots.end()) return fail("mi355_engine_bind_weight: unknown parameter '%s'", name);
-    int64_t n = 1;
-    for (int i = 0; i < ndim; ++i) n *= shape[i];
-    if (n != it->second.numel)
-        return fail("mi355_engine_bind_weight: '%s' has %lld elements, expected %lld", name, (long long)n,
-                    (long long)it->second.numel);
-    if (dtype < 0 || dtype > 2) return fail("mi355_engine_bind_weight: bad dtype %d", dtype);
-    HIPCHK(launch_convert(src, dtype, it->second.dst, it->second.dst_dt, n, (hipStream_t)stream));
-    it->second.bound = true;
+    if (!e || !name || !src) return errorf("mi355_engine_bind_weight: null argument");
+    CHK(e->bind("mi355_engine_bind_weight", name, src, dtype, ndim, shape, (hipStream_t)stream));
     train_mark_dirty(e);
     if (strstr(name, ".norm_")) e->bounds_dirty = true;
     return 0;
 }
 
-extern "C" int mi355_engine_weights_ready(mi355_engine* e) {
-    if (!e) return fail("null engine");
-    for (auto& kv : e->slots)
-        if (!kv.second.bound) return fail("parameter '%s' has not been bound", kv.first.c_str());
-    return 0;
-}
+extern "C" int mi355_engine_weights_ready(mi355_engine* e) { return e ? e->ready() : errorf("null engine"); }
 
 // -------------------------------------------------------------------------------------- plan
 struct mi355_plan {
@@ -353,25 +275,20 @@ struct mi355_plan {
     float *io_noise, *io_lp;            // step noise [max_steps][B][n_lat] fp32, log-probs [max_steps][B]
     bf16_t *io_pe, *io_pp, *io_ne, *io_np;
     std::vector<float> host_t, host_sc;
-    // hipGraph of the whole N-step loop
-    hipGraphExec_t gexec = nullptr;
-    hipStream_t cap_stream = nullptr;   // capture happens on a plan-owned stream: the caller's may be the legacy default stream (torch's
-                                        // current stream unless the user switched), which cannot be captured; the graph is LAUNCHED on the caller's
-    bool warmed = false;
-    int g_steps = -1, g_dyn = -1, g_storage = -1, g_init = -1, g_clp = -1, g_attn = -1, g_gemm = -1, g_bounds = -1, g_two = -1, g_tune = -1;
+    RolloutGraph graph;                 // hipGraph of the whole N-step loop
+    mi355_train* train = nullptr;       // training workspace (engine_train.inc), created by the first training-mode step
     // text-stream chain of a forward on a second stream (forward_core): plan-owned, created on first use
     hipStream_t side = nullptr, side_v = nullptr;   // side_v: the image stream's V^T (and dual-attention q|k / V^T) projections
     std::vector<hipEvent_t> ev_vfork, ev_vjoin, ev_djoin;   // per block: xn ready (main -> side_v), V^T ready, dual q|k|V^T ready (side_v -> main)
     std::vector<hipEvent_t> ev_join, ev_fork;   // per block: text q|k|v ready (side -> main), attention done (main -> side); [L] = forward start
-    float g_guidance = 0.f, g_sigma_max = 0.f;
 };
 
 extern "C" int mi355_plan_create(mi355_engine* e, int batch, int n_cfg, int latent_h, int latent_w, int n_text,
                                  int max_steps, mi355_plan** out) {
-    if (!e || !out) return fail("mi355_plan_create: null argument");
-    if (batch < 1 || (n_cfg != 1 && n_cfg != 2) || n_text < 1 || max_steps < 1) return fail("mi355_plan_create: bad shape");
+    if (!e || !out) return errorf("mi355_plan_create: null argument");
+    if (batch < 1 || (n_cfg != 1 && n_cfg != 2) || n_text < 1 || max_steps < 1) return errorf("mi355_plan_create: bad shape");
     const int ps = e->cfg.patch_size;
-    if (latent_h % ps || latent_w % ps) return fail("latent size must be a multiple of patch_size");
+    if (latent_h % ps || latent_w % ps) return errorf("latent size must be a multiple of patch_size");
     mi355_plan* p = new mi355_plan();
     p->e = e;
     p->B = batch; p->ncfg = n_cfg; p->Bp = batch * n_cfg;
@@ -384,60 +301,32 @@ extern "C" int mi355_plan_create(mi355_engine* e, int batch, int n_cfg, int late
     if (p->hp > e->cfg.pos_embed_max_size || p->wp > e->cfg.pos_embed_max_size) {
         const int hp = p->hp, wp = p->wp;
         delete p;
-        return fail("latent grid %dx%d exceeds pos_embed_max_size %d", hp, wp, e->cfg.pos_embed_max_size);
+        return errorf("latent grid %dx%d exceeds pos_embed_max_size %d", hp, wp, e->cfg.pos_embed_max_size);
     }
     const int D = e->D, F = e->F;
     const int64_t rows_cond = (int64_t)max_steps * p->Bp;
-    size_t off = 0;
-    auto take = [&](int64_t elems, int esz) {
-        size_t o = off;
-        off += (((size_t)elems * esz) + 255) & ~(size_t)255;
-        return o;
-    };
     const int64_t qk_el = (int64_t)p->Bp * e->cfg.num_heads * p->S_pad * 64;
     const int Ni_pad = (p->Ni + 63) / 64 * 64;
     const int64_t qk2_el = (int64_t)p->Bp * e->cfg.num_heads * Ni_pad * 64;
-    size_t o_pe = take((int64_t)p->Ni * D, 2), o_patch = take((int64_t)p->Mi * e->KP, 2);
-    size_t o_x = take((int64_t)p->Mi * D, 2), o_c = take((int64_t)p->Mc * D, 2), o_c0 = take((int64_t)p->Mc * D, 2);
-    size_t o_xn = take((int64_t)p->Mi * D, 2), o_xn2 = take((int64_t)p->Mi * D, 2), o_cn = take((int64_t)p->Mc * D, 2);
-    size_t o_q = take(qk_el, 2), o_k = take(qk_el, 2), o_vT = take(qk_el, 2);
-    size_t o_q2 = take(qk2_el, 2), o_k2 = take(qk2_el, 2), o_vT2 = take(qk2_el, 2);
-    size_t o_oi = take((int64_t)p->Mi * D, 2), o_oc = take((int64_t)p->Mc * D, 2);
-    size_t o_hid = take((int64_t)p->Mi * F, 2), o_chid = take((int64_t)p->Mc * F, 2);
-    size_t o_tp = take(rows_cond * e->cfg.time_proj_dim, 2), o_h1 = take(rows_cond * D, 2);
-    size_t o_p1 = take((int64_t)p->Bp * D, 2), o_pemb = take((int64_t)p->Bp * D, 2), o_semb = take(rows_cond * D, 2);
-    size_t o_mod = take(rows_cond * e->mod_cols, 2), o_v = take((int64_t)p->Bp * p->n_lat, 2);
-    size_t o_t = take(rows_cond, 4), o_sc = take(3 * (int64_t)max_steps, 4);
-    size_t o_ii = take((int64_t)p->B * p->n_lat, 4), o_it = take((int64_t)(max_steps + 1) * p->B * p->n_lat, 4);
-    size_t o_in = take((int64_t)max_steps * p->B * p->n_lat, 4), o_il = take((int64_t)max_steps * p->B, 4);
-    size_t o_ipe = take((int64_t)p->B * p->Nt * e->cfg.joint_attention_dim, 2), o_ipp = take((int64_t)p->B * e->cfg.pooled_projection_dim, 2);
-    size_t o_ine = take((int64_t)p->B * p->Nt * e->cfg.joint_attention_dim, 2), o_inp = take((int64_t)p->B * e->cfg.pooled_projection_dim, 2);
-    p->ws_bytes = off;
-    if (hipMalloc((void**)&p->ws, off) != hipSuccess) {
-        int r = fail("mi355_plan_create: hipMalloc of %zu bytes failed", off);
-        delete p;
-        return r;
-    }
+    const int64_t nl = (int64_t)p->B * p->n_lat, J = e->cfg.joint_attention_dim, P = e->cfg.pooled_projection_dim;
+    Carver c;
+    c.take(p->pe, (int64_t)p->Ni * D); c.take(p->patches, (int64_t)p->Mi * e->KP);
+    c.take(p->x, (int64_t)p->Mi * D); c.take(p->c, (int64_t)p->Mc * D); c.take(p->c0, (int64_t)p->Mc * D);
+    c.take(p->xn, (int64_t)p->Mi * D); c.take(p->xn2, (int64_t)p->Mi * D); c.take(p->cn, (int64_t)p->Mc * D);
+    c.take(p->q, qk_el); c.take(p->k, qk_el); c.take(p->vT, qk_el);
+    c.take(p->q2, qk2_el); c.take(p->k2, qk2_el); c.take(p->vT2, qk2_el);
+    c.take(p->o_img, (int64_t)p->Mi * D); c.take(p->o_ctx, (int64_t)p->Mc * D);
+    c.take(p->hid, (int64_t)p->Mi * F); c.take(p->chid, (int64_t)p->Mc * F);
+    c.take(p->tproj, rows_cond * e->cfg.time_proj_dim); c.take(p->h1, rows_cond * D);
+    c.take(p->p1, (int64_t)p->Bp * D); c.take(p->pemb, (int64_t)p->Bp * D); c.take(p->semb, rows_cond * D);
+    c.take(p->mod_all, rows_cond * e->mod_cols); c.take(p->v, (int64_t)p->Bp * p->n_lat);
+    c.take(p->t_dev, rows_cond); c.take(p->scal, 3 * (int64_t)max_steps);
+    c.take(p->io_init, nl * 4); c.take(p->io_traj, (int64_t)(max_steps + 1) * nl * 4);
+    c.take(p->io_noise, (int64_t)max_steps * nl); c.take(p->io_lp, (int64_t)max_steps * p->B);
+    c.take(p->io_pe, (int64_t)p->B * p->Nt * J); c.take(p->io_pp, (int64_t)p->B * P);
+    c.take(p->io_ne, (int64_t)p->B * p->Nt * J); c.take(p->io_np, (int64_t)p->B * P);
     // zero once: the padded key rows / columns of q,k,vT must stay finite (attention masks them)
-    if (hipMemset(p->ws, 0, off) != hipSuccess) {
-        (void)hipFree(p->ws);
-        delete p;
-        return fail("mi355_plan_create: hipMemset failed");
-    }
-    char* w = p->ws;
-    p->pe = (bf16_t*)(w + o_pe); p->patches = (bf16_t*)(w + o_patch);
-    p->x = (bf16_t*)(w + o_x); p->c = (bf16_t*)(w + o_c); p->c0 = (bf16_t*)(w + o_c0);
-    p->xn = (bf16_t*)(w + o_xn); p->xn2 = (bf16_t*)(w + o_xn2); p->cn = (bf16_t*)(w + o_cn);
-    p->q = (bf16_t*)(w + o_q); p->k = (bf16_t*)(w + o_k); p->vT = (bf16_t*)(w + o_vT);
-    p->q2 = (bf16_t*)(w + o_q2); p->k2 = (bf16_t*)(w + o_k2); p->vT2 = (bf16_t*)(w + o_vT2);
-    p->o_img = (bf16_t*)(w + o_oi); p->o_ctx = (bf16_t*)(w + o_oc);
-    p->hid = (bf16_t*)(w + o_hid); p->chid = (bf16_t*)(w + o_chid);
-    p->tproj = (bf16_t*)(w + o_tp); p->h1 = (bf16_t*)(w + o_h1); p->p1 = (bf16_t*)(w + o_p1);
-    p->pemb = (bf16_t*)(w + o_pemb); p->semb = (bf16_t*)(w + o_semb); p->mod_all = (bf16_t*)(w + o_mod);
-    p->v = (bf16_t*)(w + o_v);
-    p->t_dev = (float*)(w + o_t); p->scal = (float*)(w + o_sc);
-    p->io_init = w + o_ii; p->io_traj = w + o_it; p->io_noise = (float*)(w + o_in); p->io_lp = (float*)(w + o_il);
-    p->io_pe = (bf16_t*)(w + o_ipe); p->io_pp = (bf16_t*)(w + o_ipp); p->io_ne = (bf16_t*)(w + o_ine); p->io_np = (bf16_t*)(w + o_inp);
+    if (c.alloc(&p->ws, &p->ws_bytes, true, "mi355_plan_create") != 0) { delete p; return 1; }
     *out = p;
     return 0;
 }
@@ -445,8 +334,7 @@ extern "C" int mi355_plan_create(mi355_engine* e, int batch, int n_cfg, int late
 extern "C" int mi355_plan_destroy(mi355_plan* p) {
     if (!p) return 0;
     train_release(p);
-    if (p->gexec) (void)hipGraphExecDestroy(p->gexec);
-    if (p->cap_stream) (void)hipStreamDestroy(p->cap_stream);
+    p->graph.release();
     for (hipEvent_t ev : p->ev_join) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : p->ev_fork) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : p->ev_vfork) (void)hipEventDestroy(ev);
@@ -494,7 +382,7 @@ static int update_score_bounds(mi355_engine* e, hipStream_t st) {
 
 // how many attention launches of a forward take the static-bound (no running max) kernel with the weights bound now
 extern "C" int mi355_engine_attention_info(mi355_engine* e, void* stream, int* n_static, int* n_total, float* max_bound) {
-    if (!e) return fail("mi355_engine_attention_info: null engine");
+    if (!e) return errorf("mi355_engine_attention_info: null engine");
     CHK(mi355_engine_weights_ready(e));
     CHK(update_score_bounds(e, (hipStream_t)stream));
     int ns = 0, nt = 0;
@@ -527,8 +415,8 @@ static int prepare_prompt(mi355_plan* p, hipStream_t st, const void* enc_a, cons
     const int D = e->D, J = e->cfg.joint_attention_dim, P = e->cfg.pooled_projection_dim;
     const void* encs[2] = {enc_a, enc_b};
     const void* pools[2] = {pooled_a, pooled_b};
-    if (p->ncfg == 2 && (!enc_b || !pooled_b)) return fail("n_cfg == 2 needs both prompt halves");
-    if (!enc_a || !pooled_a) return fail("prompt embeddings are NULL");
+    if (p->ncfg == 2 && (!enc_b || !pooled_b)) return errorf("n_cfg == 2 needs both prompt halves");
+    if (!enc_a || !pooled_a) return errorf("prompt embeddings are NULL");
     for (int half = 0; half < p->ncfg; ++half) {
         const int rows = p->B * p->Nt;
         GemmParams g = gp((const bf16_t*)encs[half], J, e->w_ctx, J, rows, D, J, EPI_BIAS, e->b_ctx,
@@ -789,7 +677,7 @@ static int forward_core(mi355_plan* p, hipStream_t st, const void* latents, int 
 extern "C" int mi355_transformer_forward(mi355_plan* p, void* stream, const void* latents, int lat_dtype, const float* t,
                                          int t_round_dtype, const void* enc_a, const void* pooled_a, const void* enc_b,
                                          const void* pooled_b, void* v_out) {
-    if (!p || !latents || !t || !v_out) return fail("mi355_transformer_forward: null argument");
+    if (!p || !latents || !t || !v_out) return errorf("mi355_transformer_forward: null argument");
     CHK(mi355_engine_weights_ready(p->e));
     hipStream_t st = (hipStream_t)stream;
     CHK(update_score_bounds(p->e, st));
@@ -804,11 +692,11 @@ static int sde_call(hipStream_t st, int batch, int64_t n, const void* v_text, co
                     const float* sigma, const float* sigma_next, const float* eta, int scalar_stride, float sigma_max,
                     int dynamics, int compute_log_prob, void* next_out, float* next_f32, float* mean_out,
                     float* noise_pred_out, float* log_prob, float* std_dev_t, float* dt) {
-    if (!v_text || !latents || !sigma || !sigma_next || !eta) return fail("mi355_sde_step: null argument");
-    if (!next_in && !noise && dynamics != MI355_ODE) return fail("mi355_sde_step: SDE rollout step needs `noise`");
-    if (dynamics < 0 || dynamics > 3) return fail("mi355_sde_step: unknown dynamics %d", dynamics);
-    if (lat_dtype < 0 || lat_dtype > 2) return fail("mi355_sde_step: bad latent dtype %d", lat_dtype);
-    if (v_dtype < 0 || v_dtype > 2) return fail("mi355_sde_step: bad noise_pred dtype %d", v_dtype);
+    if (!v_text || !latents || !sigma || !sigma_next || !eta) return errorf("mi355_sde_step: null argument");
+    if (!next_in && !noise && dynamics != MI355_ODE) return errorf("mi355_sde_step: SDE rollout step needs `noise`");
+    if (dynamics < 0 || dynamics > 3) return errorf("mi355_sde_step: unknown dynamics %d", dynamics);
+    if (lat_dtype < 0 || lat_dtype > 2) return errorf("mi355_sde_step: bad latent dtype %d", lat_dtype);
+    if (v_dtype < 0 || v_dtype > 2) return errorf("mi355_sde_step: bad noise_pred dtype %d", v_dtype);
     SdeStepParams s;
     memset(&s, 0, sizeof(s));
     s.v_text = (const bf16_t*)v_text; s.v_uncond = (const bf16_t*)v_uncond; s.v_dt = v_dtype; s.guidance = guidance;
@@ -840,16 +728,16 @@ extern "C" int mi355_sde_step(void* stream, int batch, int64_t n, const void* v_
 // UniPC multistep update of the evaluation-mode Wan sampler (kernels: sde_step.hip; coefficients: mi355_flow/unipc.py)
 extern "C" int mi355_unipc_convert(void* stream, const void* v_text, const void* v_uncond, int v_dtype, float guidance, const void* sample,
                                    int sample_dtype, float sigma, float* x0_out, int64_t n) {
-    if (!v_text || !sample || !x0_out) return fail("mi355_unipc_convert: null argument");
-    if (n <= 0 || (n & 3)) return fail("mi355_unipc_convert: n must be a positive multiple of 4 (got %lld)", (long long)n);
+    if (!v_text || !sample || !x0_out) return errorf("mi355_unipc_convert: null argument");
+    if (n <= 0 || (n & 3)) return errorf("mi355_unipc_convert: n must be a positive multiple of 4 (got %lld)", (long long)n);
     HIPCHK(launch_unipc_convert(v_text, v_uncond, v_dtype, guidance, sample, sample_dtype, sigma, x0_out, (long)n, (hipStream_t)stream));
     return 0;
 }
 extern "C" int mi355_op_lincomb(void* stream, int n_terms, const void* const* tensors, const int* dtypes, const float* coefs, void* out, int out_dtype,
                                 int64_t n) {
-    if (!tensors || !dtypes || !coefs || !out) return fail("mi355_op_lincomb: null argument");
-    if (n_terms < 1 || n_terms > 5) return fail("mi355_op_lincomb: 1..5 terms (got %d)", n_terms);
-    if (n <= 0 || (n & 3)) return fail("mi355_op_lincomb: n must be a positive multiple of 4 (got %lld)", (long long)n);
+    if (!tensors || !dtypes || !coefs || !out) return errorf("mi355_op_lincomb: null argument");
+    if (n_terms < 1 || n_terms > 5) return errorf("mi355_op_lincomb: 1..5 terms (got %d)", n_terms);
+    if (n <= 0 || (n & 3)) return errorf("mi355_op_lincomb: n must be a positive multiple of 4 (got %lld)", (long long)n);
     HIPCHK(launch_lincomb(n_terms, tensors, dtypes, coefs, out, out_dtype, (long)n, (hipStream_t)stream));
     return 0;
 }
@@ -858,9 +746,9 @@ extern "C" int mi355_sde_step_bwd(void* stream, int batch, int64_t n, const void
                                   int lat_dtype, const void* next_in, int next_in_dtype, const float* sigma, const float* sigma_next, const float* eta,
                                   int scalar_stride, float sigma_max, int dynamics, int compute_log_prob, const float* g_log_prob,
                                   const float* g_noise_pred, const float* g_mean, float* dv) {
-    if (!v_text || !latents || !next_in || !sigma || !sigma_next || !eta || !dv) return fail("mi355_sde_step_bwd: null argument");
-    if (dynamics < 0 || dynamics > 3) return fail("mi355_sde_step_bwd: unknown dynamics %d", dynamics);
-    if (lat_dtype < 0 || lat_dtype > 2 || next_in_dtype < 0 || next_in_dtype > 2) return fail("mi355_sde_step_bwd: bad dtype");
+    if (!v_text || !latents || !next_in || !sigma || !sigma_next || !eta || !dv) return errorf("mi355_sde_step_bwd: null argument");
+    if (dynamics < 0 || dynamics > 3) return errorf("mi355_sde_step_bwd: unknown dynamics %d", dynamics);
+    if (lat_dtype < 0 || lat_dtype > 2 || next_in_dtype < 0 || next_in_dtype > 2) return errorf("mi355_sde_step_bwd: bad dtype");
     SdeBwdParams s;
     memset(&s, 0, sizeof(s));
     s.v_text = (const bf16_t*)v_text; s.v_uncond = (const bf16_t*)v_uncond; s.guidance = guidance;
@@ -878,7 +766,7 @@ extern "C" int mi355_denoise_step(mi355_plan* p, void* stream, const void* laten
                                   const float* sigma, const float* sigma_next, const float* eta, int scalar_stride,
                                   float sigma_max, int dynamics, int compute_log_prob, void* next_out, float* next_f32,
                                   float* mean_out, float* noise_pred_out, float* log_prob, float* std_dev_t, float* dt) {
-    if (!p) return fail("mi355_denoise_step: null plan");
+    if (!p) return errorf("mi355_denoise_step: null plan");
     CHK(mi355_transformer_forward(p, stream, latents, lat_dtype, t, lat_dtype, enc_a, pooled_a, enc_b, pooled_b, p->v));
     const bf16_t* vu = p->ncfg == 2 ? p->v : nullptr;
     const bf16_t* vt = p->ncfg == 2 ? p->v + (int64_t)p->B * p->n_lat : p->v;
@@ -924,12 +812,12 @@ extern "C" int mi355_rollout(mi355_plan* p, void* stream, int n_steps, const flo
                              const int32_t* keep_slot_host, void* out_latents, float* out_log_probs, void* out_final,
                              int compute_log_prob) {
     if (!p || !timesteps_host || !sigmas_host || !noise_levels_host || !init_latents || !prompt_embeds || !pooled)
-        return fail("mi355_rollout: null argument");
-    if (n_steps < 1 || n_steps > p->max_steps) return fail("mi355_rollout: n_steps %d exceeds the plan's max_steps %d", n_steps, p->max_steps);
-    if (storage_dtype < 0 || storage_dtype > 2 || init_dtype < 0 || init_dtype > 2) return fail("mi355_rollout: bad dtype");
-    if (p->ncfg == 2 && (!neg_embeds || !neg_pooled)) return fail("mi355_rollout: plan has n_cfg == 2 but no negative prompt embeddings");
-    if (!step_noise && dynamics != MI355_ODE) return fail("mi355_rollout: step_noise is NULL");
-    if (dynamics < 0 || dynamics > 3) return fail("mi355_rollout: unknown dynamics %d", dynamics);
+        return errorf("mi355_rollout: null argument");
+    if (n_steps < 1 || n_steps > p->max_steps) return errorf("mi355_rollout: n_steps %d exceeds the plan's max_steps %d", n_steps, p->max_steps);
+    if (storage_dtype < 0 || storage_dtype > 2 || init_dtype < 0 || init_dtype > 2) return errorf("mi355_rollout: bad dtype");
+    if (p->ncfg == 2 && (!neg_embeds || !neg_pooled)) return errorf("mi355_rollout: plan has n_cfg == 2 but no negative prompt embeddings");
+    if (!step_noise && dynamics != MI355_ODE) return errorf("mi355_rollout: step_noise is NULL");
+    if (dynamics < 0 || dynamics > 3) return errorf("mi355_rollout: unknown dynamics %d", dynamics);
     CHK(mi355_engine_weights_ready(p->e));
     hipStream_t st = (hipStream_t)stream;
     CHK(update_score_bounds(p->e, st));
@@ -964,54 +852,16 @@ extern "C" int mi355_rollout(mi355_plan* p, void* stream, int n_steps, const flo
     const float sigma_max = sigmas_host[1];
     const int clp = compute_log_prob && out_log_probs;
     // ---- the N-step loop: one hipGraph launch (captured on the second call of a configuration), else eager
-    bool launched = false;
-    if (g_use_graph && !g_prof.on && p->warmed) {
-        const bool same = p->gexec && p->g_steps == n_steps && p->g_dyn == dynamics && p->g_storage == storage_dtype &&
-                          p->g_init == init_dtype && p->g_clp == clp && p->g_guidance == guidance && p->g_sigma_max == sigma_max &&
-                          p->g_attn == get_attn_variant() && p->g_gemm == get_gemm_variant() && p->g_tune == tune_epoch() &&
-                          p->g_bounds == p->e->bounds_ver * 2 + (g_attn_static != 0) && p->g_two == (int)two_stream_wanted(p) * (1 + (int)late_fork_wanted(p) + 2 * (int)three_stream_wanted(p));
-        if (!same) {
-            if (two_stream_wanted(p)) CHK(two_stream_init(p));   // streams / events are created outside the capture
-            if (p->gexec) { (void)hipGraphExecDestroy(p->gexec); p->gexec = nullptr; }
-            hipGraph_t graph = nullptr;
-            hipError_t ce = hipSuccess;
-            if (!p->cap_stream) ce = hipStreamCreateWithFlags(&p->cap_stream, hipStreamNonBlocking);
-            if (ce == hipSuccess) ce = hipStreamBeginCapture(p->cap_stream, hipStreamCaptureModeRelaxed);
-            if (ce == hipSuccess) {
-                // nothing executes here: the body's launches / D2D copies on plan-owned buffers become graph nodes
-                const int rc = rollout_body(p, p->cap_stream, n_steps, dynamics, guidance, init_dtype, storage_dtype, sigma_max, clp);
-                ce = hipStreamEndCapture(p->cap_stream, &graph);
-                if (rc != 0 || ce != hipSuccess || !graph) {
-                    if (graph) (void)hipGraphDestroy(graph);
-                    graph = nullptr;
-                }
-            }
-            if (graph) {
-                ce = hipGraphInstantiate(&p->gexec, graph, nullptr, nullptr, 0);
-                (void)hipGraphDestroy(graph);
-                if (ce != hipSuccess) p->gexec = nullptr;
-            }
-            if (p->gexec) {
-                p->g_steps = n_steps; p->g_dyn = dynamics; p->g_storage = storage_dtype; p->g_init = init_dtype; p->g_clp = clp;
-                p->g_guidance = guidance; p->g_sigma_max = sigma_max; p->g_attn = get_attn_variant(); p->g_gemm = get_gemm_variant(); p->g_tune = tune_epoch();
-                p->g_bounds = p->e->bounds_ver * 2 + (g_attn_static != 0);
-                p->g_two = (int)two_stream_wanted(p) * (1 + (int)late_fork_wanted(p) + 2 * (int)three_stream_wanted(p));
-            } else {
-                // no silent fallback (header convention, reference constraints.md:144-145): the caller decides whether to
-                // retry with eager launches (mi355_tune_set(2, 0))
-                const hipError_t last = hipGetLastError();
-                return fail("mi355_rollout: hipGraph capture / instantiation of the %d-step loop failed (%s); "
-                            "mi355_tune_set(2, 0) selects eager launches", n_steps, hipGetErrorString(ce != hipSuccess ? ce : last));
-            }
-        }
-        if (p->gexec) {
-            HIPCHK(hipGraphLaunch(p->gexec, st));
-            launched = true;
-        }
-    }
-    if (!launched) {
+    if (g_use_graph && !g_prof.on && p->graph.warmed) {
+        const int key[RolloutGraph::NKEY] = {n_steps, dynamics, storage_dtype, init_dtype, clp, float_bits(guidance), float_bits(sigma_max),
+                                             get_attn_variant(), get_gemm_variant(), tune_epoch(), p->e->bounds_ver * 2 + (g_attn_static != 0),
+                                             (int)two_stream_wanted(p) * (1 + (int)late_fork_wanted(p) + 2 * (int)three_stream_wanted(p))};
+        CHK(p->graph.launch(key, st, "mi355_rollout", n_steps, 2,
+                            [&] { return two_stream_wanted(p) ? two_stream_init(p) : 0; },   // streams / events are created outside the capture
+                            [&](hipStream_t s) { return rollout_body(p, s, n_steps, dynamics, guidance, init_dtype, storage_dtype, sigma_max, clp); }));
+    } else {
         CHK(rollout_body(p, st, n_steps, dynamics, guidance, init_dtype, storage_dtype, sigma_max, clp));
-        p->warmed = true;
+        p->graph.warmed = true;
     }
     // ---- outputs: kept trajectory positions, log-probs of the SDE steps, final latents
     const size_t esz = storage_dtype == MI355_F32 ? 4 : 2;
@@ -1074,7 +924,7 @@ extern "C" int mi355_tune_set(int key, int value) {
         // refused unless the process opted in: a stale MI355_TUNE=29=... in a training environment must not corrupt rollouts silently
         const char* ok = getenv("MI355_ALLOW_ABLATION");
         if (value != 0 && !(ok && ok[0] == '1'))
-            return fail("mi355_tune_set(29, %d): the forward-ablation mask produces wrong results by construction; set MI355_ALLOW_ABLATION=1 "
+            return errorf("mi355_tune_set(29, %d): the forward-ablation mask produces wrong results by construction; set MI355_ALLOW_ABLATION=1 "
                         "to use it for a timing measurement", value);
         if (value != 0) fprintf(stderr, "mi355_flow: FORWARD ABLATION MASK %d ACTIVE -- results of the SD3.5 forward are WRONG (measurement only)\n", value);
         g_ablate = value;
@@ -1088,7 +938,7 @@ extern "C" int mi355_tune_set(int key, int value) {
     if (key == 39) { g_wgrad_tn = value; set_wgrad_tn_mode(value); return 0; }           // optimize() backward: 1 (default) = weight-gradient GEMMs read dY / X row-major through transposed LDS reads (2: 256 x 256 tiles where they fit), 0 = transposed copies
     if (key == 43) {      // (values 2..5: ablation builds of the dK/dV loop -- no VALU / no LDS reads / no barrier + loads / MFMAs only; WRONG results, measurement only)
         const char* ok = getenv("MI355_ALLOW_ABLATION");
-        if (value > 1 && value < 6 && !(ok && ok[0] == '1')) return fail("mi355_tune_set(43, %d): ablation builds produce wrong gradients; set MI355_ALLOW_ABLATION=1 for a timing measurement", value);
+        if (value > 1 && value < 6 && !(ok && ok[0] == '1')) return errorf("mi355_tune_set(43, %d): ablation builds produce wrong gradients; set MI355_ALLOW_ABLATION=1 for a timing measurement", value);
         set_attn_bwd_pipe(value); return 0;
     }         if (key == 44) { set_attn128_bwd_pipe(value); return 0; }  // head_dim-128 attention backward: 1 (default) = software-pipelined passes (gen_attn_bwd128.py), 0 = the round-4 kernels
     if (key == 40) { set_w6_mode(value); return 0; }           // 256x192-tile GEMM kernel (round 6): 0 off (default: measured slower inside the two-stream forward), 1 cost rule, 2 wherever it applies
@@ -1097,14 +947,14 @@ extern "C" int mi355_tune_set(int key, int value) {
     if (key == 38) { g_fuse_colsum = value; return 0; }        // optimize() backward: 1 (default) = column-sum finish fused into the split-K reduction launch, 0 = two launches
     if (key == 22) { g_train_two_stream = value; return 0; }   // optimize() replay: the context-stream chain of the training forward / backward on a side stream (1 = default)
     if (key == 21) { set_attn128_op_bound(value); return 0; }  // mi355_op_attention128: the |score| bound the caller asserts (0 = none)          // default GEMM dispatch: largest K for the 4-wave hand-scheduled kernel
-    return fail("mi355_tune_set: unknown key %d", key);
+    return errorf("mi355_tune_set: unknown key %d", key);
 }
 
 // ----------------------------------------------------------------------- operator-level API
 extern "C" int mi355_op_linear(void* stream, const void* A, const void* W, const float* bias, void* out, int M, int N, int K,
                                int act) {
-    if (!A || !W || !bias || !out) return fail("mi355_op_linear: null argument");
-    if (K % 64 || N % 4) return fail("mi355_op_linear: K %% 64 and N %% 4 must be 0");
+    if (!A || !W || !bias || !out) return errorf("mi355_op_linear: null argument");
+    if (K % 64 || N % 4) return errorf("mi355_op_linear: K %% 64 and N %% 4 must be 0");
     GemmParams g = gp((const bf16_t*)A, K, (const bf16_t*)W, K, M, N, K, act == 1 ? EPI_BIAS_SILU : act == 2 ? EPI_BIAS_GELU : EPI_BIAS,
                       bias, (bf16_t*)out, N);
     HIPCHK(gemm_p(g, (hipStream_t)stream));
@@ -1115,8 +965,8 @@ extern "C" int mi355_op_linear(void* stream, const void* A, const void* W, const
 // linears (K8 / K11 of SURVEY.md 2.3) as an operator, for unit tests and the GEMM A/B scripts
 extern "C" int mi355_op_linear_gate_res(void* stream, const void* A, const void* W, const float* bias, const void* gate, void* x, int M, int N,
                                         int K, int rows_per_sample) {
-    if (!A || !W || !bias || !gate || !x) return fail("mi355_op_linear_gate_res: null argument");
-    if (K % 64 || N % 8 || rows_per_sample < 1) return fail("mi355_op_linear_gate_res: K %% 64, N %% 8 must be 0 and rows_per_sample >= 1");
+    if (!A || !W || !bias || !gate || !x) return errorf("mi355_op_linear_gate_res: null argument");
+    if (K % 64 || N % 8 || rows_per_sample < 1) return errorf("mi355_op_linear_gate_res: K %% 64, N %% 8 must be 0 and rows_per_sample >= 1");
     GemmParams g = gp((const bf16_t*)A, K, (const bf16_t*)W, K, M, N, K, EPI_GATE_RES, bias, (bf16_t*)x, N);
     g.aux = (const bf16_t*)gate; g.ld_aux = N; g.rows_per_sample = rows_per_sample;
     HIPCHK(launch_gemm(g, (hipStream_t)stream));
@@ -1127,17 +977,17 @@ extern "C" int mi355_op_linear_gate_res(void* stream, const void* A, const void*
 // transposed-copy path (launch_transpose x 2 + the K-contiguous EPI_F32 GEMM).  Output: k_split fp32 partial slabs [N][K].
 extern "C" int mi355_op_wgrad(void* stream, const void* dY, int64_t ld_dy, const void* X, int64_t ld_x, float* out, int M, int N, int K, int k_split,
                               int variant, void* scratch, float* colsum) {
-    if (!dY || !X || !out || M <= 0 || N <= 0 || K <= 0 || k_split < 1) return fail("mi355_op_wgrad: bad argument");
+    if (!dY || !X || !out || M <= 0 || N <= 0 || K <= 0 || k_split < 1) return errorf("mi355_op_wgrad: bad argument");
     hipStream_t st = (hipStream_t)stream;
     if (variant == 1 || variant == 2) {          // 2 = the 256 x 256-tile form (N, K multiples of 256; no column sums)
         GemmTnParams tp{(const bf16_t*)dY, (long)ld_dy, (const bf16_t*)X, (long)ld_x, M, N, K, out, (long)K, k_split, (long)N * K, variant == 1 ? colsum : nullptr,
                         variant == 2 ? 1 : 0};
-        if (variant == 2 && (N % 256 || K % 256)) return fail("mi355_op_wgrad: variant 2 needs N %% 256 == 0 and K %% 256 == 0");
-        if (!gemm_tn_ok(tp)) return fail("mi355_op_wgrad: the row-major-operand kernel needs N %% 128 == 0, K %% 128 == 0, 16-byte aligned rows");
+        if (variant == 2 && (N % 256 || K % 256)) return errorf("mi355_op_wgrad: variant 2 needs N %% 256 == 0 and K %% 256 == 0");
+        if (!gemm_tn_ok(tp)) return errorf("mi355_op_wgrad: the row-major-operand kernel needs N %% 128 == 0, K %% 128 == 0, 16-byte aligned rows");
         HIPCHK(launch_gemm_tn(tp, st));
         return 0;
     }
-    if (!scratch) return fail("mi355_op_wgrad: variant 0 needs (N + K) * M_pad bf16 of scratch (M_pad = M rounded up to 64)");
+    if (!scratch) return errorf("mi355_op_wgrad: variant 0 needs (N + K) * M_pad bf16 of scratch (M_pad = M rounded up to 64)");
     const int Mp = (M + 63) / 64 * 64;                  // the copies are zero-padded to whole 64-row tiles (what the engines' path does)
     bf16_t* aT = (bf16_t*)scratch;
     bf16_t* xT = aT + (size_t)N * Mp;
@@ -1163,15 +1013,15 @@ extern "C" int mi355_op_linear_trace(void* stream, const void* A, const void* W,
 
 // measurement tool: n samples of {s_memtime, s_memrealtime} (int64 pairs) taken by one wave, ~sleep_iters * 8 k core clocks apart
 extern "C" int mi355_clock_probe(void* stream, void* out, int n, int sleep_iters) {
-    if (!out || n <= 0 || sleep_iters < 0) return fail("mi355_clock_probe: bad argument");
+    if (!out || n <= 0 || sleep_iters < 0) return errorf("mi355_clock_probe: bad argument");
     HIPCHK(launch_clock_probe((long long*)out, n, sleep_iters, (hipStream_t)stream));
     return 0;
 }
 
 extern "C" int mi355_op_attention(void* stream, const void* q, const void* k, const void* vT, void* o_img, void* o_ctx, int B,
                                   int H, int S, int S_pad, int n_img) {
-    if (!q || !k || !vT || !o_img) return fail("mi355_op_attention: null argument");
-    if (n_img < S && !o_ctx) return fail("mi355_op_attention: o_ctx is NULL but S > n_img");
+    if (!q || !k || !vT || !o_img) return errorf("mi355_op_attention: null argument");
+    if (n_img < S && !o_ctx) return errorf("mi355_op_attention: o_ctx is NULL but S > n_img");
     AttnParams a{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)vT, (bf16_t*)o_img, (bf16_t*)o_ctx, B, H, S, S_pad, n_img, 0,
                  g_attn_static >= 2 ? (float)g_attn_static : 0.f};
     HIPCHK(attn_p(a, (hipStream_t)stream));
@@ -1180,14 +1030,14 @@ extern "C" int mi355_op_attention(void* stream, const void* q, const void* k, co
 
 extern "C" int mi355_op_ln_modulate(void* stream, const void* x, const void* shift, const void* scale, void* out, int M, int D,
                                     int rows_per_sample, float eps) {
-    if (!x || !shift || !scale || !out) return fail("mi355_op_ln_modulate: null argument");
+    if (!x || !shift || !scale || !out) return errorf("mi355_op_ln_modulate: null argument");
     LnModParams l;
     memset(&l, 0, sizeof(l));
     // shift / scale are separate [nb][D] tensors: address them relative to `shift`
     l.x = (const bf16_t*)x; l.out = (bf16_t*)out; l.out2 = nullptr; l.mod = (const bf16_t*)shift; l.mod_ld = D;
     l.shift_off = 0;
     const long delta = (const bf16_t*)scale - (const bf16_t*)shift;
-    if (delta < -2147483647L || delta > 2147483647L) return fail("mi355_op_ln_modulate: shift/scale too far apart");
+    if (delta < -2147483647L || delta > 2147483647L) return errorf("mi355_op_ln_modulate: shift/scale too far apart");
     l.scale_off = (int)delta;
     l.M = M; l.D = D; l.rows_per_sample = rows_per_sample; l.eps = eps;
     HIPCHK(lnmod_p(l, (hipStream_t)stream));

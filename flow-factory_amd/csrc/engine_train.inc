@@ -81,21 +81,15 @@ struct TrainEngineState {
     bool wmod_dirty = true;
     bool full = false;                  // mi355_engine_set_train_scope
     bool dirty = true;
-    std::map<std::string, float*> grads;      // parameter name -> fp32 gradient buffer (caller-owned), absent = frozen
+    GradRegistry grads;                 // parameter name -> gradient buffer (caller-owned), absent = frozen
 };
-static std::map<mi355_engine*, TrainEngineState*> g_train_engines;
 
 static void train_mark_dirty(mi355_engine* e) {
-    auto it = g_train_engines.find(e);
-    if (it != g_train_engines.end()) { it->second->dirty = true; it->second->wmod_dirty = true; }
+    if (e->train) { e->train->dirty = true; e->train->wmod_dirty = true; }
 }
-
-static TrainEngineState* train_state(mi355_engine* e) {
-    auto it = g_train_engines.find(e);
-    if (it != g_train_engines.end()) return it->second;
-    TrainEngineState* s = new TrainEngineState();
-    g_train_engines[e] = s;
-    return s;
+static TrainEngineState* train_state(mi355_engine* e) {      // created on first use
+    if (!e->train) e->train = new TrainEngineState();
+    return e->train;
 }
 
 static bool trainable_name(const std::string& n) {
@@ -109,43 +103,35 @@ static bool trainable_name(const std::string& n) {
 }
 
 extern "C" int mi355_engine_set_grad(mi355_engine* e, const char* name, float* grad) {
-    if (!e || !name) return fail("mi355_engine_set_grad: null argument");
-    if (e->slots.find(name) == e->slots.end()) return fail("mi355_engine_set_grad: unknown parameter '%s'", name);
+    if (!e || !name) return errorf("mi355_engine_set_grad: null argument");
+    if (e->slots.find(name) == e->slots.end()) return errorf("mi355_engine_set_grad: unknown parameter '%s'", name);
     TrainEngineState* s = train_state(e);
-    if (!grad) {
-        auto it = s->grads.find(name);
-        if (it != s->grads.end()) { grad_buf_mark(it->second, DT_F32); s->grads.erase(it); }
-        return 0;
-    }
-    if (!strcmp(name, "pos_embed.pos_embed")) return fail("mi355_engine_set_grad: pos_embed.pos_embed is a buffer, not a trainable parameter");
-    if (!trainable_name(name) && !s->full)
-        return fail("mi355_engine_set_grad: '%s' lies outside the transformer blocks' linear layers: select the full scope with "
-                    "mi355_engine_set_train_scope(engine, 1) BEFORE the training-mode forward", name);
-    { auto prev = s->grads.find(name); if (prev != s->grads.end() && prev->second != grad) grad_buf_mark(prev->second, DT_F32); }   // (a re-registration un-marks the buffer it replaces)
-    s->grads[name] = grad;
-    grad_buf_mark(grad, DT_F32);
+    if (grad && !strcmp(name, "pos_embed.pos_embed")) return errorf("mi355_engine_set_grad: pos_embed.pos_embed is a buffer, not a trainable parameter");
+    if (grad && !trainable_name(name) && !s->full)
+        return errorf("mi355_engine_set_grad: '%s' lies outside the transformer blocks' linear layers: select the full scope with "
+                      "mi355_engine_set_train_scope(engine, 1) BEFORE the training-mode forward", name);
+    s->grads.set(name, grad);
     return 0;
 }
 // the same with the buffer's dtype: MI355_F32, or MI355_BF16 for the weights / biases of the linear layers inside the transformer blocks (the
 // kernels that finish those gradients round their fp32 sums to bf16 on the way out: the values of `fp32 buffer -> bf16`, minus the round trip)
 extern "C" int mi355_engine_set_grad_typed(mi355_engine* e, const char* name, void* grad, int dtype) {
     if (dtype == DT_F32 || !grad) return mi355_engine_set_grad(e, name, (float*)grad);
-    if (dtype != DT_BF16) return fail("mi355_engine_set_grad_typed: gradient buffers are fp32 or bf16 (dtype %d)", dtype);
-    if (!e || !name) return fail("mi355_engine_set_grad_typed: null argument");
-    if (!trainable_name(name)) return fail("mi355_engine_set_grad_typed: bf16 gradient buffers are limited to the linear layers inside the transformer blocks ('%s')", name);
+    if (dtype != DT_BF16) return errorf("mi355_engine_set_grad_typed: gradient buffers are fp32 or bf16 (dtype %d)", dtype);
+    if (!e || !name) return errorf("mi355_engine_set_grad_typed: null argument");
+    if (!trainable_name(name)) return errorf("mi355_engine_set_grad_typed: bf16 gradient buffers are limited to the linear layers inside the transformer blocks ('%s')", name);
     const int rc = mi355_engine_set_grad(e, name, (float*)grad);
     if (rc == 0) grad_buf_mark(grad, DT_BF16);
     return rc;
 }
 // 0: gradients of the blocks' linear layers only (default); 1: of every parameter (the next training-mode forward stashes more)
 extern "C" int mi355_engine_set_train_scope(mi355_engine* e, int full) {
-    if (!e) return fail("null engine");
+    if (!e) return errorf("null engine");
     train_state(e)->full = full != 0;
     return 0;
 }
 extern "C" int mi355_engine_clear_grads(mi355_engine* e) {
-    if (!e) return fail("null engine");
-    for (auto& kv : train_state(e)->grads) grad_buf_mark(kv.second, DT_F32);
+    if (!e) return errorf("null engine");
     train_state(e)->grads.clear();
     return 0;
 }
@@ -155,11 +141,7 @@ extern "C" int mi355_engine_grad_supported(mi355_engine* e, const char* name) {
     return trainable_name(name) ? 0 : 2;
 }
 
-static float* grad_of(mi355_engine* e, const std::string& name) {
-    TrainEngineState* s = train_state(e);
-    auto it = s->grads.find(name);
-    return it == s->grads.end() ? nullptr : it->second;
-}
+static float* grad_of(mi355_engine* e, const std::string& name) { return train_state(e)->grads.find(name); }
 
 // ---- transposed weights -------------------------------------------------------------------------------------------
 static int ensure_transposed_weights(mi355_engine* e, hipStream_t st) {
@@ -167,30 +149,19 @@ static int ensure_transposed_weights(mi355_engine* e, hipStream_t st) {
     const int D = e->D, F = e->F, L = e->L;
     const int NO = e->cfg.patch_size * e->cfg.patch_size * e->cfg.out_channels;
     if (!s->arenaT) {
-        size_t off = 0;
-        auto take = [&](int64_t n) { size_t o = off; off += ((size_t)n * 2 + 255) & ~(size_t)255; return o; };
-        std::vector<size_t> offs;
+        Carver c;
+        s->wt.resize(L);
         for (int i = 0; i < L; ++i) {
             const BlockW& b = e->blk[i];
-            offs.push_back(take((int64_t)D * 3 * D)); offs.push_back(take((int64_t)D * D));
-            offs.push_back(take((int64_t)D * 3 * D)); offs.push_back(b.last ? 0 : take((int64_t)D * D));
-            offs.push_back(b.dual ? take((int64_t)D * 3 * D) : 0); offs.push_back(b.dual ? take((int64_t)D * D) : 0);
-            offs.push_back(take((int64_t)D * F)); offs.push_back(take((int64_t)F * D));
-            offs.push_back(b.last ? 0 : take((int64_t)D * F)); offs.push_back(b.last ? 0 : take((int64_t)F * D));
-        }
-        const size_t o_proj = take((int64_t)D * NO);
-        s->bytes = off;
-        if (hipMalloc((void**)&s->arenaT, off) != hipSuccess) return fail("training: hipMalloc of %zu bytes for the transposed weights failed", off);
-        s->wt.resize(L);
-        char* a = s->arenaT;
-        for (int i = 0; i < L; ++i) {
             TrainWT& w = s->wt[i];
-            const size_t* o = &offs[(size_t)i * 10];
-            w.qkv = (bf16_t*)(a + o[0]); w.o = (bf16_t*)(a + o[1]); w.cqkv = (bf16_t*)(a + o[2]); w.co = (bf16_t*)(a + o[3]);
-            w.qkv2 = (bf16_t*)(a + o[4]); w.o2 = (bf16_t*)(a + o[5]); w.ff1 = (bf16_t*)(a + o[6]); w.ff2 = (bf16_t*)(a + o[7]);
-            w.cff1 = (bf16_t*)(a + o[8]); w.cff2 = (bf16_t*)(a + o[9]);
+            c.take(w.qkv, (int64_t)D * 3 * D); c.take(w.o, (int64_t)D * D);
+            c.take(w.cqkv, (int64_t)D * 3 * D); if (!b.last) c.take(w.co, (int64_t)D * D);
+            if (b.dual) { c.take(w.qkv2, (int64_t)D * 3 * D); c.take(w.o2, (int64_t)D * D); }
+            c.take(w.ff1, (int64_t)D * F); c.take(w.ff2, (int64_t)F * D);
+            if (!b.last) { c.take(w.cff1, (int64_t)D * F); c.take(w.cff2, (int64_t)F * D); }
         }
-        s->proj = (bf16_t*)(a + o_proj);
+        c.take(s->proj, (int64_t)D * NO);
+        CHK(c.alloc(&s->arenaT, &s->bytes, false, "training", " for the transposed weights"));
         s->dirty = true;
     }
     if (!s->dirty) return 0;
@@ -219,11 +190,8 @@ static int ensure_transposed_weights(mi355_engine* e, hipStream_t st) {
 }
 
 // ---- training workspace ----------------------------------------------------------------------------------------------
-static std::map<mi355_plan*, mi355_train*> g_trains;
-
 static int train_of(mi355_plan* p, mi355_train** out) {
-    auto it = g_trains.find(p);
-    if (it != g_trains.end()) { *out = it->second; return 0; }
+    if (p->train) { *out = p->train; return 0; }
     mi355_engine* e = p->e;
     const int D = e->D, F = e->F, L = e->L, H = e->cfg.num_heads;
     const int Mi = p->Mi, Mc = p->Mc, Ni = p->Ni;
@@ -233,78 +201,40 @@ static int train_of(mi355_plan* p, mi355_train** out) {
     t->p = p;
     t->Mi_pad = (Mi + 63) / 64 * 64; t->Mc_pad = (Mc + 63) / 64 * 64;
     const int Mmax_pad = t->Mi_pad > t->Mc_pad ? t->Mi_pad : t->Mc_pad;
-    size_t off = 0;
-    auto take = [&](int64_t elems, int esz) { size_t o = off; off += (((size_t)elems * esz) + 255) & ~(size_t)255; return o; };
-    struct BO { size_t v[25]; };
-    std::vector<BO> bo(L);
-    for (int i = 0; i < L; ++i) {
-        const BlockW& b = e->blk[i];
-        size_t* o = bo[i].v;
-        int n = 0;
-        o[n++] = take((int64_t)Mi * D, 2); o[n++] = take((int64_t)Mi * D, 2); o[n++] = b.dual ? take((int64_t)Mi * D, 2) : 0;   // x_in xn xn2
-        o[n++] = take((int64_t)Mi * D, 2); o[n++] = take((int64_t)Mi * D, 2); o[n++] = take((int64_t)Mi * F, 2);               // x_mid xn_mlp pre
-        o[n++] = take((int64_t)Mi * D, 2); o[n++] = b.dual ? take((int64_t)Mi * D, 2) : 0;                                     // o_img o2
-        o[n++] = take((int64_t)Mc * D, 2); o[n++] = take((int64_t)Mc * D, 2);                                                  // c_in cn
-        o[n++] = b.last ? 0 : take((int64_t)Mc * D, 2); o[n++] = b.last ? 0 : take((int64_t)Mc * D, 2);                        // c_mid cn_mlp
-        o[n++] = b.last ? 0 : take((int64_t)Mc * F, 2); o[n++] = take((int64_t)Mc * D, 2);                                     // cpre o_ctx
-        o[n++] = take(qk_el, 2); o[n++] = take(qk_el, 2); o[n++] = take(qk_el, 2);                                             // q k vT
-        o[n++] = b.dual ? take(qk2_el, 2) : 0; o[n++] = b.dual ? take(qk2_el, 2) : 0; o[n++] = b.dual ? take(qk2_el, 2) : 0;    // q2 k2 vT2
-        o[n++] = take((int64_t)p->Bp * H * p->S_pad, 4); o[n++] = b.dual ? take((int64_t)p->Bp * H * Ni_pad, 4) : 0;           // lse lse2
-        o[n++] = take((int64_t)Mi * 2 * H, 4); o[n++] = take((int64_t)Mc * 2 * H, 4); o[n++] = b.dual ? take((int64_t)Mi * 2 * H, 4) : 0;   // rstd
-    }
-    const size_t o_xf = take((int64_t)Mi * D, 2);
-    const size_t o_modc = take((int64_t)p->Bp * e->mod_cols, 2), o_vc = take((int64_t)p->Bp * p->n_lat, 2);
-    const size_t o_dx = take((int64_t)Mi * D, 2), o_dc = take((int64_t)Mc * D, 2), o_dy = take((int64_t)Mi * D, 2), o_dyc = take((int64_t)Mc * D, 2);
-    const size_t o_dpre = take((int64_t)Mi * F, 2), o_hid = take((int64_t)Mi * F, 2), o_dprec = take((int64_t)Mc * F, 2);
-    const size_t o_dxn = take((int64_t)Mi * D, 2), o_dxn2 = take((int64_t)Mi * D, 2), o_dcn = take((int64_t)Mc * D, 2);
-    const size_t o_doi = take((int64_t)Mi * D, 2), o_doc = take((int64_t)Mc * D, 2);
-    const size_t o_doh = take(qk_el, 2), o_v = take(qk_el, 2), o_nld = take((int64_t)p->Bp * H * p->S_pad * 2, 4);
-    const size_t o_dq = take(qk_el, 2), o_dk = take(qk_el, 2), o_dvh = take(qk_el, 2);
-    const size_t o_dqi = take((int64_t)Mi * 3 * D, 2), o_dqc = take((int64_t)Mc * 3 * D, 2);
-    const size_t o_aT = take((int64_t)F * Mmax_pad, 2), o_xT = take((int64_t)F * Mmax_pad, 2);
-    const size_t o_aTc = take((int64_t)F * t->Mc_pad, 2), o_xTc = take((int64_t)F * t->Mc_pad, 2), o_hidc = take((int64_t)Mc * F, 2);
-    const size_t o_dproj = take((int64_t)Mi * 64, 2);
-    const size_t o_delta = take((int64_t)p->Bp * H * p->S_pad, 4), o_dv32 = take((int64_t)p->Bp * p->n_lat, 4);
-    t->part_floats = (size_t)16 * D * D > (size_t)2 * F * D ? (size_t)16 * D * D : (size_t)2 * F * D;
-    const size_t o_part = take((int64_t)t->part_floats, 4), o_cs = take((int64_t)(Mmax_pad / 64 > 64 ? Mmax_pad / 64 : 64) * F, 4), o_zb = take(F > 3 * D ? F : 3 * D, 4);
-    const size_t o_partc = take((int64_t)t->part_floats, 4), o_csc = take((int64_t)(t->Mc_pad / 64 > 64 ? t->Mc_pad / 64 : 64) * F, 4);
-    t->ws_bytes = off;
-    if (hipMalloc((void**)&t->ws, off) != hipSuccess) {
-        delete t;
-        return fail("training: hipMalloc of %zu bytes of activation stash + backward scratch failed", off);
-    }
-    if (hipMemset(t->ws, 0, off) != hipSuccess) { (void)hipFree(t->ws); delete t; return fail("training: hipMemset failed"); }
-    char* w = t->ws;
+    Carver c;
     t->blk.resize(L);
-    for (int i = 0; i < L; ++i) {
+    for (int i = 0; i < L; ++i) {      // (a block without a dual attention / the last block's context stream has no such buffers: they stay null)
+        const BlockW& b = e->blk[i];
         TrainBlk& k = t->blk[i];
-        const size_t* o = bo[i].v;
-        int n = 0;
-        k.x_in = (bf16_t*)(w + o[n++]); k.xn = (bf16_t*)(w + o[n++]); k.xn2 = (bf16_t*)(w + o[n++]);
-        k.x_mid = (bf16_t*)(w + o[n++]); k.xn_mlp = (bf16_t*)(w + o[n++]); k.pre = (bf16_t*)(w + o[n++]);
-        k.o_img = (bf16_t*)(w + o[n++]); k.o2 = (bf16_t*)(w + o[n++]);
-        k.c_in = (bf16_t*)(w + o[n++]); k.cn = (bf16_t*)(w + o[n++]); k.c_mid = (bf16_t*)(w + o[n++]); k.cn_mlp = (bf16_t*)(w + o[n++]);
-        k.cpre = (bf16_t*)(w + o[n++]); k.o_ctx = (bf16_t*)(w + o[n++]);
-        k.q = (bf16_t*)(w + o[n++]); k.k = (bf16_t*)(w + o[n++]); k.vT = (bf16_t*)(w + o[n++]);
-        k.q2 = (bf16_t*)(w + o[n++]); k.k2 = (bf16_t*)(w + o[n++]); k.vT2 = (bf16_t*)(w + o[n++]);
-        k.lse = (float*)(w + o[n++]); k.lse2 = (float*)(w + o[n++]);
-        k.rstd_img = (float*)(w + o[n++]); k.rstd_ctx = (float*)(w + o[n++]); k.rstd2 = (float*)(w + o[n++]);
+        c.take(k.x_in, (int64_t)Mi * D); c.take(k.xn, (int64_t)Mi * D); if (b.dual) c.take(k.xn2, (int64_t)Mi * D);
+        c.take(k.x_mid, (int64_t)Mi * D); c.take(k.xn_mlp, (int64_t)Mi * D); c.take(k.pre, (int64_t)Mi * F);
+        c.take(k.o_img, (int64_t)Mi * D); if (b.dual) c.take(k.o2, (int64_t)Mi * D);
+        c.take(k.c_in, (int64_t)Mc * D); c.take(k.cn, (int64_t)Mc * D);
+        if (!b.last) { c.take(k.c_mid, (int64_t)Mc * D); c.take(k.cn_mlp, (int64_t)Mc * D); c.take(k.cpre, (int64_t)Mc * F); }
+        c.take(k.o_ctx, (int64_t)Mc * D);
+        c.take(k.q, qk_el); c.take(k.k, qk_el); c.take(k.vT, qk_el);
+        if (b.dual) { c.take(k.q2, qk2_el); c.take(k.k2, qk2_el); c.take(k.vT2, qk2_el); }
+        c.take(k.lse, (int64_t)p->Bp * H * p->S_pad); if (b.dual) c.take(k.lse2, (int64_t)p->Bp * H * Ni_pad);
+        c.take(k.rstd_img, (int64_t)Mi * 2 * H); c.take(k.rstd_ctx, (int64_t)Mc * 2 * H); if (b.dual) c.take(k.rstd2, (int64_t)Mi * 2 * H);
     }
-    t->x_final = (bf16_t*)(w + o_xf);
-    t->mod = (bf16_t*)(w + o_modc); t->vnet = (bf16_t*)(w + o_vc);
-    t->dx = (bf16_t*)(w + o_dx); t->dc = (bf16_t*)(w + o_dc); t->dy = (bf16_t*)(w + o_dy); t->dyc = (bf16_t*)(w + o_dyc);
-    t->dpre = (bf16_t*)(w + o_dpre); t->hid = (bf16_t*)(w + o_hid); t->dpre_c = (bf16_t*)(w + o_dprec);
-    t->dxn = (bf16_t*)(w + o_dxn); t->dxn2 = (bf16_t*)(w + o_dxn2); t->dcn = (bf16_t*)(w + o_dcn);
-    t->do_img = (bf16_t*)(w + o_doi); t->do_ctx = (bf16_t*)(w + o_doc);
-    t->doh = (bf16_t*)(w + o_doh); t->v = (bf16_t*)(w + o_v); t->nld = (float*)(w + o_nld);
-    t->dq = (bf16_t*)(w + o_dq); t->dk = (bf16_t*)(w + o_dk); t->dv = (bf16_t*)(w + o_dvh);
-    t->dqkv_img = (bf16_t*)(w + o_dqi); t->dqkv_ctx = (bf16_t*)(w + o_dqc);
-    t->aT = (bf16_t*)(w + o_aT); t->xT = (bf16_t*)(w + o_xT); t->dproj = (bf16_t*)(w + o_dproj);
-    t->delta = (float*)(w + o_delta); t->dv32 = (float*)(w + o_dv32); t->part = (float*)(w + o_part); t->csum = (float*)(w + o_cs);
-    t->zero_bias = (float*)(w + o_zb);
-    t->aT_c = (bf16_t*)(w + o_aTc); t->xT_c = (bf16_t*)(w + o_xTc); t->hid_c = (bf16_t*)(w + o_hidc);
-    t->part_c = (float*)(w + o_partc); t->csum_c = (float*)(w + o_csc);
-    g_trains[p] = t;
+    c.take(t->x_final, (int64_t)Mi * D);
+    c.take(t->mod, (int64_t)p->Bp * e->mod_cols); c.take(t->vnet, (int64_t)p->Bp * p->n_lat);
+    c.take(t->dx, (int64_t)Mi * D); c.take(t->dc, (int64_t)Mc * D); c.take(t->dy, (int64_t)Mi * D); c.take(t->dyc, (int64_t)Mc * D);
+    c.take(t->dpre, (int64_t)Mi * F); c.take(t->hid, (int64_t)Mi * F); c.take(t->dpre_c, (int64_t)Mc * F);
+    c.take(t->dxn, (int64_t)Mi * D); c.take(t->dxn2, (int64_t)Mi * D); c.take(t->dcn, (int64_t)Mc * D);
+    c.take(t->do_img, (int64_t)Mi * D); c.take(t->do_ctx, (int64_t)Mc * D);
+    c.take(t->doh, qk_el); c.take(t->v, qk_el); c.take(t->nld, (int64_t)p->Bp * H * p->S_pad * 2);
+    c.take(t->dq, qk_el); c.take(t->dk, qk_el); c.take(t->dv, qk_el);
+    c.take(t->dqkv_img, (int64_t)Mi * 3 * D); c.take(t->dqkv_ctx, (int64_t)Mc * 3 * D);
+    c.take(t->aT, (int64_t)F * Mmax_pad); c.take(t->xT, (int64_t)F * Mmax_pad);
+    c.take(t->aT_c, (int64_t)F * t->Mc_pad); c.take(t->xT_c, (int64_t)F * t->Mc_pad); c.take(t->hid_c, (int64_t)Mc * F);
+    c.take(t->dproj, (int64_t)Mi * 64);
+    c.take(t->delta, (int64_t)p->Bp * H * p->S_pad); c.take(t->dv32, (int64_t)p->Bp * p->n_lat);
+    t->part_floats = (size_t)16 * D * D > (size_t)2 * F * D ? (size_t)16 * D * D : (size_t)2 * F * D;
+    c.take(t->part, (int64_t)t->part_floats); c.take(t->csum, (int64_t)(Mmax_pad / 64 > 64 ? Mmax_pad / 64 : 64) * F); c.take(t->zero_bias, F > 3 * D ? F : 3 * D);
+    c.take(t->part_c, (int64_t)t->part_floats); c.take(t->csum_c, (int64_t)(t->Mc_pad / 64 > 64 ? t->Mc_pad / 64 : 64) * F);
+    if (c.alloc(&t->ws, &t->ws_bytes, true, "training", " of activation stash + backward scratch") != 0) { delete t; return 1; }
+    p->train = t;
     *out = t;
     return 0;
 }
@@ -315,60 +245,44 @@ static int train_full_of(mi355_train* t) {
     mi355_engine* e = p->e;
     const int D = e->D, L = e->L, T = e->cfg.time_proj_dim, P = e->cfg.pooled_projection_dim, J = e->cfg.joint_attention_dim;
     const int Mi = p->Mi, Mc = p->Mc, Bp = p->Bp;
-    size_t off = 0;
-    auto take = [&](int64_t elems, int esz) { size_t o = off; off += (((size_t)elems * esz) + 255) & ~(size_t)255; return o; };
-    std::vector<size_t> bo;
-    for (int i = 0; i < L; ++i) {
-        const BlockW& b = e->blk[i];
-        bo.push_back(take((int64_t)Mi * D, 2)); bo.push_back(b.dual ? take((int64_t)Mi * D, 2) : 0); bo.push_back(take((int64_t)Mi * D, 2));
-        bo.push_back(b.last ? 0 : take((int64_t)Mc * D, 2)); bo.push_back(b.last ? 0 : take((int64_t)Mc * D, 2));
-    }
-    const int maxw = D > T ? (D > P ? D : P) : (T > P ? T : P);
-    const size_t o_xn = take((int64_t)Mi * D, 2), o_pat = take((int64_t)Mi * e->KP, 2), o_enc = take((int64_t)Mc * J, 2), o_pool = take((int64_t)Bp * P, 2);
-    const size_t o_tp = take((int64_t)Bp * T, 2), o_h1 = take((int64_t)Bp * D, 2), o_p1 = take((int64_t)Bp * D, 2), o_pe = take((int64_t)Bp * D, 2);
-    const size_t o_se = take((int64_t)Bp * D, 2), o_d16 = take((int64_t)64 * e->mod_cols, 2);
-    const size_t o_te = take((int64_t)64 * D, 2), o_dte = take((int64_t)64 * D, 2), o_dh1 = take((int64_t)64 * D, 2), o_pr1 = take((int64_t)64 * D, 2);
-    const size_t o_dse = take((int64_t)64 * D, 2), o_wts = take((int64_t)D * maxw, 2);
-    const size_t o_dm = take((int64_t)Bp * e->mod_cols, 4), o_dwp = take((int64_t)rms_bwd_grid(Bp, p->S) * 4 * 64, 4);
-    if (hipMalloc((void**)&t->wsf, off) != hipSuccess) return fail("training (full scope): hipMalloc of %zu bytes failed", off);
-    if (hipMemset(t->wsf, 0, off) != hipSuccess) return fail("training (full scope): hipMemset failed");
-    t->wsf_bytes = off;
-    char* w = t->wsf;
+    Carver c;
     t->fblk.resize(L);
     for (int i = 0; i < L; ++i) {
+        const BlockW& b = e->blk[i];
         TrainBlkFull& f = t->fblk[i];
-        f.y_o = (bf16_t*)(w + bo[i * 5]); f.y_o2 = (bf16_t*)(w + bo[i * 5 + 1]); f.y_ff = (bf16_t*)(w + bo[i * 5 + 2]);
-        f.y_co = (bf16_t*)(w + bo[i * 5 + 3]); f.y_cff = (bf16_t*)(w + bo[i * 5 + 4]);
+        c.take(f.y_o, (int64_t)Mi * D); if (b.dual) c.take(f.y_o2, (int64_t)Mi * D); c.take(f.y_ff, (int64_t)Mi * D);
+        if (!b.last) { c.take(f.y_co, (int64_t)Mc * D); c.take(f.y_cff, (int64_t)Mc * D); }
     }
-    t->xn_out = (bf16_t*)(w + o_xn); t->patches = (bf16_t*)(w + o_pat); t->enc = (bf16_t*)(w + o_enc); t->pool = (bf16_t*)(w + o_pool);
-    t->tproj = (bf16_t*)(w + o_tp); t->h1 = (bf16_t*)(w + o_h1); t->p1 = (bf16_t*)(w + o_p1); t->pemb = (bf16_t*)(w + o_pe); t->semb = (bf16_t*)(w + o_se);
-    t->dmod16 = (bf16_t*)(w + o_d16); t->temb = (bf16_t*)(w + o_te); t->dtemb = (bf16_t*)(w + o_dte); t->dh1 = (bf16_t*)(w + o_dh1);
-    t->pre1 = (bf16_t*)(w + o_pr1); t->dsemb = (bf16_t*)(w + o_dse); t->wT_small = (bf16_t*)(w + o_wts);
-    t->dmod = (float*)(w + o_dm); t->dw_part = (float*)(w + o_dwp);
+    const int maxw = D > T ? (D > P ? D : P) : (T > P ? T : P);
+    c.take(t->xn_out, (int64_t)Mi * D); c.take(t->patches, (int64_t)Mi * e->KP); c.take(t->enc, (int64_t)Mc * J); c.take(t->pool, (int64_t)Bp * P);
+    c.take(t->tproj, (int64_t)Bp * T); c.take(t->h1, (int64_t)Bp * D); c.take(t->p1, (int64_t)Bp * D); c.take(t->pemb, (int64_t)Bp * D);
+    c.take(t->semb, (int64_t)Bp * D); c.take(t->dmod16, (int64_t)64 * e->mod_cols);
+    c.take(t->temb, (int64_t)64 * D); c.take(t->dtemb, (int64_t)64 * D); c.take(t->dh1, (int64_t)64 * D); c.take(t->pre1, (int64_t)64 * D);
+    c.take(t->dsemb, (int64_t)64 * D); c.take(t->wT_small, (int64_t)D * maxw);
+    c.take(t->dmod, (int64_t)Bp * e->mod_cols); c.take(t->dw_part, (int64_t)rms_bwd_grid(Bp, p->S) * 4 * 64);
+    CHK(c.alloc(&t->wsf, &t->wsf_bytes, true, "training (full scope)"));
     return 0;
 }
 
 static void train_release(mi355_plan* p) {
-    auto it = g_trains.find(p);
-    if (it == g_trains.end()) return;
-    if (it->second->wsf) (void)hipFree(it->second->wsf);
-    if (it->second->ws) (void)hipFree(it->second->ws);
-    for (hipEvent_t ev : it->second->ev) (void)hipEventDestroy(ev);
-    if (it->second->side) (void)hipStreamDestroy(it->second->side);
-    delete it->second;
-    g_trains.erase(it);
+    mi355_train* t = p->train;
+    if (!t) return;
+    if (t->wsf) (void)hipFree(t->wsf);
+    if (t->ws) (void)hipFree(t->ws);
+    for (hipEvent_t ev : t->ev) (void)hipEventDestroy(ev);
+    if (t->side) (void)hipStreamDestroy(t->side);
+    delete t;
+    p->train = nullptr;
 }
 static void train_release_engine(mi355_engine* e) {
-    auto it = g_train_engines.find(e);
-    if (it == g_train_engines.end()) return;
-    if (it->second->arenaT) (void)hipFree(it->second->arenaT);
-    if (it->second->wmodT) (void)hipFree(it->second->wmodT);
-    delete it->second;
-    g_train_engines.erase(it);
+    if (!e->train) return;
+    if (e->train->arenaT) (void)hipFree(e->train->arenaT);
+    if (e->train->wmodT) (void)hipFree(e->train->wmodT);
+    delete e->train;
+    e->train = nullptr;
 }
 extern "C" int64_t mi355_plan_training_bytes(mi355_plan* p) {
-    auto it = g_trains.find(p);
-    return it == g_trains.end() ? 0 : (int64_t)(it->second->ws_bytes + it->second->wsf_bytes);
+    return p && p->train ? (int64_t)(p->train->ws_bytes + p->train->wsf_bytes) : 0;
 }
 
 // ---- training-mode forward: forward_core with per-block buffers ---------------------------------------------------
@@ -417,7 +331,7 @@ static int train_side_init(mi355_train* t) {
     if (err != hipSuccess) {
         for (hipEvent_t a : ev) (void)hipEventDestroy(a);
         if (side) (void)hipStreamDestroy(side);
-        return fail("training: side stream / event creation failed: %s", hipGetErrorString(err));
+        return errorf("training: side stream / event creation failed: %s", hipGetErrorString(err));
     }
     t->ev = ev;
     t->side = side;
@@ -518,8 +432,8 @@ extern "C" int mi355_denoise_step_train(mi355_plan* p, void* stream, const void*
                                         int next_in_dtype, const float* sigma, const float* sigma_next, const float* eta, int scalar_stride,
                                         float sigma_max, int dynamics, int compute_log_prob, float* next_f32, float* mean_out,
                                         float* noise_pred_out, float* log_prob, float* std_dev_t, float* dt) {
-    if (!p || !latents || !t) return fail("mi355_denoise_step_train: null argument");
-    if (!next_in) return fail("mi355_denoise_step_train: the differentiable step is the REPLAY of a stored transition: next_in is required");
+    if (!p || !latents || !t) return errorf("mi355_denoise_step_train: null argument");
+    if (!next_in) return errorf("mi355_denoise_step_train: the differentiable step is the REPLAY of a stored transition: next_in is required");
     CHK(mi355_engine_weights_ready(p->e));
     hipStream_t st = (hipStream_t)stream;
     CHK(update_score_bounds(p->e, st));
@@ -632,7 +546,7 @@ static int wgrad(mi355_train* t, hipStream_t st, const bf16_t* dY, long ldY, int
         g.out_f32 = gw; g.k_split = 1;
         HIPCHK(gemm_p(g, ws));
     } else {
-        if ((size_t)N * K > t->part_floats) return fail("wgrad: a %d x %d gradient does not fit the split-K scratch", N, K);   // (bf16 output, single split)
+        if ((size_t)N * K > t->part_floats) return errorf("wgrad: a %d x %d gradient does not fit the split-K scratch", N, K);   // (bf16 output, single split)
         g.out_f32 = w.part; g.k_split = split; g.split_stride = (long)N * K;
         HIPCHK(gemm_p(g, ws));
         hipError_t fe = hipErrorNotSupported;
@@ -706,7 +620,7 @@ static int full_scope_tail(mi355_plan* p, mi355_train* t, hipStream_t st) {
     for (const char* c : cond) any = any || GN(c);
     if (!any) return 0;
     if (!ts->wmodT) {
-        if (hipMalloc((void**)&ts->wmodT, (size_t)D * e->mod_cols * 2) != hipSuccess) return fail("training: hipMalloc of the transposed modulation weights failed");
+        if (hipMalloc((void**)&ts->wmodT, (size_t)D * e->mod_cols * 2) != hipSuccess) return errorf("training: hipMalloc of the transposed modulation weights failed");
         ts->wmod_dirty = true;
     }
     if (ts->wmod_dirty) {
@@ -756,11 +670,10 @@ extern "C" int mi355_denoise_step_backward(mi355_plan* p, void* stream, const vo
                                            int next_in_dtype, const float* sigma, const float* sigma_next, const float* eta, int scalar_stride,
                                            float sigma_max, int dynamics, int compute_log_prob, const float* g_log_prob, const float* g_noise_pred,
                                            const float* g_mean) {
-    if (!p || !latents || !next_in) return fail("mi355_denoise_step_backward: null argument");
-    auto it = g_trains.find(p);
-    if (it == g_trains.end()) return fail("mi355_denoise_step_backward: no training-mode forward has run on this plan");
-    if (get_attn_variant() < 1) return fail("mi355_denoise_step_backward: needs the pre-scaled-q attention variant (mi355_tune_set(1, 1))");
-    mi355_train* t = it->second;
+    if (!p || !latents || !next_in) return errorf("mi355_denoise_step_backward: null argument");
+    if (!p->train) return errorf("mi355_denoise_step_backward: no training-mode forward has run on this plan");
+    if (get_attn_variant() < 1) return errorf("mi355_denoise_step_backward: needs the pre-scaled-q attention variant (mi355_tune_set(1, 1))");
+    mi355_train* t = p->train;
     mi355_engine* e = p->e;
     hipStream_t st = (hipStream_t)stream;
     CHK(ensure_transposed_weights(e, st));
@@ -774,9 +687,9 @@ extern "C" int mi355_denoise_step_backward(mi355_plan* p, void* stream, const vo
     auto G = [&](int i, const char* leaf) { return grad_of(e, "transformer_blocks." + std::to_string(i) + leaf); };
     const bool full = t->fwd_full;
     if (!full)
-        for (auto& kv : ts->grads)
+        for (auto& kv : ts->grads.grads)
             if (!trainable_name(kv.first))
-                return fail("mi355_denoise_step_backward: a gradient is registered for '%s' but the forward ran in the default scope "
+                return errorf("mi355_denoise_step_backward: a gradient is registered for '%s' but the forward ran in the default scope "
                             "(mi355_engine_set_train_scope(engine, 1) must precede it)", kv.first.c_str());
     float* dmod = full ? t->dmod : nullptr;
     if (full) HIPCHK(hipMemsetAsync(t->dmod, 0, (size_t)p->Bp * e->mod_cols * 4, st));
@@ -918,7 +831,7 @@ extern "C" int mi355_denoise_step_backward(mi355_plan* p, void* stream, const vo
 // [B][H][S_pad][64].  Scratch is allocated and freed inside (test helper, synchronises).
 extern "C" int mi355_op_attention_fwd_bwd(void* stream, const void* q, const void* k, const void* vT, const void* d_o, void* o, void* dq, void* dk,
                                           void* dv, int B, int H, int S, int S_pad) {
-    if (!q || !k || !vT || !d_o || !o || !dq || !dk || !dv) return fail("mi355_op_attention_fwd_bwd: null argument");
+    if (!q || !k || !vT || !d_o || !o || !dq || !dk || !dv) return errorf("mi355_op_attention_fwd_bwd: null argument");
     hipStream_t st = (hipStream_t)stream;
     const size_t el = (size_t)B * H * S_pad * 64;
     char* ws = nullptr;
@@ -938,6 +851,6 @@ extern "C" int mi355_op_attention_fwd_bwd(void* stream, const void* q, const voi
     if (err == hipSuccess) err = launch_attention_bwd(ab, st);
     if (err == hipSuccess) err = hipStreamSynchronize(st);
     (void)hipFree(ws);
-    if (err != hipSuccess) return fail("mi355_op_attention_fwd_bwd: %s", hipGetErrorString(err));
+    if (err != hipSuccess) return errorf("mi355_op_attention_fwd_bwd: %s", hipGetErrorString(err));
     return 0;
 }

@@ -26,8 +26,6 @@ using namespace mi355;
 
 namespace {
 
-struct FSlot { void* dst; int dst_dt; int64_t numel; bool bound; };
-
 struct DoubleW {
     bf16_t *w_qk, *w_v, *w_o, *w_cqk, *w_cv, *w_co, *w_ff1, *w_ff2, *w_cff1, *w_cff2;
     float *b_qk, *b_v, *b_o, *b_cqk, *b_cv, *b_co, *b_ff1, *b_ff2, *b_cff1, *b_cff2;
@@ -43,59 +41,22 @@ struct SingleW {
     float bound = 0.f;
 };
 
-// value-round an fp32 to a storage dtype on the host (bf16 / fp16 round-to-nearest-even)
-float host_round(float v, int dt) {
-    if (dt == DT_F32) return v;
-    if (dt == DT_BF16) {
-        unsigned u;
-        memcpy(&u, &v, 4);
-        u += 0x7fffu + ((u >> 16) & 1u);
-        u &= 0xffff0000u;
-        memcpy(&v, &u, 4);
-        return v;
-    }
-    return (float)(_Float16)v;
-}
-
 }  // namespace
 
-struct mi355_flux {
+struct FluxTrainState;
+struct mi355_flux_train;
+
+struct mi355_flux : ParamTable {
     mi355_flux_cfg cfg;
     int D, F, L, LS, H;
     int mod_cols, mod_out;
-    char* arena16 = nullptr;
-    char* arena32 = nullptr;
-    size_t used16 = 0, used32 = 0;
     bf16_t *w_x, *w_ctx, *w_t1, *w_t2, *w_g1, *w_g2, *w_p1, *w_p2, *w_mod, *w_proj;
     float *b_x, *b_ctx, *b_t1, *b_t2, *b_g1, *b_g2, *b_p1, *b_p2, *b_mod, *b_proj;
     std::vector<DoubleW> dbl;
     std::vector<SingleW> sgl;
-    std::map<std::string, FSlot> slots;
-    std::vector<std::string> names;
     bool bounds_dirty = true;
     int bounds_ver = 0;          // bumped whenever the per-block score bounds are recomputed (they are baked into a captured graph)
-
-    bf16_t* a16(int64_t n) {
-        size_t bytes = ((size_t)n * 2 + 255) & ~(size_t)255;
-        char* p = arena16 ? arena16 + used16 : nullptr;
-        used16 += bytes;
-        return (bf16_t*)p;
-    }
-    float* a32(int64_t n) {
-        size_t bytes = ((size_t)n * 4 + 255) & ~(size_t)255;
-        char* p = arena32 ? arena32 + used32 : nullptr;
-        used32 += bytes;
-        return (float*)p;
-    }
-    void reg(const std::string& name, void* dst, int dt, int64_t numel) {
-        if (!arena16) return;
-        slots[name] = FSlot{dst, dt, numel, false};
-        names.push_back(name);
-    }
-    void lin(const std::string& name, bf16_t* w, float* b, int out_f, int in_f) {
-        reg(name + ".weight", w, DT_BF16, (int64_t)out_f * in_f);
-        reg(name + ".bias", b, DT_F32, out_f);
-    }
+    FluxTrainState* train = nullptr;   // training-mode state (flux_train.inc), created on first use
     void layout();
 };
 
@@ -185,16 +146,7 @@ extern "C" int mi355_flux_create(const mi355_flux_cfg* cfg, mi355_flux** out) {
     e->H = cfg->num_heads; e->D = cfg->num_heads * cfg->head_dim; e->F = 4 * e->D;
     e->L = cfg->num_layers; e->LS = cfg->num_single_layers;
     e->layout();
-    const size_t cap16 = e->used16, cap32 = e->used32;
-    hipError_t e1 = hipMalloc((void**)&e->arena16, cap16);
-    hipError_t e2 = hipMalloc((void**)&e->arena32, cap32);
-    if (e1 != hipSuccess || e2 != hipSuccess) {
-        int r = errorf("mi355_flux_create: hipMalloc of %zu + %zu bytes failed", cap16, cap32);
-        if (e->arena16) (void)hipFree(e->arena16);
-        if (e->arena32) (void)hipFree(e->arena32);
-        delete e;
-        return r;
-    }
+    if (e->alloc("mi355_flux_create") != 0) { delete e; return 1; }
     e->layout();
     *out = e;
     return 0;
@@ -203,38 +155,21 @@ extern "C" int mi355_flux_create(const mi355_flux_cfg* cfg, mi355_flux** out) {
 extern "C" int mi355_flux_destroy(mi355_flux* e) {
     if (!e) return 0;
     flux_train_release_engine(e);
-    if (e->arena16) (void)hipFree(e->arena16);
-    if (e->arena32) (void)hipFree(e->arena32);
+    e->release();
     delete e;
     return 0;
 }
 extern "C" int mi355_flux_num_params(mi355_flux* e) { return e ? (int)e->names.size() : 0; }
-extern "C" const char* mi355_flux_param_name(mi355_flux* e, int i) {
-    if (!e || i < 0 || i >= (int)e->names.size()) return nullptr;
-    return e->names[i].c_str();
-}
+extern "C" const char* mi355_flux_param_name(mi355_flux* e, int i) { return e ? e->param_name(i) : nullptr; }
 extern "C" int mi355_flux_bind_weight(mi355_flux* e, const char* name, const void* src, int dtype, int ndim, const int64_t* shape,
                                       void* stream) {
     if (!e || !name || !src) return errorf("mi355_flux_bind_weight: null argument");
-    auto it = e->slots.find(name);
-    if (it == e->slots.end()) return errorf("mi355_flux_bind_weight: unknown parameter '%s'", name);
-    int64_t n = 1;
-    for (int i = 0; i < ndim; ++i) n *= shape[i];
-    if (n != it->second.numel)
-        return errorf("mi355_flux_bind_weight: '%s' has %lld elements, expected %lld", name, (long long)n, (long long)it->second.numel);
-    if (dtype < 0 || dtype > 2) return errorf("mi355_flux_bind_weight: bad dtype %d", dtype);
-    HIPCHK(launch_convert(src, dtype, it->second.dst, it->second.dst_dt, n, (hipStream_t)stream));
-    it->second.bound = true;
+    CHK(e->bind("mi355_flux_bind_weight", name, src, dtype, ndim, shape, (hipStream_t)stream));
     if (strstr(name, ".norm_")) e->bounds_dirty = true;
     flux_train_mark_dirty(e);          // the transposed copies the backward's dgrad GEMMs read are stale
     return 0;
 }
-extern "C" int mi355_flux_weights_ready(mi355_flux* e) {
-    if (!e) return errorf("null engine");
-    for (auto& kv : e->slots)
-        if (!kv.second.bound) return errorf("parameter '%s' has not been bound", kv.first.c_str());
-    return 0;
-}
+extern "C" int mi355_flux_weights_ready(mi355_flux* e) { return e ? e->ready() : errorf("null engine"); }
 
 // -------------------------------------------------------------------------------------- plan
 struct mi355_flux_plan {
@@ -257,12 +192,8 @@ struct mi355_flux_plan {
     char* ws_side = nullptr;
     bf16_t *qkbuf_c = nullptr, *big_c = nullptr;
     std::vector<hipEvent_t> ev_join, ev_fork;   // per double block: text q|k|v ready (side -> main), attention done (main -> side); [L] = start / end
-    // hipGraph of the N-step loop (opt-in, mi355_tune_set key 16): captured on a plan-owned stream on the second call of a configuration
-    hipGraphExec_t gexec = nullptr;
-    hipStream_t cap_stream = nullptr;
-    bool warmed = false;
-    int g_steps = -1, g_dyn = -1, g_storage = -1, g_init = -1, g_clp = -1, g_noise = -1, g_bounds = -1, g_two = -1, g_gemm = -1, g_attn = -1, g_tune = -1;
-    float g_sigma_max = 0.f;
+    RolloutGraph graph;                 // hipGraph of the N-step loop (mi355_tune_set key 16), captured on the second call of a configuration
+    mi355_flux_train* train = nullptr;  // training workspace (flux_train.inc), created by the first training-mode forward
 };
 
 extern "C" int mi355_flux_plan_create(mi355_flux* e, int batch, int latent_h, int latent_w, int n_text, int max_steps,
@@ -277,50 +208,26 @@ extern "C" int mi355_flux_plan_create(mi355_flux* e, int batch, int latent_h, in
     p->n_lat = (int64_t)p->Ni * e->cfg.in_channels;
     const int D = e->D, F = e->F;
     const int64_t rows_cond = (int64_t)max_steps * batch;
-    size_t off = 0;
-    auto take = [&](int64_t elems, int esz) {
-        size_t o = off;
-        off += (((size_t)elems * esz) + 255) & ~(size_t)255;
-        return o;
-    };
     const int64_t qk_el = (int64_t)batch * e->H * p->S_pad * 128;
     const int64_t nl = (int64_t)batch * p->n_lat;
-    size_t o_l16 = take(nl, 2), o_x = take((int64_t)p->Mi * D, 2), o_c = take((int64_t)p->Mc * D, 2), o_c0 = take((int64_t)p->Mc * D, 2);
-    size_t o_xn = take((int64_t)p->Mi * D, 2), o_cn = take((int64_t)p->Mc * D, 2);
-    size_t o_y = take((int64_t)p->M * D, 2), o_yn = take((int64_t)p->M * D, 2), o_qkb = take((int64_t)p->M * 2 * D, 2);
-    size_t o_q = take(qk_el, 2), o_k = take(qk_el, 2), o_vT = take(qk_el, 2);
-    size_t o_oi = take((int64_t)p->Mi * D, 2), o_oc = take((int64_t)p->Mc * D, 2);
-    size_t o_big = take((int64_t)p->M * (D + F), 2);        // single blocks: [attn | gelu(mlp)]; double blocks: ff hidden (img, then ctx)
-    size_t o_v = take(nl, 2);
-    size_t o_tp = take(rows_cond * e->cfg.time_proj_dim, 2), o_gp = take((int64_t)batch * e->cfg.time_proj_dim, 2);
-    size_t o_h1 = take(rows_cond * D, 2), o_p1 = take((int64_t)batch * D, 2), o_pemb = take((int64_t)batch * D, 2);
-    size_t o_gemb = take((int64_t)batch * D, 2), o_semb = take(rows_cond * D, 2), o_mod = take(rows_cond * e->mod_cols, 2);
-    size_t o_cs = take((int64_t)p->S * 64, 8);
-    size_t o_t = take(rows_cond, 4), o_g = take(batch, 4), o_sc = take(3 * (int64_t)max_steps, 4);
-    size_t o_ii = take(nl, 4), o_it = take((int64_t)(max_steps + 1) * nl, 4), o_in = take((int64_t)max_steps * nl, 4);
-    size_t o_il = take((int64_t)max_steps * batch, 4);
-    size_t o_ipe = take((int64_t)batch * p->Nt * e->cfg.joint_attention_dim, 2), o_ipp = take((int64_t)batch * e->cfg.pooled_projection_dim, 2);
-    p->ws_bytes = off;
-    if (hipMalloc((void**)&p->ws, off) != hipSuccess) {
-        int r = errorf("mi355_flux_plan_create: hipMalloc of %zu bytes failed", off);
-        delete p;
-        return r;
-    }
-    if (hipMemset(p->ws, 0, off) != hipSuccess) {   // padded key rows / columns of q,k,vT must stay finite
-        (void)hipFree(p->ws);
-        delete p;
-        return errorf("mi355_flux_plan_create: hipMemset failed");
-    }
-    char* w = p->ws;
-    p->lat16 = (bf16_t*)(w + o_l16); p->x = (bf16_t*)(w + o_x); p->c = (bf16_t*)(w + o_c); p->c0 = (bf16_t*)(w + o_c0);
-    p->xn = (bf16_t*)(w + o_xn); p->cn = (bf16_t*)(w + o_cn); p->y = (bf16_t*)(w + o_y); p->yn = (bf16_t*)(w + o_yn);
-    p->qkbuf = (bf16_t*)(w + o_qkb); p->q = (bf16_t*)(w + o_q); p->k = (bf16_t*)(w + o_k); p->vT = (bf16_t*)(w + o_vT);
-    p->o_img = (bf16_t*)(w + o_oi); p->o_ctx = (bf16_t*)(w + o_oc); p->big = (bf16_t*)(w + o_big); p->v = (bf16_t*)(w + o_v);
-    p->tproj = (bf16_t*)(w + o_tp); p->gproj = (bf16_t*)(w + o_gp); p->h1 = (bf16_t*)(w + o_h1); p->p1 = (bf16_t*)(w + o_p1);
-    p->pemb = (bf16_t*)(w + o_pemb); p->gemb = (bf16_t*)(w + o_gemb); p->semb = (bf16_t*)(w + o_semb); p->mod_all = (bf16_t*)(w + o_mod);
-    p->cs = (float2*)(w + o_cs); p->t_dev = (float*)(w + o_t); p->g_dev = (float*)(w + o_g); p->scal = (float*)(w + o_sc);
-    p->io_init = w + o_ii; p->io_traj = w + o_it; p->io_noise = (float*)(w + o_in); p->io_lp = (float*)(w + o_il);
-    p->io_pe = (bf16_t*)(w + o_ipe); p->io_pp = (bf16_t*)(w + o_ipp);
+    Carver c;
+    c.take(p->lat16, nl); c.take(p->x, (int64_t)p->Mi * D); c.take(p->c, (int64_t)p->Mc * D); c.take(p->c0, (int64_t)p->Mc * D);
+    c.take(p->xn, (int64_t)p->Mi * D); c.take(p->cn, (int64_t)p->Mc * D);
+    c.take(p->y, (int64_t)p->M * D); c.take(p->yn, (int64_t)p->M * D); c.take(p->qkbuf, (int64_t)p->M * 2 * D);
+    c.take(p->q, qk_el); c.take(p->k, qk_el); c.take(p->vT, qk_el);
+    c.take(p->o_img, (int64_t)p->Mi * D); c.take(p->o_ctx, (int64_t)p->Mc * D);
+    c.take(p->big, (int64_t)p->M * (D + F));        // single blocks: [attn | gelu(mlp)]; double blocks: ff hidden (img, then ctx)
+    c.take(p->v, nl);
+    c.take(p->tproj, rows_cond * e->cfg.time_proj_dim); c.take(p->gproj, (int64_t)batch * e->cfg.time_proj_dim);
+    c.take(p->h1, rows_cond * D); c.take(p->p1, (int64_t)batch * D); c.take(p->pemb, (int64_t)batch * D);
+    c.take(p->gemb, (int64_t)batch * D); c.take(p->semb, rows_cond * D); c.take(p->mod_all, rows_cond * e->mod_cols);
+    c.take(p->cs, (int64_t)p->S * 64);
+    c.take(p->t_dev, rows_cond); c.take(p->g_dev, batch); c.take(p->scal, 3 * (int64_t)max_steps);
+    c.take(p->io_init, nl * 4); c.take(p->io_traj, (int64_t)(max_steps + 1) * nl * 4); c.take(p->io_noise, (int64_t)max_steps * nl);
+    c.take(p->io_lp, (int64_t)max_steps * batch);
+    c.take(p->io_pe, (int64_t)batch * p->Nt * e->cfg.joint_attention_dim); c.take(p->io_pp, (int64_t)batch * e->cfg.pooled_projection_dim);
+    // zeroed: the padded key rows / columns of q, k, vT must stay finite
+    if (c.alloc(&p->ws, &p->ws_bytes, true, "mi355_flux_plan_create") != 0) { delete p; return 1; }
     // rotary table of the joint sequence [txt (ids 0) | img (0, row, col)]: FluxPosEmbed evaluates the angles in float64
     // (get_1d_rotary_pos_embed(freqs_dtype=float64)) and casts cos / sin to fp32
     {
@@ -350,8 +257,7 @@ extern "C" int mi355_flux_plan_create(mi355_flux* e, int batch, int latent_h, in
 extern "C" int mi355_flux_plan_destroy(mi355_flux_plan* p) {
     if (!p) return 0;
     flux_train_release(p);
-    if (p->gexec) (void)hipGraphExecDestroy(p->gexec);
-    if (p->cap_stream) (void)hipStreamDestroy(p->cap_stream);
+    p->graph.release();
     for (hipEvent_t ev : p->ev_join) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : p->ev_fork) (void)hipEventDestroy(ev);
     if (p->side) (void)hipStreamDestroy(p->side);
@@ -496,10 +402,10 @@ bool flux_two_stream_wanted(const mi355_flux_plan* p) {
 
 int flux_two_stream_init(mi355_flux_plan* p) {
     if (p->side) return 0;
-    const size_t qkb = (((size_t)p->Mc * 2 * p->e->D * 2) + 255) & ~(size_t)255, big = (((size_t)p->Mc * p->e->F * 2) + 255) & ~(size_t)255;
-    HIPCHK(hipMalloc((void**)&p->ws_side, qkb + big));
-    p->qkbuf_c = (bf16_t*)p->ws_side;
-    p->big_c = (bf16_t*)(p->ws_side + qkb);
+    Carver c;
+    size_t bytes;
+    c.take(p->qkbuf_c, (int64_t)p->Mc * 2 * p->e->D); c.take(p->big_c, (int64_t)p->Mc * p->e->F);
+    CHK(c.alloc(&p->ws_side, &bytes, false, "flux two-stream forward"));
     for (int i = 0; i <= p->e->L; ++i) {
         hipEvent_t a, b;
         HIPCHK(hipEventCreateWithFlags(&a, hipEventDisableTiming));
@@ -698,47 +604,15 @@ extern "C" int mi355_flux_rollout(mi355_flux_plan* p, void* stream, int n_steps,
         }
         return 0;
     };
-    bool launched = false;
-    if (g_flux_graph && p->warmed) {
+    if (g_flux_graph && p->graph.warmed) {
         const int two = (int)flux_two_stream_wanted(p);
-        const bool same = p->gexec && p->g_steps == n_steps && p->g_dyn == dynamics && p->g_storage == storage_dtype && p->g_init == init_dtype &&
-                          p->g_clp == clp && p->g_noise == (int)(step_noise != nullptr) && p->g_sigma_max == sigma_max &&
-                          p->g_bounds == p->e->bounds_ver && p->g_two == two && p->g_gemm == get_gemm_variant() && p->g_attn == get_attn128_variant() && p->g_tune == tune_epoch();
-        if (!same) {
-            if (two) CHK(flux_two_stream_init(p));              // streams / events / buffers are created outside the capture
-            if (p->gexec) { (void)hipGraphExecDestroy(p->gexec); p->gexec = nullptr; }
-            hipGraph_t graph = nullptr;
-            hipError_t ce = hipSuccess;
-            if (!p->cap_stream) ce = hipStreamCreateWithFlags(&p->cap_stream, hipStreamNonBlocking);
-            if (ce == hipSuccess) ce = hipStreamBeginCapture(p->cap_stream, hipStreamCaptureModeRelaxed);
-            if (ce == hipSuccess) {
-                const int rc = body(p->cap_stream);             // nothing executes: launches / D2D copies become graph nodes
-                ce = hipStreamEndCapture(p->cap_stream, &graph);
-                if (rc != 0 || ce != hipSuccess || !graph) {
-                    if (graph) (void)hipGraphDestroy(graph);
-                    graph = nullptr;
-                }
-            }
-            if (graph) {
-                ce = hipGraphInstantiate(&p->gexec, graph, nullptr, nullptr, 0);
-                (void)hipGraphDestroy(graph);
-                if (ce != hipSuccess) p->gexec = nullptr;
-            }
-            if (!p->gexec) {                                    // no silent fallback: the caller chooses eager launches with key 16 = 0
-                const hipError_t last = hipGetLastError();
-                return errorf("mi355_flux_rollout: hipGraph capture / instantiation of the %d-step loop failed (%s); mi355_tune_set(16, 0) "
-                              "selects eager launches", n_steps, hipGetErrorString(ce != hipSuccess ? ce : last));
-            }
-            p->g_steps = n_steps; p->g_dyn = dynamics; p->g_storage = storage_dtype; p->g_init = init_dtype; p->g_clp = clp;
-            p->g_noise = (int)(step_noise != nullptr); p->g_sigma_max = sigma_max; p->g_bounds = p->e->bounds_ver; p->g_two = two;
-            p->g_gemm = get_gemm_variant(); p->g_attn = get_attn128_variant(); p->g_tune = tune_epoch();
-        }
-        HIPCHK(hipGraphLaunch(p->gexec, st));
-        launched = true;
-    }
-    if (!launched) {
+        const int key[RolloutGraph::NKEY] = {n_steps, dynamics, storage_dtype, init_dtype, clp, (int)(step_noise != nullptr), float_bits(sigma_max),
+                                             p->e->bounds_ver, two, get_gemm_variant(), get_attn128_variant(), tune_epoch()};
+        // (streams / events / buffers are created outside the capture)
+        CHK(p->graph.launch(key, st, "mi355_flux_rollout", n_steps, 16, [&] { return two ? flux_two_stream_init(p) : 0; }, body));
+    } else {
         CHK(body(st));
-        p->warmed = true;
+        p->graph.warmed = true;
     }
     if (keep_slot_host && out_latents)
         for (int i = 0; i <= n_steps; ++i)

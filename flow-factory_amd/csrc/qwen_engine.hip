@@ -28,8 +28,6 @@ using namespace mi355;
 
 namespace {
 
-struct QSlot { void* dst; int dst_dt; int64_t numel; bool bound; };
-
 struct QBlockW {
     bf16_t *w_qk, *w_v, *w_o, *w_cqk, *w_cv, *w_co, *w_ff1, *w_ff2, *w_cff1, *w_cff2;
     float *b_qk, *b_v, *b_o, *b_cqk, *b_cv, *b_co, *b_ff1, *b_ff2, *b_cff1, *b_cff2;
@@ -46,57 +44,21 @@ struct QTrainBlk {
     float *lse, *rstd_img, *rstd_ctx;
 };
 
-float q_host_round(float v, int dt) {
-    if (dt == DT_F32) return v;
-    if (dt == DT_BF16) {
-        unsigned u;
-        memcpy(&u, &v, 4);
-        u += 0x7fffu + ((u >> 16) & 1u);
-        u &= 0xffff0000u;
-        memcpy(&v, &u, 4);
-        return v;
-    }
-    return (float)(_Float16)v;
-}
-
 }  // namespace
 
-struct mi355_qwen {
+struct QwenTrainState;
+struct mi355_qwen_train;
+
+struct mi355_qwen : ParamTable {
     mi355_qwen_cfg cfg;
     int D, F, L, H;
     int mod_cols, mod_out;
-    char* arena16 = nullptr;
-    char* arena32 = nullptr;
-    size_t used16 = 0, used32 = 0;
     bf16_t *w_x, *w_ctx, *w_t1, *w_t2, *w_mod, *w_proj;
     float *b_x, *b_ctx, *b_t1, *b_t2, *b_mod, *b_proj, *txt_norm;
     std::vector<QBlockW> blk;
-    std::map<std::string, QSlot> slots;
-    std::vector<std::string> names;
     bool bounds_dirty = true;
     int bounds_ver = 0;          // bumped whenever the per-block score bounds are recomputed (they are baked into a captured graph)
-
-    bf16_t* a16(int64_t n) {
-        size_t bytes = ((size_t)n * 2 + 255) & ~(size_t)255;
-        char* p = arena16 ? arena16 + used16 : nullptr;
-        used16 += bytes;
-        return (bf16_t*)p;
-    }
-    float* a32(int64_t n) {
-        size_t bytes = ((size_t)n * 4 + 255) & ~(size_t)255;
-        char* p = arena32 ? arena32 + used32 : nullptr;
-        used32 += bytes;
-        return (float*)p;
-    }
-    void reg(const std::string& name, void* dst, int dt, int64_t numel) {
-        if (!arena16) return;
-        slots[name] = QSlot{dst, dt, numel, false};
-        names.push_back(name);
-    }
-    void lin(const std::string& name, bf16_t* w, float* b, int out_f, int in_f) {
-        reg(name + ".weight", w, DT_BF16, (int64_t)out_f * in_f);
-        reg(name + ".bias", b, DT_F32, out_f);
-    }
+    QwenTrainState* train = nullptr;   // training-mode state (qwen_train.inc), created on first use
     void layout();
 };
 
@@ -165,16 +127,7 @@ extern "C" int mi355_qwen_create(const mi355_qwen_cfg* cfg, mi355_qwen** out) {
     e->cfg = *cfg;
     e->H = cfg->num_heads; e->D = cfg->num_heads * cfg->head_dim; e->F = 4 * e->D; e->L = cfg->num_layers;
     e->layout();
-    const size_t cap16 = e->used16, cap32 = e->used32;
-    hipError_t e1 = hipMalloc((void**)&e->arena16, cap16);
-    hipError_t e2 = hipMalloc((void**)&e->arena32, cap32);
-    if (e1 != hipSuccess || e2 != hipSuccess) {
-        int r = errorf("mi355_qwen_create: hipMalloc of %zu + %zu bytes failed", cap16, cap32);
-        if (e->arena16) (void)hipFree(e->arena16);
-        if (e->arena32) (void)hipFree(e->arena32);
-        delete e;
-        return r;
-    }
+    if (e->alloc("mi355_qwen_create") != 0) { delete e; return 1; }
     e->layout();
     *out = e;
     return 0;
@@ -183,38 +136,21 @@ extern "C" int mi355_qwen_create(const mi355_qwen_cfg* cfg, mi355_qwen** out) {
 extern "C" int mi355_qwen_destroy(mi355_qwen* e) {
     if (!e) return 0;
     qwen_train_release_engine(e);
-    if (e->arena16) (void)hipFree(e->arena16);
-    if (e->arena32) (void)hipFree(e->arena32);
+    e->release();
     delete e;
     return 0;
 }
 extern "C" int mi355_qwen_num_params(mi355_qwen* e) { return e ? (int)e->names.size() : 0; }
-extern "C" const char* mi355_qwen_param_name(mi355_qwen* e, int i) {
-    if (!e || i < 0 || i >= (int)e->names.size()) return nullptr;
-    return e->names[i].c_str();
-}
+extern "C" const char* mi355_qwen_param_name(mi355_qwen* e, int i) { return e ? e->param_name(i) : nullptr; }
 extern "C" int mi355_qwen_bind_weight(mi355_qwen* e, const char* name, const void* src, int dtype, int ndim, const int64_t* shape,
                                       void* stream) {
     if (!e || !name || !src) return errorf("mi355_qwen_bind_weight: null argument");
-    auto it = e->slots.find(name);
-    if (it == e->slots.end()) return errorf("mi355_qwen_bind_weight: unknown parameter '%s'", name);
-    int64_t n = 1;
-    for (int i = 0; i < ndim; ++i) n *= shape[i];
-    if (n != it->second.numel)
-        return errorf("mi355_qwen_bind_weight: '%s' has %lld elements, expected %lld", name, (long long)n, (long long)it->second.numel);
-    if (dtype < 0 || dtype > 2) return errorf("mi355_qwen_bind_weight: bad dtype %d", dtype);
-    HIPCHK(launch_convert(src, dtype, it->second.dst, it->second.dst_dt, n, (hipStream_t)stream));
-    it->second.bound = true;
+    CHK(e->bind("mi355_qwen_bind_weight", name, src, dtype, ndim, shape, (hipStream_t)stream));
     qwen_train_mark_dirty(e);          // the transposed copies the backward's dgrad GEMMs read are stale
     if (strstr(name, ".norm_")) e->bounds_dirty = true;
     return 0;
 }
-extern "C" int mi355_qwen_weights_ready(mi355_qwen* e) {
-    if (!e) return errorf("null engine");
-    for (auto& kv : e->slots)
-        if (!kv.second.bound) return errorf("parameter '%s' has not been bound", kv.first.c_str());
-    return 0;
-}
+extern "C" int mi355_qwen_weights_ready(mi355_qwen* e) { return e ? e->ready() : errorf("null engine"); }
 
 // -------------------------------------------------------------------------------------- plan
 struct mi355_qwen_plan {
@@ -240,12 +176,8 @@ struct mi355_qwen_plan {
     char* ws_side = nullptr;
     bf16_t *qkbuf_c = nullptr, *big_c = nullptr;
     std::vector<hipEvent_t> ev_join, ev_fork;   // per block: text q|k|v ready (side -> main), attention done (main -> side); [L] = forward start / end
-    // hipGraph of the N-step loop (opt-in, mi355_tune_set key 17): captured on a plan-owned stream on the second call of a configuration
-    hipGraphExec_t gexec = nullptr;
-    hipStream_t cap_stream = nullptr;
-    bool warmed = false;
-    int g_steps = -1, g_dyn = -1, g_storage = -1, g_init = -1, g_clp = -1, g_noise = -1, g_bounds = -1, g_two = -1, g_gemm = -1, g_attn = -1, g_tune = -1;
-    float g_sigma_max = 0.f, g_guidance = 0.f;
+    RolloutGraph graph;                 // hipGraph of the N-step loop (mi355_tune_set key 17), captured on the second call of a configuration
+    mi355_qwen_train* train = nullptr;  // training workspace (qwen_train.inc), created by the first training-mode forward
 };
 
 extern "C" int mi355_qwen_plan_create(mi355_qwen* e, int batch, int n_cfg, int latent_h, int latent_w, int n_text, int max_steps,
@@ -261,49 +193,24 @@ extern "C" int mi355_qwen_plan_create(mi355_qwen* e, int batch, int n_cfg, int l
     p->n_lat = (int64_t)p->Ni * e->cfg.in_channels;
     const int D = e->D, F = e->F, J = e->cfg.joint_attention_dim, FB = p->FB;
     const int64_t rows_cond = (int64_t)(max_steps > FB ? max_steps : FB);
-    size_t off = 0;
-    auto take = [&](int64_t elems, int esz) {
-        size_t o = off;
-        off += (((size_t)elems * esz) + 255) & ~(size_t)255;
-        return o;
-    };
     const int64_t qk_el = (int64_t)FB * e->H * p->S_pad * 128;
     const int64_t nl = (int64_t)batch * p->n_lat;
     const int64_t big_rows = p->Mi > p->Mc ? p->Mi : p->Mc;
-    size_t o_l16 = take(nl, 2), o_x = take((int64_t)p->Mi * D, 2), o_c = take((int64_t)p->Mc * D, 2), o_c0 = take((int64_t)p->Mc * D, 2);
-    size_t o_xn = take((int64_t)p->Mi * D, 2), o_cn = take((int64_t)p->Mc * D, 2), o_qkb = take(big_rows * 2 * D, 2);
-    size_t o_q = take(qk_el, 2), o_k = take(qk_el, 2), o_vT = take(qk_el, 2);
-    size_t o_oi = take((int64_t)p->Mi * D, 2), o_oc = take((int64_t)p->Mc * D, 2), o_big = take(big_rows * F, 2);
-    size_t o_v2 = take((int64_t)FB * p->n_lat, 2), o_v = take(nl, 2);
-    size_t o_tp = take(rows_cond * e->cfg.time_proj_dim, 2), o_h1 = take(rows_cond * D, 2), o_semb = take(rows_cond * D, 2);
-    size_t o_mod = take(rows_cond * e->mod_cols, 2), o_txtn = take((int64_t)p->Mc * J, 2);
-    size_t o_cs = take((int64_t)p->S * 64, 8);
-    size_t o_t = take(rows_cond, 4), o_sc = take(3 * (int64_t)max_steps, 4), o_kl = take(FB, 4);
-    size_t o_ii = take(nl, 4), o_it = take((int64_t)(max_steps + 1) * nl, 4), o_in = take((int64_t)max_steps * nl, 4);
-    size_t o_il = take((int64_t)max_steps * batch, 4);
-    size_t o_ipe = take((int64_t)p->Mc * J, 2);
-    p->ws_bytes = off;
-    if (hipMalloc((void**)&p->ws, off) != hipSuccess) {
-        int r = errorf("mi355_qwen_plan_create: hipMalloc of %zu bytes failed", off);
-        delete p;
-        return r;
-    }
-    if (hipMemset(p->ws, 0, off) != hipSuccess) {   // padded key rows / columns of q, k, vT must stay finite
-        (void)hipFree(p->ws);
-        delete p;
-        return errorf("mi355_qwen_plan_create: hipMemset failed");
-    }
-    char* w = p->ws;
-    p->lat16 = (bf16_t*)(w + o_l16); p->x = (bf16_t*)(w + o_x); p->c = (bf16_t*)(w + o_c); p->c0 = (bf16_t*)(w + o_c0);
-    p->xn = (bf16_t*)(w + o_xn); p->cn = (bf16_t*)(w + o_cn); p->qkbuf = (bf16_t*)(w + o_qkb);
-    p->q = (bf16_t*)(w + o_q); p->k = (bf16_t*)(w + o_k); p->vT = (bf16_t*)(w + o_vT);
-    p->o_img = (bf16_t*)(w + o_oi); p->o_ctx = (bf16_t*)(w + o_oc); p->big = (bf16_t*)(w + o_big);
-    p->v2 = (bf16_t*)(w + o_v2); p->v = (bf16_t*)(w + o_v);
-    p->tproj = (bf16_t*)(w + o_tp); p->h1 = (bf16_t*)(w + o_h1); p->semb = (bf16_t*)(w + o_semb); p->mod_all = (bf16_t*)(w + o_mod);
-    p->txtn = (bf16_t*)(w + o_txtn);
-    p->cs = (float2*)(w + o_cs); p->t_dev = (float*)(w + o_t); p->scal = (float*)(w + o_sc); p->kvlen = (int*)(w + o_kl);
-    p->io_init = w + o_ii; p->io_traj = w + o_it; p->io_noise = (float*)(w + o_in); p->io_lp = (float*)(w + o_il);
-    p->io_pe = (bf16_t*)(w + o_ipe);
+    Carver c;
+    c.take(p->lat16, nl); c.take(p->x, (int64_t)p->Mi * D); c.take(p->c, (int64_t)p->Mc * D); c.take(p->c0, (int64_t)p->Mc * D);
+    c.take(p->xn, (int64_t)p->Mi * D); c.take(p->cn, (int64_t)p->Mc * D); c.take(p->qkbuf, big_rows * 2 * D);
+    c.take(p->q, qk_el); c.take(p->k, qk_el); c.take(p->vT, qk_el);
+    c.take(p->o_img, (int64_t)p->Mi * D); c.take(p->o_ctx, (int64_t)p->Mc * D); c.take(p->big, big_rows * F);
+    c.take(p->v2, (int64_t)FB * p->n_lat); c.take(p->v, nl);
+    c.take(p->tproj, rows_cond * e->cfg.time_proj_dim); c.take(p->h1, rows_cond * D); c.take(p->semb, rows_cond * D);
+    c.take(p->mod_all, rows_cond * e->mod_cols); c.take(p->txtn, (int64_t)p->Mc * J);
+    c.take(p->cs, (int64_t)p->S * 64);
+    c.take(p->t_dev, rows_cond); c.take(p->scal, 3 * (int64_t)max_steps); c.take(p->kvlen, FB);
+    c.take(p->io_init, nl * 4); c.take(p->io_traj, (int64_t)(max_steps + 1) * nl * 4); c.take(p->io_noise, (int64_t)max_steps * nl);
+    c.take(p->io_lp, (int64_t)max_steps * batch);
+    c.take(p->io_pe, (int64_t)p->Mc * J);
+    // zeroed: the padded key rows / columns of q, k, vT must stay finite
+    if (c.alloc(&p->ws, &p->ws_bytes, true, "mi355_qwen_plan_create") != 0) { delete p; return 1; }
     // rotary table of the joint sequence in THIS engine's order [img | txt] (attention is order-invariant once the angles are applied).
     // QwenEmbedRope (diffusers transformer_qwenimage.py): fp32 angles pos * theta^(-2j/dim); image token (frame 0, row r, col c) sits at
     // (0, r - (hp - hp/2), c - (wp - wp/2)) when scale_rope (rows/cols centred: negative indices first), else (0, r, c); text token j at
@@ -345,8 +252,7 @@ extern "C" int mi355_qwen_plan_create(mi355_qwen* e, int batch, int n_cfg, int l
 extern "C" int mi355_qwen_plan_destroy(mi355_qwen_plan* p) {
     if (!p) return 0;
     qwen_train_release(p);
-    if (p->gexec) (void)hipGraphExecDestroy(p->gexec);
-    if (p->cap_stream) (void)hipStreamDestroy(p->cap_stream);
+    p->graph.release();
     for (hipEvent_t ev : p->ev_join) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : p->ev_fork) (void)hipEventDestroy(ev);
     if (p->side) (void)hipStreamDestroy(p->side);
@@ -473,10 +379,10 @@ bool qwen_two_stream_wanted(const mi355_qwen_plan* p) {
 
 int qwen_two_stream_init(mi355_qwen_plan* p) {
     if (p->side) return 0;
-    const size_t qkb = (((size_t)p->Mc * 2 * p->e->D * 2) + 255) & ~(size_t)255, big = (((size_t)p->Mc * p->e->F * 2) + 255) & ~(size_t)255;
-    HIPCHK(hipMalloc((void**)&p->ws_side, qkb + big));
-    p->qkbuf_c = (bf16_t*)p->ws_side;
-    p->big_c = (bf16_t*)(p->ws_side + qkb);
+    Carver c;
+    size_t bytes;
+    c.take(p->qkbuf_c, (int64_t)p->Mc * 2 * p->e->D); c.take(p->big_c, (int64_t)p->Mc * p->e->F);
+    CHK(c.alloc(&p->ws_side, &bytes, false, "qwen two-stream forward"));
     for (int i = 0; i <= p->e->L; ++i) {
         hipEvent_t a, b;
         HIPCHK(hipEventCreateWithFlags(&a, hipEventDisableTiming));
@@ -663,7 +569,7 @@ extern "C" int mi355_qwen_rollout(mi355_qwen_plan* p, void* stream, int n_steps,
     for (int i = 0; i < n_steps; ++i) {
         // qwen_image.py:497, 534: timestep = t.to(latents.dtype); the model receives timestep / 1000 (same dtype) and its sinusoidal
         // projection multiplies by 1000 in fp32 (Timesteps(scale=1000)): the angle base is (t_model * 1000)
-        const float tm = q_host_round(q_host_round(timesteps_host[i], storage_dtype) / 1000.0f, storage_dtype);
+        const float tm = host_round(host_round(timesteps_host[i], storage_dtype) / 1000.0f, storage_dtype);
         tt[i] = tm * 1000.0f;
         const float t_next = (i + 1 < n_steps) ? timesteps_host[i + 1] : 0.0f;
         sc[i] = timesteps_host[i] / 1000.0f;
@@ -701,47 +607,15 @@ extern "C" int mi355_qwen_rollout(mi355_qwen_plan* p, void* stream, int n_steps,
         }
         return 0;
     };
-    bool launched = false;
-    if (g_qwen_graph && p->warmed) {
+    if (g_qwen_graph && p->graph.warmed) {
         const int two = (int)qwen_two_stream_wanted(p);
-        const bool same = p->gexec && p->g_steps == n_steps && p->g_dyn == dynamics && p->g_storage == storage_dtype && p->g_init == init_dtype &&
-                          p->g_clp == clp && p->g_noise == (int)(step_noise != nullptr) && p->g_sigma_max == sigma_max && p->g_guidance == guidance_scale &&
-                          p->g_bounds == p->e->bounds_ver && p->g_two == two && p->g_gemm == get_gemm_variant() && p->g_attn == get_attn128_variant() && p->g_tune == tune_epoch();
-        if (!same) {
-            if (two) CHK(qwen_two_stream_init(p));              // streams / events / buffers are created outside the capture
-            if (p->gexec) { (void)hipGraphExecDestroy(p->gexec); p->gexec = nullptr; }
-            hipGraph_t graph = nullptr;
-            hipError_t ce = hipSuccess;
-            if (!p->cap_stream) ce = hipStreamCreateWithFlags(&p->cap_stream, hipStreamNonBlocking);
-            if (ce == hipSuccess) ce = hipStreamBeginCapture(p->cap_stream, hipStreamCaptureModeRelaxed);
-            if (ce == hipSuccess) {
-                const int rc = body(p->cap_stream);             // nothing executes: launches / D2D copies become graph nodes
-                ce = hipStreamEndCapture(p->cap_stream, &graph);
-                if (rc != 0 || ce != hipSuccess || !graph) {
-                    if (graph) (void)hipGraphDestroy(graph);
-                    graph = nullptr;
-                }
-            }
-            if (graph) {
-                ce = hipGraphInstantiate(&p->gexec, graph, nullptr, nullptr, 0);
-                (void)hipGraphDestroy(graph);
-                if (ce != hipSuccess) p->gexec = nullptr;
-            }
-            if (!p->gexec) {                                    // no silent fallback: the caller chooses eager launches with key 17 = 0
-                const hipError_t last = hipGetLastError();
-                return errorf("mi355_qwen_rollout: hipGraph capture / instantiation of the %d-step loop failed (%s); mi355_tune_set(17, 0) "
-                              "selects eager launches", n_steps, hipGetErrorString(ce != hipSuccess ? ce : last));
-            }
-            p->g_steps = n_steps; p->g_dyn = dynamics; p->g_storage = storage_dtype; p->g_init = init_dtype; p->g_clp = clp;
-            p->g_noise = (int)(step_noise != nullptr); p->g_sigma_max = sigma_max; p->g_guidance = guidance_scale; p->g_bounds = p->e->bounds_ver;
-            p->g_two = two; p->g_gemm = get_gemm_variant(); p->g_attn = get_attn128_variant(); p->g_tune = tune_epoch();
-        }
-        HIPCHK(hipGraphLaunch(p->gexec, st));
-        launched = true;
-    }
-    if (!launched) {
+        const int key[RolloutGraph::NKEY] = {n_steps, dynamics, storage_dtype, init_dtype, clp, (int)(step_noise != nullptr), float_bits(sigma_max),
+                                             float_bits(guidance_scale), p->e->bounds_ver, two, get_gemm_variant(), get_attn128_variant(), tune_epoch()};
+        // (streams / events / buffers are created outside the capture)
+        CHK(p->graph.launch(key, st, "mi355_qwen_rollout", n_steps, 17, [&] { return two ? qwen_two_stream_init(p) : 0; }, body));
+    } else {
         CHK(body(st));
-        p->warmed = true;
+        p->graph.warmed = true;
     }
     if (keep_slot_host && out_latents)
         for (int i = 0; i <= n_steps; ++i)

@@ -22,7 +22,7 @@ struct QwenTrainState {      // per engine
     std::vector<QBlkWT> wt;
     bf16_t* projT = nullptr;
     bool dirty = true;
-    std::map<std::string, float*> grads;
+    GradRegistry grads;
 };
 struct mi355_qwen_train {    // per plan
     mi355_qwen_plan* p;
@@ -37,34 +37,25 @@ struct mi355_qwen_train {    // per plan
     int Mi_pad, Mc_pad;
 };
 
-static std::map<mi355_qwen*, QwenTrainState*> g_qwen_train_engines;
-static std::map<mi355_qwen_plan*, mi355_qwen_train*> g_qwen_trains;
-
-static QwenTrainState* qwen_train_state(mi355_qwen* e) {
-    auto it = g_qwen_train_engines.find(e);
-    if (it != g_qwen_train_engines.end()) return it->second;
-    QwenTrainState* s = new QwenTrainState();
-    g_qwen_train_engines[e] = s;
-    return s;
+static QwenTrainState* qwen_train_state(mi355_qwen* e) {      // created on first use
+    if (!e->train) e->train = new QwenTrainState();
+    return e->train;
 }
 static void qwen_train_mark_dirty(mi355_qwen* e) {
-    auto it = g_qwen_train_engines.find(e);
-    if (it != g_qwen_train_engines.end()) it->second->dirty = true;
+    if (e->train) e->train->dirty = true;
 }
 static void qwen_train_release(mi355_qwen_plan* p) {
-    auto it = g_qwen_trains.find(p);
-    if (it == g_qwen_trains.end()) return;
-    t_wgrad_streams_destroy(it->second->sc);
-    if (it->second->ws) (void)hipFree(it->second->ws);
-    delete it->second;
-    g_qwen_trains.erase(it);
+    if (!p->train) return;
+    t_wgrad_streams_destroy(p->train->sc);
+    if (p->train->ws) (void)hipFree(p->train->ws);
+    delete p->train;
+    p->train = nullptr;
 }
 static void qwen_train_release_engine(mi355_qwen* e) {
-    auto it = g_qwen_train_engines.find(e);
-    if (it == g_qwen_train_engines.end()) return;
-    if (it->second->arenaT) (void)hipFree(it->second->arenaT);
-    delete it->second;
-    g_qwen_train_engines.erase(it);
+    if (!e->train) return;
+    if (e->train->arenaT) (void)hipFree(e->train->arenaT);
+    delete e->train;
+    e->train = nullptr;
 }
 
 static bool qwen_trainable_name(const std::string& n) {
@@ -80,17 +71,9 @@ static bool qwen_trainable_name(const std::string& n) {
 extern "C" int mi355_qwen_set_grad(mi355_qwen* e, const char* name, float* grad) {
     if (!e || !name) return errorf("mi355_qwen_set_grad: null argument");
     if (e->slots.find(name) == e->slots.end()) return errorf("mi355_qwen_set_grad: unknown parameter '%s'", name);
-    QwenTrainState* s = qwen_train_state(e);
-    if (!grad) {
-        auto it = s->grads.find(name);
-        if (it != s->grads.end()) { grad_buf_mark(it->second, DT_F32); s->grads.erase(it); }
-        return 0;
-    }
-    if (!qwen_trainable_name(name))
+    if (grad && !qwen_trainable_name(name))
         return errorf("mi355_qwen_set_grad: '%s' lies outside the native backward's scope (the linear layers inside the transformer blocks)", name);
-    { auto prev = s->grads.find(name); if (prev != s->grads.end() && prev->second != grad) grad_buf_mark(prev->second, DT_F32); }   // (a re-registration un-marks the buffer it replaces)
-    s->grads[name] = grad;
-    grad_buf_mark(grad, DT_F32);
+    qwen_train_state(e)->grads.set(name, grad);
     return 0;
 }
 // the same with the buffer's dtype: MI355_F32, or MI355_BF16 for the weights / biases of the linear layers inside the transformer blocks (the
@@ -106,7 +89,6 @@ extern "C" int mi355_qwen_set_grad_typed(mi355_qwen* e, const char* name, void* 
 }
 extern "C" int mi355_qwen_clear_grads(mi355_qwen* e) {
     if (!e) return errorf("null engine");
-    for (auto& kv : qwen_train_state(e)->grads) grad_buf_mark(kv.second, DT_F32);
     qwen_train_state(e)->grads.clear();
     return 0;
 }
@@ -116,40 +98,24 @@ extern "C" int mi355_qwen_grad_supported(mi355_qwen* e, const char* name) {
     return qwen_trainable_name(name) ? 0 : 1;
 }
 extern "C" int64_t mi355_qwen_plan_training_bytes(mi355_qwen_plan* p) {
-    auto it = g_qwen_trains.find(p);
-    return it == g_qwen_trains.end() ? 0 : (int64_t)it->second->ws_bytes;
+    return p && p->train ? (int64_t)p->train->ws_bytes : 0;
 }
 
-static float* qgrad_of(mi355_qwen* e, const std::string& name) {
-    QwenTrainState* s = qwen_train_state(e);
-    auto it = s->grads.find(name);
-    return it == s->grads.end() ? nullptr : it->second;
-}
+static float* qgrad_of(mi355_qwen* e, const std::string& name) { return qwen_train_state(e)->grads.find(name); }
 
 // ---- transposed weights -------------------------------------------------------------------------------------------
 static int qwen_ensure_transposed(mi355_qwen* e, hipStream_t st) {
     QwenTrainState* s = qwen_train_state(e);
     const int D = e->D, F = e->F, L = e->L, C = e->cfg.in_channels;
     if (!s->arenaT) {
-        size_t off = 0;
-        auto take = [&](int64_t n) { size_t o = off; off += ((size_t)n * 2 + 255) & ~(size_t)255; return o; };
-        std::vector<size_t> ob;
-        for (int i = 0; i < L; ++i) {
-            ob.push_back(take((int64_t)D * 3 * D)); ob.push_back(take((int64_t)D * D)); ob.push_back(take((int64_t)D * 3 * D)); ob.push_back(take((int64_t)D * D));
-            ob.push_back(take((int64_t)D * F)); ob.push_back(take((int64_t)F * D)); ob.push_back(take((int64_t)D * F)); ob.push_back(take((int64_t)F * D));
-        }
-        const size_t o_proj = take((int64_t)D * C);
-        s->bytes = off;
-        if (hipMalloc((void**)&s->arenaT, off) != hipSuccess) return errorf("qwen training: hipMalloc of %zu bytes for the transposed weights failed", off);
-        char* a = s->arenaT;
+        Carver c;
         s->wt.resize(L);
-        for (int i = 0; i < L; ++i) {
-            QBlkWT& w = s->wt[i];
-            const size_t* o = &ob[(size_t)i * 8];
-            w.qkv = (bf16_t*)(a + o[0]); w.o = (bf16_t*)(a + o[1]); w.cqkv = (bf16_t*)(a + o[2]); w.co = (bf16_t*)(a + o[3]);
-            w.ff1 = (bf16_t*)(a + o[4]); w.ff2 = (bf16_t*)(a + o[5]); w.cff1 = (bf16_t*)(a + o[6]); w.cff2 = (bf16_t*)(a + o[7]);
+        for (QBlkWT& w : s->wt) {
+            c.take(w.qkv, (int64_t)D * 3 * D); c.take(w.o, (int64_t)D * D); c.take(w.cqkv, (int64_t)D * 3 * D); c.take(w.co, (int64_t)D * D);
+            c.take(w.ff1, (int64_t)D * F); c.take(w.ff2, (int64_t)F * D); c.take(w.cff1, (int64_t)D * F); c.take(w.cff2, (int64_t)F * D);
         }
-        s->projT = (bf16_t*)(a + o_proj);
+        c.take(s->projT, (int64_t)D * C);
+        CHK(c.alloc(&s->arenaT, &s->bytes, false, "qwen training", " for the transposed weights"));
         s->dirty = true;
     }
     if (!s->dirty) return 0;
@@ -173,8 +139,7 @@ static int qwen_ensure_transposed(mi355_qwen* e, hipStream_t st) {
 
 // ---- training workspace ----------------------------------------------------------------------------------------------
 static int qwen_train_of(mi355_qwen_plan* p, mi355_qwen_train** out) {
-    auto it = g_qwen_trains.find(p);
-    if (it != g_qwen_trains.end()) { *out = it->second; return 0; }
+    if (p->train) { *out = p->train; return 0; }
     mi355_qwen* e = p->e;
     const int D = e->D, F = e->F, L = e->L, H = e->H, C = e->cfg.in_channels;
     const int Mi = p->Mi, Mc = p->Mc;
@@ -183,67 +148,34 @@ static int qwen_train_of(mi355_qwen_plan* p, mi355_qwen_train** out) {
     t->p = p;
     t->Mi_pad = (Mi + 63) / 64 * 64; t->Mc_pad = (Mc + 63) / 64 * 64;
     const int Mmax = Mi > Mc ? Mi : Mc, Mmax_pad = t->Mi_pad > t->Mc_pad ? t->Mi_pad : t->Mc_pad;
-    size_t off = 0;
-    auto take = [&](int64_t elems, int esz) { size_t o = off; off += (((size_t)elems * esz) + 255) & ~(size_t)255; return o; };
-    struct BO { size_t v[18]; };
-    std::vector<BO> bo(L);
-    for (int i = 0; i < L; ++i) {
-        size_t* o = bo[i].v;
-        int n = 0;
-        o[n++] = take((int64_t)Mi * D, 2); o[n++] = take((int64_t)Mi * D, 2); o[n++] = take((int64_t)Mi * D, 2); o[n++] = take((int64_t)Mi * D, 2);   // x_in xn x_mid xn_mlp
-        o[n++] = take((int64_t)Mi * F, 2); o[n++] = take((int64_t)Mi * D, 2);                                                                   // pre o_img
-        o[n++] = take((int64_t)Mc * D, 2); o[n++] = take((int64_t)Mc * D, 2); o[n++] = take((int64_t)Mc * D, 2); o[n++] = take((int64_t)Mc * D, 2);   // c_in cn c_mid cn_mlp
-        o[n++] = take((int64_t)Mc * F, 2); o[n++] = take((int64_t)Mc * D, 2);                                                                   // cpre o_ctx
-        o[n++] = take(qk_el, 2); o[n++] = take(qk_el, 2); o[n++] = take(qk_el, 2);                                                              // q k vT
-        o[n++] = take((int64_t)p->FB * H * p->S_pad, 4); o[n++] = take((int64_t)Mi * 2 * H, 4); o[n++] = take((int64_t)Mc * 2 * H, 4);          // lse rstd
-    }
-    const size_t o_xf = take((int64_t)Mi * D, 2), o_mod = take((int64_t)p->FB * e->mod_cols, 2), o_vraw = take((int64_t)p->FB * p->n_lat, 2), o_kv = take(p->FB, 4);
-    const size_t o_dx = take((int64_t)Mi * D, 2), o_dc = take((int64_t)Mc * D, 2), o_dvb = take((int64_t)Mi * C, 2);
-    const size_t o_g1 = take((int64_t)Mi * D, 2), o_g1c = take((int64_t)Mc * D, 2), o_g2 = take((int64_t)Mi * D, 2), o_g2c = take((int64_t)Mc * D, 2);
-    const size_t o_g3 = take((int64_t)Mi * D, 2), o_g3c = take((int64_t)Mc * D, 2);
-    const size_t o_wide = take((int64_t)Mi * (3 * D + F), 2), o_widec = take((int64_t)Mc * (3 * D + F), 2), o_hid = take((int64_t)Mmax * F, 2);
-    const size_t o_doh = take(qk_el, 2), o_v = take(qk_el, 2), o_dq = take(qk_el, 2), o_dk = take(qk_el, 2), o_dvh = take(qk_el, 2);
-    const size_t o_delta = take((int64_t)p->FB * H * p->S_pad, 4), o_nld = take((int64_t)p->FB * H * p->S_pad * 2, 4);
-    const int n_slots = get_wgrad_side() ? WG_SLOTS : 1;
-    size_t o_aT[WG_SLOTS], o_xT[WG_SLOTS];
-    for (int i = 0; i < n_slots; ++i) { o_aT[i] = take((int64_t)F * Mmax_pad, 2); o_xT[i] = take((int64_t)F * Mmax_pad, 2); }
-    t->sc.part_floats = (size_t)16 * D * D > (size_t)2 * F * D ? (size_t)16 * D * D : (size_t)2 * F * D;
-    const int nrt = Mmax_pad / 64 > 64 ? Mmax_pad / 64 : 64;
-    const size_t o_part = take((int64_t)t->sc.part_floats, 4), o_cs = take((int64_t)nrt * F, 4), o_zb = take(F > 3 * D ? F : 3 * D, 4);
-    const size_t o_hidc = take((int64_t)Mc * F, 2), o_csc = take((int64_t)(t->Mc_pad / 64 > 64 ? t->Mc_pad / 64 : 64) * F, 4);
-    t->ws_bytes = off;
-    if (hipMalloc((void**)&t->ws, off) != hipSuccess) {
-        delete t;
-        return errorf("qwen training: hipMalloc of %zu bytes of activation stash + backward scratch failed", off);
-    }
-    if (hipMemset(t->ws, 0, off) != hipSuccess) { (void)hipFree(t->ws); delete t; return errorf("qwen training: hipMemset failed"); }
-    char* w = t->ws;
-    t->blk.resize(L);
-    for (int i = 0; i < L; ++i) {
-        QTrainBlk& k = t->blk[i];
-        const size_t* o = bo[i].v;
-        int n = 0;
-        k.x_in = (bf16_t*)(w + o[n++]); k.xn = (bf16_t*)(w + o[n++]); k.x_mid = (bf16_t*)(w + o[n++]); k.xn_mlp = (bf16_t*)(w + o[n++]);
-        k.pre = (bf16_t*)(w + o[n++]); k.o_img = (bf16_t*)(w + o[n++]);
-        k.c_in = (bf16_t*)(w + o[n++]); k.cn = (bf16_t*)(w + o[n++]); k.c_mid = (bf16_t*)(w + o[n++]); k.cn_mlp = (bf16_t*)(w + o[n++]);
-        k.cpre = (bf16_t*)(w + o[n++]); k.o_ctx = (bf16_t*)(w + o[n++]);
-        k.q = (bf16_t*)(w + o[n++]); k.k = (bf16_t*)(w + o[n++]); k.vT = (bf16_t*)(w + o[n++]);
-        k.lse = (float*)(w + o[n++]); k.rstd_img = (float*)(w + o[n++]); k.rstd_ctx = (float*)(w + o[n++]);
-    }
-    t->x_final = (bf16_t*)(w + o_xf); t->mod = (bf16_t*)(w + o_mod); t->vraw = (bf16_t*)(w + o_vraw); t->kvlen = (int*)(w + o_kv);
-    t->dx = (bf16_t*)(w + o_dx); t->dc = (bf16_t*)(w + o_dc); t->dvb = (bf16_t*)(w + o_dvb);
     TrainScratch& sc = t->sc;
-    sc.g1 = (bf16_t*)(w + o_g1); sc.g1c = (bf16_t*)(w + o_g1c); sc.g2 = (bf16_t*)(w + o_g2); sc.g2c = (bf16_t*)(w + o_g2c);
-    sc.g3 = (bf16_t*)(w + o_g3); sc.g3c = (bf16_t*)(w + o_g3c);
-    sc.wide = (bf16_t*)(w + o_wide); sc.widec = (bf16_t*)(w + o_widec); sc.hid = (bf16_t*)(w + o_hid);
-    sc.doh = (bf16_t*)(w + o_doh); sc.v = (bf16_t*)(w + o_v); sc.dq = (bf16_t*)(w + o_dq); sc.dk = (bf16_t*)(w + o_dk); sc.dvh = (bf16_t*)(w + o_dvh);
-    sc.delta = (float*)(w + o_delta); sc.nld = (float*)(w + o_nld);
-    for (int i = 0; i < n_slots; ++i) { sc.slot[i].aT = (bf16_t*)(w + o_aT[i]); sc.slot[i].xT = (bf16_t*)(w + o_xT[i]); }
+    Carver c;
+    t->blk.resize(L);
+    for (QTrainBlk& k : t->blk) {
+        c.take(k.x_in, (int64_t)Mi * D); c.take(k.xn, (int64_t)Mi * D); c.take(k.x_mid, (int64_t)Mi * D); c.take(k.xn_mlp, (int64_t)Mi * D);
+        c.take(k.pre, (int64_t)Mi * F); c.take(k.o_img, (int64_t)Mi * D);
+        c.take(k.c_in, (int64_t)Mc * D); c.take(k.cn, (int64_t)Mc * D); c.take(k.c_mid, (int64_t)Mc * D); c.take(k.cn_mlp, (int64_t)Mc * D);
+        c.take(k.cpre, (int64_t)Mc * F); c.take(k.o_ctx, (int64_t)Mc * D);
+        c.take(k.q, qk_el); c.take(k.k, qk_el); c.take(k.vT, qk_el);
+        c.take(k.lse, (int64_t)p->FB * H * p->S_pad); c.take(k.rstd_img, (int64_t)Mi * 2 * H); c.take(k.rstd_ctx, (int64_t)Mc * 2 * H);
+    }
+    c.take(t->x_final, (int64_t)Mi * D); c.take(t->mod, (int64_t)p->FB * e->mod_cols); c.take(t->vraw, (int64_t)p->FB * p->n_lat); c.take(t->kvlen, p->FB);
+    c.take(t->dx, (int64_t)Mi * D); c.take(t->dc, (int64_t)Mc * D); c.take(t->dvb, (int64_t)Mi * C);
+    c.take(sc.g1, (int64_t)Mi * D); c.take(sc.g1c, (int64_t)Mc * D); c.take(sc.g2, (int64_t)Mi * D); c.take(sc.g2c, (int64_t)Mc * D);
+    c.take(sc.g3, (int64_t)Mi * D); c.take(sc.g3c, (int64_t)Mc * D);
+    c.take(sc.wide, (int64_t)Mi * (3 * D + F)); c.take(sc.widec, (int64_t)Mc * (3 * D + F)); c.take(sc.hid, (int64_t)Mmax * F);
+    c.take(sc.doh, qk_el); c.take(sc.v, qk_el); c.take(sc.dq, qk_el); c.take(sc.dk, qk_el); c.take(sc.dvh, qk_el);
+    c.take(sc.delta, (int64_t)p->FB * H * p->S_pad); c.take(sc.nld, (int64_t)p->FB * H * p->S_pad * 2);
+    const int n_slots = get_wgrad_side() ? WG_SLOTS : 1;
+    for (int i = 0; i < n_slots; ++i) { c.take(sc.slot[i].aT, (int64_t)F * Mmax_pad); c.take(sc.slot[i].xT, (int64_t)F * Mmax_pad); }
+    sc.part_floats = (size_t)16 * D * D > (size_t)2 * F * D ? (size_t)16 * D * D : (size_t)2 * F * D;
+    const int nrt = Mmax_pad / 64 > 64 ? Mmax_pad / 64 : 64;
+    c.take(sc.part, (int64_t)sc.part_floats); c.take(sc.csum, (int64_t)nrt * F); c.take(sc.zero_bias, F > 3 * D ? F : 3 * D);
+    c.take(sc.hid_c, (int64_t)Mc * F); c.take(sc.csum_c, (int64_t)(t->Mc_pad / 64 > 64 ? t->Mc_pad / 64 : 64) * F);
+    if (c.alloc(&t->ws, &t->ws_bytes, true, "qwen training", " of activation stash + backward scratch") != 0) { delete t; return 1; }
     sc.aT_rows = F; sc.xT_rows = F;
     if (t_wgrad_streams_init(sc, n_slots > 1) != 0) { t_wgrad_streams_destroy(sc); (void)hipFree(t->ws); delete t; return 1; }
-    sc.part = (float*)(w + o_part); sc.csum = (float*)(w + o_cs); sc.zero_bias = (float*)(w + o_zb);
-    sc.hid_c = (bf16_t*)(w + o_hidc); sc.csum_c = (float*)(w + o_csc);
-    g_qwen_trains[p] = t;
+    p->train = t;
     *out = t;
     return 0;
 }
@@ -283,9 +215,8 @@ extern "C" int mi355_qwen_forward_train(mi355_qwen_plan* p, void* stream, const 
 // d loss / d weights from dv = d loss / d v_out [B][Ni][C] fp32 (v_out = the prediction of the LAST mi355_qwen_forward_train on this plan)
 extern "C" int mi355_qwen_backward(mi355_qwen_plan* p, void* stream, const float* dv) {
     if (!p || !dv) return errorf("mi355_qwen_backward: null argument");
-    auto it = g_qwen_trains.find(p);
-    if (it == g_qwen_trains.end() || !it->second->have_forward) return errorf("mi355_qwen_backward: no training-mode forward has run on this plan");
-    mi355_qwen_train* t = it->second;
+    if (!p->train || !p->train->have_forward) return errorf("mi355_qwen_backward: no training-mode forward has run on this plan");
+    mi355_qwen_train* t = p->train;
     mi355_qwen* e = p->e;
     hipStream_t st = (hipStream_t)stream;
     CHK(qwen_ensure_transposed(e, st));

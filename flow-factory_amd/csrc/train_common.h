@@ -1,10 +1,33 @@
-// mi355_flow -- helpers shared by the native backward passes of the head_dim-128 engines (flux_train.inc, qwen_train.inc): the dgrad / wgrad
-// GEMM wrappers, the attention-backward and q | k producer backward sequences, and the scratch they work in.  (The SD3.5 engine's training
-// file, engine_train.inc, predates this header and keeps its own copies: head_dim 64, per-block dual attention, side-stream scratch pairs.)
+// mi355_flow -- training-side helpers shared by the engines' *_train.inc files: the gradient-buffer registry of an engine (all four engines), and,
+// for the native backward passes of the head_dim-128 engines (flux_train.inc, qwen_train.inc, wan_train.inc), the dgrad / wgrad GEMM wrappers, the
+// attention-backward and q | k producer backward sequences, and the scratch they work in.  (The SD3.5 engine's training file, engine_train.inc,
+// predates this header and keeps its own dgrad / wgrad helpers: head_dim 64, per-block dual attention, side-stream scratch pairs.)
 #pragma once
 #include "engine_common.h"
 
 namespace mi355 {
+
+// Parameter name -> caller-owned gradient buffer (absent = frozen; every backward OVERWRITES the buffers), with the buffers' dtype bookkeeping
+// (grad_buf_mark): fp32 when registered -- the *_set_grad_typed functions re-mark a bf16 buffer afterwards -- and un-marked when it leaves.
+// Which names an engine accepts is the engine's own rule (its trainable-name predicate and refusal messages).
+struct GradRegistry {
+    std::map<std::string, float*> grads;
+    void set(const std::string& name, float* grad) {       // null un-registers
+        auto prev = grads.find(name);
+        if (prev != grads.end() && prev->second != grad) grad_buf_mark(prev->second, DT_F32);    // (a re-registration un-marks the buffer it replaces)
+        if (!grad) { if (prev != grads.end()) grads.erase(prev); return; }
+        grads[name] = grad;
+        grad_buf_mark(grad, DT_F32);
+    }
+    void clear() {
+        for (auto& kv : grads) grad_buf_mark(kv.second, DT_F32);
+        grads.clear();
+    }
+    float* find(const std::string& name) const {
+        auto it = grads.find(name);
+        return it == grads.end() ? nullptr : it->second;
+    }
+};
 
 // One in-flight weight-gradient group: its operands in contraction-contiguous form (aT: the dY columns, [rows <= aT_rows][M_pad]; xT: the
 // layer input, [rows <= xT_rows][M_pad]) + the events that hand it to the side stream and back.

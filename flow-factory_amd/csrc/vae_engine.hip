@@ -223,21 +223,12 @@ extern "C" int mi355_vae_plan_create(mi355_vae* v, int max_batch, int latent_h, 
     for (int i = 0; i < nb; ++i) cmax = c.block_out_channels[i] > cmax ? c.block_out_channels[i] : cmax;
     mi355_vae_plan* p = new mi355_vae_plan();
     p->v = v; p->B = max_batch; p->h = latent_h; p->w = latent_w;
-    const size_t buf = ((size_t)max_batch * act * 2 + 255) & ~(size_t)255;
-    const size_t sc = ((size_t)S * S * 4 + 255) & ~(size_t)255, pb = ((size_t)S * S * 2 + 255) & ~(size_t)255;
-    const size_t vt = ((size_t)top * S * 2 + 255) & ~(size_t)255;
-    const size_t part = ((size_t)max_batch * 1024 * cmax * 2 * 4 + 255) & ~(size_t)255;
-    const size_t ad = ((size_t)max_batch * 2 * cmax * 4 + 255) & ~(size_t)255;
-    p->ws_bytes = 4 * buf + sc + pb + vt + part + ad;
-    if (hipMalloc((void**)&p->ws, p->ws_bytes) != hipSuccess) {
-        int r = errorf("mi355_vae_plan_create: hipMalloc of %zu bytes failed", p->ws_bytes);
-        delete p;
-        return r;
-    }
-    char* q = p->ws;
-    p->X = (bf16_t*)q; q += buf; p->Y = (bf16_t*)q; q += buf; p->T1 = (bf16_t*)q; q += buf; p->T2 = (bf16_t*)q; q += buf;
-    p->SC = (float*)q; q += sc; p->P = (bf16_t*)q; q += pb; p->VT = (bf16_t*)q; q += vt;
-    p->part = (float*)q; q += part; p->ad = (float*)q; q += ad;
+    const int64_t buf = (int64_t)max_batch * act;
+    Carver cv;
+    cv.take(p->X, buf); cv.take(p->Y, buf); cv.take(p->T1, buf); cv.take(p->T2, buf);
+    cv.take(p->SC, (int64_t)S * S); cv.take(p->P, (int64_t)S * S); cv.take(p->VT, (int64_t)top * S);
+    cv.take(p->part, (int64_t)max_batch * 1024 * cmax * 2); cv.take(p->ad, (int64_t)max_batch * 2 * cmax);
+    if (cv.alloc(&p->ws, &p->ws_bytes, false, "mi355_vae_plan_create") != 0) { delete p; return 1; }
     *out = p;
     return 0;
 }

@@ -27,8 +27,6 @@ using namespace mi355;
 
 namespace {
 
-struct WSlot { void* dst; int dst_dt; int64_t numel; bool bound; };
-
 // per-block activation stash of the training-mode forward (wan_train.inc): what the backward of the block needs
 struct WTrainBlk {
     bf16_t *x_in, *xn1, *o1, *x_mid1, *xn2, *o2, *x_mid2, *xn3, *pre;     // [M][D] each; pre [M][F]
@@ -46,42 +44,19 @@ struct WanBlockW {
 
 }  // namespace
 
-struct mi355_wan {
+struct WanTrainState;
+struct mi355_wan_train;
+
+struct mi355_wan : ParamTable {
     mi355_wan_cfg cfg;
     int D, F, L, H, KP, NO;
-    char* arena16 = nullptr;
-    char* arena32 = nullptr;
-    size_t used16 = 0, used32 = 0;
     bf16_t *w_patch, *w_t1, *w_t2, *w_tp, *w_x1, *w_x2, *w_proj;
     float *b_patch, *b_t1, *b_t2, *b_tp, *b_x1, *b_x2, *b_proj, *table_out;
     std::vector<WanBlockW> blk;
-    std::map<std::string, WSlot> slots;
-    std::vector<std::string> names;
     bool derived_dirty = true;   // ln2_mod tables / score bounds need a rebuild after a (re)bind
     int derived_ver = 0;         // bumped by every rebuild (the bounds are baked into a captured graph)
     std::vector<float> bound_self, bound_cross;
-
-    bf16_t* a16(int64_t n) {
-        size_t bytes = ((size_t)n * 2 + 255) & ~(size_t)255;
-        char* p = arena16 ? arena16 + used16 : nullptr;
-        used16 += bytes;
-        return (bf16_t*)p;
-    }
-    float* a32(int64_t n) {
-        size_t bytes = ((size_t)n * 4 + 255) & ~(size_t)255;
-        char* p = arena32 ? arena32 + used32 : nullptr;
-        used32 += bytes;
-        return (float*)p;
-    }
-    void reg(const std::string& name, void* dst, int dt, int64_t numel) {
-        if (!arena16) return;
-        slots[name] = WSlot{dst, dt, numel, false};
-        names.push_back(name);
-    }
-    void lin(const std::string& name, bf16_t* w, float* b, int out_f, int in_f) {
-        reg(name + ".weight", w, DT_BF16, (int64_t)out_f * in_f);
-        reg(name + ".bias", b, DT_F32, out_f);
-    }
+    WanTrainState* train = nullptr;   // training-mode state (wan_train.inc), created on first use
     void layout();
 };
 
@@ -145,16 +120,7 @@ extern "C" int mi355_wan_create(const mi355_wan_cfg* cfg, mi355_wan** out) {
     e->H = cfg->num_heads; e->D = cfg->num_heads * 128; e->F = cfg->ffn_dim; e->L = cfg->num_layers; e->KP = KP;
     e->NO = cfg->out_channels * 4;
     e->layout();
-    const size_t cap16 = e->used16, cap32 = e->used32;
-    hipError_t e1 = hipMalloc((void**)&e->arena16, cap16);
-    hipError_t e2 = hipMalloc((void**)&e->arena32, cap32);
-    if (e1 != hipSuccess || e2 != hipSuccess) {
-        int r = errorf("mi355_wan_create: hipMalloc of %zu + %zu bytes failed", cap16, cap32);
-        if (e->arena16) (void)hipFree(e->arena16);
-        if (e->arena32) (void)hipFree(e->arena32);
-        delete e;
-        return r;
-    }
+    if (e->alloc("mi355_wan_create") != 0) { delete e; return 1; }
     e->layout();
     *out = e;
     return 0;
@@ -163,38 +129,21 @@ extern "C" int mi355_wan_create(const mi355_wan_cfg* cfg, mi355_wan** out) {
 extern "C" int mi355_wan_destroy(mi355_wan* e) {
     if (!e) return 0;
     wan_train_release_engine(e);
-    if (e->arena16) (void)hipFree(e->arena16);
-    if (e->arena32) (void)hipFree(e->arena32);
+    e->release();
     delete e;
     return 0;
 }
 extern "C" int mi355_wan_num_params(mi355_wan* e) { return e ? (int)e->names.size() : 0; }
-extern "C" const char* mi355_wan_param_name(mi355_wan* e, int i) {
-    if (!e || i < 0 || i >= (int)e->names.size()) return nullptr;
-    return e->names[i].c_str();
-}
+extern "C" const char* mi355_wan_param_name(mi355_wan* e, int i) { return e ? e->param_name(i) : nullptr; }
 extern "C" int mi355_wan_bind_weight(mi355_wan* e, const char* name, const void* src, int dtype, int ndim, const int64_t* shape,
                                      void* stream) {
     if (!e || !name || !src) return errorf("mi355_wan_bind_weight: null argument");
-    auto it = e->slots.find(name);
-    if (it == e->slots.end()) return errorf("mi355_wan_bind_weight: unknown parameter '%s'", name);
-    int64_t n = 1;
-    for (int i = 0; i < ndim; ++i) n *= shape[i];
-    if (n != it->second.numel)
-        return errorf("mi355_wan_bind_weight: '%s' has %lld elements, expected %lld", name, (long long)n, (long long)it->second.numel);
-    if (dtype < 0 || dtype > 2) return errorf("mi355_wan_bind_weight: bad dtype %d", dtype);
-    HIPCHK(launch_convert(src, dtype, it->second.dst, it->second.dst_dt, n, (hipStream_t)stream));
-    it->second.bound = true;
+    CHK(e->bind("mi355_wan_bind_weight", name, src, dtype, ndim, shape, (hipStream_t)stream));
     e->derived_dirty = true;
     wan_train_mark_dirty(e);           // the transposed copies the backward's dgrad GEMMs read are stale
     return 0;
 }
-extern "C" int mi355_wan_weights_ready(mi355_wan* e) {
-    if (!e) return errorf("null engine");
-    for (auto& kv : e->slots)
-        if (!kv.second.bound) return errorf("parameter '%s' has not been bound", kv.first.c_str());
-    return 0;
-}
+extern "C" int mi355_wan_weights_ready(mi355_wan* e) { return e ? e->ready() : errorf("null engine"); }
 
 // -------------------------------------------------------------------------------------- plan
 struct mi355_wan_plan {
@@ -214,6 +163,7 @@ struct mi355_wan_plan {
     float* max2_part;          // scratch of the kernel that measures them
     std::vector<float> host_t, host_sc;
     int mod_cols;
+    mi355_wan_train* train = nullptr;   // training workspace (wan_train.inc), created by the first training-mode forward
 };
 
 extern "C" int mi355_wan_plan_create(mi355_wan* e, int batch, int n_cfg, int latent_t, int latent_h, int latent_w, int n_text,
@@ -231,49 +181,24 @@ extern "C" int mi355_wan_plan_create(mi355_wan* e, int batch, int n_cfg, int lat
     const int D = e->D, F = e->F;
     p->mod_cols = e->L * 6 * D + 2 * D;
     const int64_t rows_cond = (int64_t)max_steps * p->Bp;
-    size_t off = 0;
-    auto take = [&](int64_t elems, int esz) {
-        size_t o = off;
-        off += (((size_t)elems * esz) + 255) & ~(size_t)255;
-        return o;
-    };
     const int64_t qk_el = (int64_t)p->Bp * e->H * p->S_pad * 128;
     const int64_t kx_el = (int64_t)p->Bp * e->H * p->Nt_pad * 128;
     const int64_t nl = (int64_t)batch * p->n_lat;
-    size_t o_pat = take((int64_t)p->M * e->KP, 2), o_x = take((int64_t)p->M * D, 2), o_xn = take((int64_t)p->M * D, 2);
-    size_t o_qkb = take((int64_t)p->M * 2 * D, 2), o_q = take(qk_el, 2), o_k = take(qk_el, 2), o_vT = take(qk_el, 2);
-    size_t o_o = take((int64_t)p->M * D, 2), o_hid = take((int64_t)p->M * F, 2), o_v = take((int64_t)p->Bp * p->n_lat, 2);
-    size_t o_ctx = take((int64_t)p->Mc * D, 2), o_c1 = take((int64_t)p->Mc * D, 2), o_kvb = take((int64_t)p->Mc * 2 * D, 2);
-    size_t o_kx = take(kx_el * e->L, 2), o_vTx = take(kx_el * e->L, 2);
-    size_t o_tpi = take(rows_cond * e->cfg.freq_dim, 2), o_h1 = take(rows_cond * D, 2), o_temb = take(rows_cond * D, 2);
-    size_t o_semb = take(rows_cond * D, 2), o_tp6 = take(rows_cond * 6 * D, 2), o_mod = take(rows_cond * p->mod_cols, 2);
-    size_t o_cs = take((int64_t)p->S * 64, 8), o_t = take(rows_cond, 4), o_sc = take(3 * (int64_t)max_steps, 4);
-    size_t o_ii = take(nl, 4), o_it = take((int64_t)(max_steps + 1) * nl, 4), o_in = take((int64_t)max_steps * nl, 4);
-    size_t o_il = take((int64_t)max_steps * batch, 4);
-    size_t o_ipe = take((int64_t)batch * n_text * e->cfg.text_dim, 2), o_ine = take((int64_t)batch * n_text * e->cfg.text_dim, 2);
-    size_t o_max2 = take((int64_t)2 * p->Bp * e->H, 4), o_m2p = take((int64_t)p->Bp * norm_rope_parts(p->S) * e->H, 4);
-    p->ws_bytes = off;
-    if (hipMalloc((void**)&p->ws, off) != hipSuccess) {
-        int r = errorf("mi355_wan_plan_create: hipMalloc of %zu bytes failed", off);
-        delete p;
-        return r;
-    }
-    if (hipMemset(p->ws, 0, off) != hipSuccess) {   // padded key rows / columns of q, k, vT, kx, vTx must stay finite
-        (void)hipFree(p->ws);
-        delete p;
-        return errorf("mi355_wan_plan_create: hipMemset failed");
-    }
-    char* w = p->ws;
-    p->patches = (bf16_t*)(w + o_pat); p->x = (bf16_t*)(w + o_x); p->xn = (bf16_t*)(w + o_xn); p->qkbuf = (bf16_t*)(w + o_qkb);
-    p->q = (bf16_t*)(w + o_q); p->k = (bf16_t*)(w + o_k); p->vT = (bf16_t*)(w + o_vT); p->o = (bf16_t*)(w + o_o);
-    p->hid = (bf16_t*)(w + o_hid); p->v = (bf16_t*)(w + o_v); p->ctx = (bf16_t*)(w + o_ctx); p->c1 = (bf16_t*)(w + o_c1);
-    p->kvbuf = (bf16_t*)(w + o_kvb); p->kx = (bf16_t*)(w + o_kx); p->vTx = (bf16_t*)(w + o_vTx);
-    p->tproj_in = (bf16_t*)(w + o_tpi); p->h1 = (bf16_t*)(w + o_h1); p->temb = (bf16_t*)(w + o_temb); p->semb = (bf16_t*)(w + o_semb);
-    p->tp6 = (bf16_t*)(w + o_tp6); p->mod_all = (bf16_t*)(w + o_mod);
-    p->cs = (float2*)(w + o_cs); p->t_dev = (float*)(w + o_t); p->scal = (float*)(w + o_sc);
-    p->io_init = w + o_ii; p->io_traj = w + o_it; p->io_noise = (float*)(w + o_in); p->io_lp = (float*)(w + o_il);
-    p->io_pe = (bf16_t*)(w + o_ipe); p->io_ne = (bf16_t*)(w + o_ine);
-    p->max2 = (unsigned*)(w + o_max2); p->max2_part = (float*)(w + o_m2p);
+    Carver c;
+    c.take(p->patches, (int64_t)p->M * e->KP); c.take(p->x, (int64_t)p->M * D); c.take(p->xn, (int64_t)p->M * D);
+    c.take(p->qkbuf, (int64_t)p->M * 2 * D); c.take(p->q, qk_el); c.take(p->k, qk_el); c.take(p->vT, qk_el);
+    c.take(p->o, (int64_t)p->M * D); c.take(p->hid, (int64_t)p->M * F); c.take(p->v, (int64_t)p->Bp * p->n_lat);
+    c.take(p->ctx, (int64_t)p->Mc * D); c.take(p->c1, (int64_t)p->Mc * D); c.take(p->kvbuf, (int64_t)p->Mc * 2 * D);
+    c.take(p->kx, kx_el * e->L); c.take(p->vTx, kx_el * e->L);
+    c.take(p->tproj_in, rows_cond * e->cfg.freq_dim); c.take(p->h1, rows_cond * D); c.take(p->temb, rows_cond * D);
+    c.take(p->semb, rows_cond * D); c.take(p->tp6, rows_cond * 6 * D); c.take(p->mod_all, rows_cond * p->mod_cols);
+    c.take(p->cs, (int64_t)p->S * 64); c.take(p->t_dev, rows_cond); c.take(p->scal, 3 * (int64_t)max_steps);
+    c.take(p->io_init, nl * 4); c.take(p->io_traj, (int64_t)(max_steps + 1) * nl * 4); c.take(p->io_noise, (int64_t)max_steps * nl);
+    c.take(p->io_lp, (int64_t)max_steps * batch);
+    c.take(p->io_pe, (int64_t)batch * n_text * e->cfg.text_dim); c.take(p->io_ne, (int64_t)batch * n_text * e->cfg.text_dim);
+    c.take(p->max2, (int64_t)2 * p->Bp * e->H); c.take(p->max2_part, (int64_t)p->Bp * norm_rope_parts(p->S) * e->H);
+    // zeroed: the padded key rows / columns of q, k, vT, kx, vTx must stay finite
+    if (c.alloc(&p->ws, &p->ws_bytes, true, "mi355_wan_plan_create") != 0) { delete p; return 1; }
     // rotary table (WanRotaryPosEmbed): head_dim 128 -> t / h / w axes of 44 / 42 / 42 features, float64 angles, adjacent pairs
     {
         const int hw = 2 * (128 / 6), ax[3] = {128 - 2 * hw, hw, hw};

@@ -21,7 +21,7 @@ struct WanTrainState {       // per engine
     std::vector<WBlkWT> wt;
     bf16_t* projT = nullptr;
     bool dirty = true;
-    std::map<std::string, float*> grads;
+    GradRegistry grads;
 };
 struct mi355_wan_train {     // per plan
     mi355_wan_plan* p;
@@ -35,34 +35,25 @@ struct mi355_wan_train {     // per plan
     int M_pad, Mc_pad;
 };
 
-static std::map<mi355_wan*, WanTrainState*> g_wan_train_engines;
-static std::map<mi355_wan_plan*, mi355_wan_train*> g_wan_trains;
-
-static WanTrainState* wan_train_state(mi355_wan* e) {
-    auto it = g_wan_train_engines.find(e);
-    if (it != g_wan_train_engines.end()) return it->second;
-    WanTrainState* s = new WanTrainState();
-    g_wan_train_engines[e] = s;
-    return s;
+static WanTrainState* wan_train_state(mi355_wan* e) {      // created on first use
+    if (!e->train) e->train = new WanTrainState();
+    return e->train;
 }
 static void wan_train_mark_dirty(mi355_wan* e) {
-    auto it = g_wan_train_engines.find(e);
-    if (it != g_wan_train_engines.end()) it->second->dirty = true;
+    if (e->train) e->train->dirty = true;
 }
 static void wan_train_release(mi355_wan_plan* p) {
-    auto it = g_wan_trains.find(p);
-    if (it == g_wan_trains.end()) return;
-    t_wgrad_streams_destroy(it->second->sc);
-    if (it->second->ws) (void)hipFree(it->second->ws);
-    delete it->second;
-    g_wan_trains.erase(it);
+    if (!p->train) return;
+    t_wgrad_streams_destroy(p->train->sc);
+    if (p->train->ws) (void)hipFree(p->train->ws);
+    delete p->train;
+    p->train = nullptr;
 }
 static void wan_train_release_engine(mi355_wan* e) {
-    auto it = g_wan_train_engines.find(e);
-    if (it == g_wan_train_engines.end()) return;
-    if (it->second->arenaT) (void)hipFree(it->second->arenaT);
-    delete it->second;
-    g_wan_train_engines.erase(it);
+    if (!e->train) return;
+    if (e->train->arenaT) (void)hipFree(e->train->arenaT);
+    delete e->train;
+    e->train = nullptr;
 }
 
 static bool wan_trainable_name(const std::string& n) {
@@ -77,17 +68,9 @@ static bool wan_trainable_name(const std::string& n) {
 extern "C" int mi355_wan_set_grad(mi355_wan* e, const char* name, float* grad) {
     if (!e || !name) return errorf("mi355_wan_set_grad: null argument");
     if (e->slots.find(name) == e->slots.end()) return errorf("mi355_wan_set_grad: unknown parameter '%s'", name);
-    WanTrainState* s = wan_train_state(e);
-    if (!grad) {
-        auto it = s->grads.find(name);
-        if (it != s->grads.end()) { grad_buf_mark(it->second, DT_F32); s->grads.erase(it); }
-        return 0;
-    }
-    if (!wan_trainable_name(name))
+    if (grad && !wan_trainable_name(name))
         return errorf("mi355_wan_set_grad: '%s' lies outside the native backward's scope (the linear layers inside the transformer blocks)", name);
-    { auto prev = s->grads.find(name); if (prev != s->grads.end() && prev->second != grad) grad_buf_mark(prev->second, DT_F32); }   // (a re-registration un-marks the buffer it replaces)
-    s->grads[name] = grad;
-    grad_buf_mark(grad, DT_F32);
+    wan_train_state(e)->grads.set(name, grad);
     return 0;
 }
 extern "C" int mi355_wan_set_grad_typed(mi355_wan* e, const char* name, void* grad, int dtype) {
@@ -99,7 +82,6 @@ extern "C" int mi355_wan_set_grad_typed(mi355_wan* e, const char* name, void* gr
 }
 extern "C" int mi355_wan_clear_grads(mi355_wan* e) {
     if (!e) return errorf("null engine");
-    for (auto& kv : wan_train_state(e)->grads) grad_buf_mark(kv.second, DT_F32);
     wan_train_state(e)->grads.clear();
     return 0;
 }
@@ -109,40 +91,24 @@ extern "C" int mi355_wan_grad_supported(mi355_wan* e, const char* name) {
     return wan_trainable_name(name) ? 0 : 1;
 }
 extern "C" int64_t mi355_wan_plan_training_bytes(mi355_wan_plan* p) {
-    auto it = g_wan_trains.find(p);
-    return it == g_wan_trains.end() ? 0 : (int64_t)it->second->ws_bytes;
+    return p && p->train ? (int64_t)p->train->ws_bytes : 0;
 }
 
-static float* wgrad_of(mi355_wan* e, const std::string& name) {
-    WanTrainState* s = wan_train_state(e);
-    auto it = s->grads.find(name);
-    return it == s->grads.end() ? nullptr : it->second;
-}
+static float* wgrad_of(mi355_wan* e, const std::string& name) { return wan_train_state(e)->grads.find(name); }
 
 // ---- transposed weights (dgrad operands) -------------------------------------------------------------------------------------------
 static int wan_ensure_transposed(mi355_wan* e, hipStream_t st) {
     WanTrainState* s = wan_train_state(e);
     const int D = e->D, F = e->F, L = e->L, NO = e->NO;
     if (!s->arenaT) {
-        size_t off = 0;
-        auto take = [&](int64_t n) { size_t o = off; off += ((size_t)n * 2 + 255) & ~(size_t)255; return o; };
-        std::vector<size_t> ob;
-        for (int i = 0; i < L; ++i) {
-            ob.push_back(take((int64_t)D * 3 * D)); ob.push_back(take((int64_t)D * D)); ob.push_back(take((int64_t)D * D)); ob.push_back(take((int64_t)D * D));
-            ob.push_back(take((int64_t)D * F)); ob.push_back(take((int64_t)F * D));
-        }
-        const size_t o_proj = take((int64_t)D * NO);
-        s->bytes = off;
-        if (hipMalloc((void**)&s->arenaT, off) != hipSuccess) return errorf("wan training: hipMalloc of %zu bytes for the transposed weights failed", off);
-        char* a = s->arenaT;
+        Carver c;
         s->wt.resize(L);
-        for (int i = 0; i < L; ++i) {
-            WBlkWT& w = s->wt[i];
-            const size_t* o = &ob[(size_t)i * 6];
-            w.qkv = (bf16_t*)(a + o[0]); w.o = (bf16_t*)(a + o[1]); w.q2 = (bf16_t*)(a + o[2]); w.o2 = (bf16_t*)(a + o[3]);
-            w.ff1 = (bf16_t*)(a + o[4]); w.ff2 = (bf16_t*)(a + o[5]);
+        for (WBlkWT& w : s->wt) {
+            c.take(w.qkv, (int64_t)D * 3 * D); c.take(w.o, (int64_t)D * D); c.take(w.q2, (int64_t)D * D); c.take(w.o2, (int64_t)D * D);
+            c.take(w.ff1, (int64_t)D * F); c.take(w.ff2, (int64_t)F * D);
         }
-        s->projT = (bf16_t*)(a + o_proj);
+        c.take(s->projT, (int64_t)D * NO);
+        CHK(c.alloc(&s->arenaT, &s->bytes, false, "wan training", " for the transposed weights"));
         s->dirty = true;
     }
     if (!s->dirty) return 0;
@@ -163,8 +129,7 @@ static int wan_ensure_transposed(mi355_wan* e, hipStream_t st) {
 
 // ---- training workspace ----------------------------------------------------------------------------------------------
 static int wan_train_of(mi355_wan_plan* p, mi355_wan_train** out) {
-    auto it = g_wan_trains.find(p);
-    if (it != g_wan_trains.end()) { *out = it->second; return 0; }
+    if (p->train) { *out = p->train; return 0; }
     mi355_wan* e = p->e;
     const int D = e->D, F = e->F, L = e->L, H = e->H, NO = e->NO;
     const int M = p->M, Mc = p->Mc;
@@ -173,73 +138,42 @@ static int wan_train_of(mi355_wan_plan* p, mi355_wan_train** out) {
     mi355_wan_train* t = new mi355_wan_train();
     t->p = p;
     t->M_pad = (M + 63) / 64 * 64; t->Mc_pad = (Mc + 63) / 64 * 64;
-    size_t off = 0;
-    auto take = [&](int64_t elems, int esz) { size_t o = off; off += (((size_t)elems * esz) + 255) & ~(size_t)255; return o; };
-    struct BO { size_t v[18]; };
-    std::vector<BO> bo(L);
-    for (int i = 0; i < L; ++i) {
-        size_t* o = bo[i].v;
-        int n = 0;
-        for (int j = 0; j < 8; ++j) o[n++] = take((int64_t)M * D, 2);                          // x_in xn1 o1 x_mid1 xn2 o2 x_mid2 xn3
-        o[n++] = take((int64_t)M * F, 2);                                                      // pre
-        o[n++] = take(qk_el, 2); o[n++] = take(qk_el, 2); o[n++] = take(qk_el, 2); o[n++] = take(qk_el, 2);     // q k vT q2
-        o[n++] = take(bhs, 4); o[n++] = take(bhs, 4); o[n++] = take(M, 4); o[n++] = take(M, 4); o[n++] = take(M, 4);   // lse1 lse2 rstd_q rstd_k rstd_q2
+    TrainScratch& sc = t->sc;
+    Carver c;
+    t->blk.resize(L);
+    for (WTrainBlk& k : t->blk) {
+        c.take(k.x_in, (int64_t)M * D); c.take(k.xn1, (int64_t)M * D); c.take(k.o1, (int64_t)M * D); c.take(k.x_mid1, (int64_t)M * D);
+        c.take(k.xn2, (int64_t)M * D); c.take(k.o2, (int64_t)M * D); c.take(k.x_mid2, (int64_t)M * D); c.take(k.xn3, (int64_t)M * D);
+        c.take(k.pre, (int64_t)M * F);
+        c.take(k.q, qk_el); c.take(k.k, qk_el); c.take(k.vT, qk_el); c.take(k.q2, qk_el);
+        c.take(k.lse1, bhs); c.take(k.lse2, bhs); c.take(k.rstd_q, M); c.take(k.rstd_k, M); c.take(k.rstd_q2, M);
     }
-    const size_t o_xf = take((int64_t)M * D, 2), o_mod = take((int64_t)p->Bp * p->mod_cols, 2);
-    const size_t o_kx = take(kx_el * L, 2), o_vTx = take(kx_el * L, 2), o_ctx = take((int64_t)Mc * D, 2), o_rkx = take((int64_t)L * Mc, 4);
-    const size_t o_dx = take((int64_t)M * D, 2), o_dproj = take((int64_t)M * NO, 2), o_widec = take((int64_t)Mc * 2 * D, 2);
-    const size_t o_g1 = take((int64_t)M * D, 2), o_g2 = take((int64_t)M * D, 2), o_g3 = take((int64_t)M * D, 2);
-    const size_t o_wide = take((int64_t)M * (3 * D + F), 2), o_hid = take((int64_t)M * F, 2);
+    c.take(t->x_final, (int64_t)M * D); c.take(t->mod, (int64_t)p->Bp * p->mod_cols);
+    c.take(t->kx, kx_el * L); c.take(t->vTx, kx_el * L); c.take(t->ctx, (int64_t)Mc * D); c.take(t->rstd_kx, (int64_t)L * Mc);
+    c.take(t->dx, (int64_t)M * D); c.take(t->dproj, (int64_t)M * NO); c.take(t->widec, (int64_t)Mc * 2 * D);
+    c.take(sc.g1, (int64_t)M * D); c.take(sc.g2, (int64_t)M * D); c.take(sc.g3, (int64_t)M * D);
+    c.take(sc.wide, (int64_t)M * (3 * D + F)); c.take(sc.hid, (int64_t)M * F);
     // (the cross-attention backward puts its transposed V and its dK / dV -- stride Nt_pad * 128 per (batch, head) -- into the same v / dk / dvh
     // scratch as the self-attention: those three hold the LONGER of the two key counts, a 512-token prompt on a single small frame has
     // Nt_pad > S_pad (ADVICE r4))
     const int64_t kv_el = qk_el > kx_el ? qk_el : kx_el;
-    const size_t o_doh = take(qk_el, 2), o_v = take(kv_el, 2), o_dq = take(qk_el, 2), o_dk = take(kv_el, 2), o_dvh = take(kv_el, 2);
-    const size_t o_delta = take(bhs, 4), o_nld = take(bhs * 2, 4);
+    c.take(sc.doh, qk_el); c.take(sc.v, kv_el); c.take(sc.dq, qk_el); c.take(sc.dk, kv_el); c.take(sc.dvh, kv_el);
+    c.take(sc.delta, bhs); c.take(sc.nld, bhs * 2);
     const int n_slots = get_wgrad_side() ? WG_SLOTS : 1;
     const int rows_T = F > 3 * D ? F : 3 * D;
-    size_t o_aT[WG_SLOTS], o_xT[WG_SLOTS];
     // (operand slots and column-sum partials serve the text-side weight gradients too: rows = the LONGER of the two token counts -- a clip shorter
     // than its prompt overflowed slots sized by the video rows in the first GPU run of this file, profiles/r04t_wan_bwd_diag.txt)
     const int Mmax_pad = t->M_pad > t->Mc_pad ? t->M_pad : t->Mc_pad;
-    for (int i = 0; i < n_slots; ++i) { o_aT[i] = take((int64_t)rows_T * Mmax_pad, 2); o_xT[i] = take((int64_t)F * Mmax_pad, 2); }
-    t->sc.part_floats = (size_t)16 * D * D > (size_t)2 * F * D ? (size_t)16 * D * D : (size_t)2 * F * D;
+    for (int i = 0; i < n_slots; ++i) { c.take(sc.slot[i].aT, (int64_t)rows_T * Mmax_pad); c.take(sc.slot[i].xT, (int64_t)F * Mmax_pad); }
+    sc.part_floats = (size_t)16 * D * D > (size_t)2 * F * D ? (size_t)16 * D * D : (size_t)2 * F * D;
     const int nrt = Mmax_pad / 64 > 64 ? Mmax_pad / 64 : 64;
-    const size_t o_part = take((int64_t)t->sc.part_floats, 4), o_cs = take((int64_t)nrt * F, 4), o_zb = take(F > 3 * D ? F : 3 * D, 4);
-    t->ws_bytes = off;
-    if (hipMalloc((void**)&t->ws, off) != hipSuccess) {
-        delete t;
-        return errorf("wan training: hipMalloc of %zu bytes of activation stash + backward scratch failed", off);
-    }
-    if (hipMemset(t->ws, 0, off) != hipSuccess) { (void)hipFree(t->ws); delete t; return errorf("wan training: hipMemset failed"); }
-    char* w = t->ws;
-    t->blk.resize(L);
-    for (int i = 0; i < L; ++i) {
-        WTrainBlk& k = t->blk[i];
-        const size_t* o = bo[i].v;
-        int n = 0;
-        k.x_in = (bf16_t*)(w + o[n++]); k.xn1 = (bf16_t*)(w + o[n++]); k.o1 = (bf16_t*)(w + o[n++]); k.x_mid1 = (bf16_t*)(w + o[n++]);
-        k.xn2 = (bf16_t*)(w + o[n++]); k.o2 = (bf16_t*)(w + o[n++]); k.x_mid2 = (bf16_t*)(w + o[n++]); k.xn3 = (bf16_t*)(w + o[n++]);
-        k.pre = (bf16_t*)(w + o[n++]);
-        k.q = (bf16_t*)(w + o[n++]); k.k = (bf16_t*)(w + o[n++]); k.vT = (bf16_t*)(w + o[n++]); k.q2 = (bf16_t*)(w + o[n++]);
-        k.lse1 = (float*)(w + o[n++]); k.lse2 = (float*)(w + o[n++]); k.rstd_q = (float*)(w + o[n++]); k.rstd_k = (float*)(w + o[n++]);
-        k.rstd_q2 = (float*)(w + o[n++]);
-    }
-    t->x_final = (bf16_t*)(w + o_xf); t->mod = (bf16_t*)(w + o_mod);
-    t->kx = (bf16_t*)(w + o_kx); t->vTx = (bf16_t*)(w + o_vTx); t->ctx = (bf16_t*)(w + o_ctx); t->rstd_kx = (float*)(w + o_rkx);
-    t->dx = (bf16_t*)(w + o_dx); t->dproj = (bf16_t*)(w + o_dproj); t->widec = (bf16_t*)(w + o_widec);
-    TrainScratch& sc = t->sc;
-    sc.g1 = (bf16_t*)(w + o_g1); sc.g2 = (bf16_t*)(w + o_g2); sc.g3 = (bf16_t*)(w + o_g3);
+    c.take(sc.part, (int64_t)sc.part_floats); c.take(sc.csum, (int64_t)nrt * F); c.take(sc.zero_bias, F > 3 * D ? F : 3 * D);
+    if (c.alloc(&t->ws, &t->ws_bytes, true, "wan training", " of activation stash + backward scratch") != 0) { delete t; return 1; }
     sc.g1c = sc.g2c = sc.g3c = nullptr; sc.widec = t->widec;
-    sc.wide = (bf16_t*)(w + o_wide); sc.hid = (bf16_t*)(w + o_hid);
-    sc.doh = (bf16_t*)(w + o_doh); sc.v = (bf16_t*)(w + o_v); sc.dq = (bf16_t*)(w + o_dq); sc.dk = (bf16_t*)(w + o_dk); sc.dvh = (bf16_t*)(w + o_dvh);
-    sc.delta = (float*)(w + o_delta); sc.nld = (float*)(w + o_nld);
-    for (int i = 0; i < n_slots; ++i) { sc.slot[i].aT = (bf16_t*)(w + o_aT[i]); sc.slot[i].xT = (bf16_t*)(w + o_xT[i]); }
     sc.aT_rows = rows_T; sc.xT_rows = F;
-    sc.part = (float*)(w + o_part); sc.csum = (float*)(w + o_cs); sc.zero_bias = (float*)(w + o_zb);
     sc.tn_default = true;          // weight gradients on row-major operands (train_common.h: measured -1.9 % on the config-D step)
     if (t_wgrad_streams_init(sc, n_slots > 1) != 0) { t_wgrad_streams_destroy(sc); (void)hipFree(t->ws); delete t; return 1; }
-    g_wan_trains[p] = t;
+    p->train = t;
     *out = t;
     return 0;
 }
@@ -273,9 +207,8 @@ extern "C" int mi355_wan_forward_train(mi355_wan_plan* p, void* stream, const vo
 // d loss / d weights from dv = d loss / d v_out [Bp][C][T][h][w] fp32 (v_out = the prediction of the LAST mi355_wan_forward_train on this plan)
 extern "C" int mi355_wan_backward(mi355_wan_plan* p, void* stream, const float* dv) {
     if (!p || !dv) return errorf("mi355_wan_backward: null argument");
-    auto it = g_wan_trains.find(p);
-    if (it == g_wan_trains.end() || !it->second->have_forward) return errorf("mi355_wan_backward: no training-mode forward has run on this plan");
-    mi355_wan_train* t = it->second;
+    if (!p->train || !p->train->have_forward) return errorf("mi355_wan_backward: no training-mode forward has run on this plan");
+    mi355_wan_train* t = p->train;
     mi355_wan* e = p->e;
     hipStream_t st = (hipStream_t)stream;
     CHK(wan_ensure_transposed(e, st));

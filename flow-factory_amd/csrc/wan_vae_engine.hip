@@ -257,19 +257,12 @@ extern "C" int mi355_wvae_plan_create(mi355_wvae* v, int max_batch, int latent_t
     p->v = v; p->B = max_batch; p->T = latent_t; p->h = latent_h; p->w = latent_w;
     p->S = S; p->S_pad = (S + 63) / 64 * 64;
     const int top = v->dims[0];
-    const size_t buf = ((size_t)max_batch * act * 2 + 255) & ~(size_t)255;
-    const size_t sc = ((size_t)S * p->S_pad * 4 + 255) & ~(size_t)255, pb = ((size_t)S * p->S_pad * 2 + 255) & ~(size_t)255;
-    const size_t vt = ((size_t)pad64(top) * p->S_pad * 2 + 255) & ~(size_t)255;
-    p->ws_bytes = 4 * buf + sc + pb + vt;
-    if (hipMalloc((void**)&p->ws, p->ws_bytes) != hipSuccess) {
-        int r = errorf("mi355_wvae_plan_create: hipMalloc of %zu bytes failed", p->ws_bytes);
-        delete p;
-        return r;
-    }
-    char* q = p->ws;
-    p->X = (bf16_t*)q; q += buf; p->Y = (bf16_t*)q; q += buf; p->T1 = (bf16_t*)q; q += buf; p->T2 = (bf16_t*)q; q += buf;
-    p->SC = (float*)q; q += sc; p->P = (bf16_t*)q; q += pb; p->VT = (bf16_t*)q; q += vt;
-    if (hipMemset(p->VT, 0, vt) != hipSuccess) {       // key columns S..S_pad of V^T stay zero (the softmax writes zero probabilities there)
+    const int64_t buf = (int64_t)max_batch * act, vt = (int64_t)pad64(top) * p->S_pad;
+    Carver cv;
+    cv.take(p->X, buf); cv.take(p->Y, buf); cv.take(p->T1, buf); cv.take(p->T2, buf);
+    cv.take(p->SC, (int64_t)S * p->S_pad); cv.take(p->P, (int64_t)S * p->S_pad); cv.take(p->VT, vt);
+    if (cv.alloc(&p->ws, &p->ws_bytes, false, "mi355_wvae_plan_create") != 0) { delete p; return 1; }
+    if (hipMemset(p->VT, 0, (size_t)vt * 2) != hipSuccess) {       // key columns S..S_pad of V^T stay zero (the softmax writes zero probabilities there)
         (void)hipFree(p->ws);
         delete p;
         return errorf("mi355_wvae_plan_create: hipMemset failed");
