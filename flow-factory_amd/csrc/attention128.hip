@@ -166,7 +166,9 @@ __global__ __launch_bounds__(NWAVE * 64, 2) void attn128_kernel(Attn128Params p)
         if (!STATIC && (t == 0 || __any(mx > THR))) {
             mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
             const float delta = (t == 0) ? mx : fmaxf(mx, 0.f);
-            const float alpha = __builtin_amdgcn_exp2f(-delta);
+            // (the first tile may LOWER m: delta < 0.  l and O are still zero then, and for a query whose first-tile scores are all below -128
+            //  2^(-delta) overflows to inf: 0 * inf = NaN in l and O.  Clamped: the factor of the first tile is 1, every later one is unchanged.)
+            const float alpha = __builtin_amdgcn_exp2f(fminf(-delta, 0.f));
             m_run += delta;
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb)

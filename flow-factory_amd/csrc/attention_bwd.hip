@@ -282,6 +282,21 @@ __global__ __launch_bounds__(NWAVES * 64, 2) void attn_bwd_dkv_tr_kernel(AttnBwd
 // ---- pass 2: dQ.  LDS stage: K [64 keys][64 d] | V [64 keys][64 d]; ring of 4, two workgroups per CU
 constexpr int ST2T = 2 * TILE;
 constexpr int NST2 = 4;
+// Tail hazard of the UN-MASKED dQ passes (the software-pipelined kernels below).  A zero padding key of the last tile has score 0, so its
+// probability is 2^(0 - L) for a query with log-sum-exp L: harmless while it is finite (dZ * k_pad = dZ * 0 = 0), but for a query whose every real
+// score is far below zero it overflows -- L < -128: P = inf, dZ = inf, inf * 0 = NaN in that query's dQ row (measured: tests/
+// test_gpu_attention_edges.py::test_bwd64_operand_classes, rows with every score in [-200, -140]).  So when S % 64 != 0 the launch is split per
+// block of p.dq_rows queries: a block with any L < -60 (2^60 * |dP - Delta| is still far from overflow; no score proven <= 60 gets there) is left to
+// the masked kernel right below, which is bit-identical on all other rows; every other block runs the pipelined pass as before.  Every WAVE scans the
+// whole block (2 or 4 loads per lane) and votes, so the answer is workgroup-uniform without a barrier and without LDS: __syncthreads_or would bring a
+// static LDS variable, and the pipelined kernels need their dynamic LDS to start at address 0 (they trap otherwise).
+__device__ __forceinline__ bool dq_tail_hazard(const AttnBwdParams& p, long bh, int block) {
+    int bad = 0;
+    const int r0 = block * p.dq_rows, r1 = min(r0 + p.dq_rows, p.S);
+    for (int r = r0 + (int)(threadIdx.x & 63); r < r1; r += 64) bad |= !(p.lse[bh * p.S_pad + r] >= -60.f);      // (a NaN counts as a hazard)
+    return __any(bad) != 0;
+}
+
 __global__ __launch_bounds__(NWAVES * 64, 2) void attn_bwd_dq_tr_kernel(AttnBwdParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -297,6 +312,7 @@ __global__ __launch_bounds__(NWAVES * 64, 2) void attn_bwd_dq_tr_kernel(AttnBwdP
     }
     const int qblk = wid % nqb;
     const long bh = wid / nqb;
+    if (p.dq_mode == 2 && !dq_tail_hazard(p, bh, qblk * QB / p.dq_rows)) return;      // only the blocks the un-masked pass leaves out
     const bf16_t* Kg = p.k + bh * p.S_pad * 64;
     const bf16_t* Vg = p.v + bh * p.S_pad * 64;
     const int q_row = qblk * QB + wave * 32 + lq;
@@ -416,7 +432,9 @@ __global__ __launch_bounds__(NWAVES * 64, 2) void attn_bwd_dq_tr_kernel(AttnBwdP
 // the kernels above (kept: mi355_tune_set(43, 0), and the A/B of tests/test_gpu_backward.py).
 // CONTRACT (both pairs of kernels relied on it already -- a masked probability times a NaN is a NaN): rows [S, S_pad) of q, k, v and dO are
 // ZERO.  The engines' workspaces are zero-initialised and only rows < S are ever written; the pipelined loops carry no tail masks at all (a zero
-// query row adds exactly 0 to dK^T / dV^T, a zero key row exactly 0 to dQ^T).
+// query row adds exactly 0 to dK^T / dV^T, a zero key row exactly 0 to dQ^T).  "Exactly 0" needs the zero row's probability to be FINITE: true in the
+// dK/dV pass (a padding query has L = 0 from the prep kernel: P = 1) and in the dQ pass for every query with L >= -60; blocks with a lower L go to
+// the masked kernel (dq_tail_hazard above).
 #include "attn_bwd64_asm.inc"
 
 // ABL (timing only, results garbage; mi355_tune_set(43, 2..5) under MI355_ALLOW_ABLATION=1): 1 no exp / scale / pack, 2 no LDS reads, 3 no barrier /
@@ -515,6 +533,7 @@ __global__ __launch_bounds__(NWAVES * 64, 2) void attn_bwd_dq_pipe_kernel(AttnBw
     const int qblk = wid % nqb;
     const long bh = wid / nqb;
     if ((unsigned)(size_t)(__attribute__((address_space(3))) char*)smem != 0u) __builtin_trap();
+    if (p.dq_mode == 1 && dq_tail_hazard(p, bh, qblk)) return;      // no tail masks here: the masked kernel takes this block
     const bf16_t* Kg = p.k + bh * p.S_pad * 64;
     const bf16_t* Vg = p.v + bh * p.S_pad * 64;
     const int q_row = qblk * QB + wave * 32 + lq;
@@ -655,6 +674,7 @@ __global__ __launch_bounds__(NWAVES * 64, 1) void attn_bwd_dq_pipe2_kernel(AttnB
     const int qblk = wid % nqb;
     const long bh = wid / nqb;
     if ((unsigned)(size_t)(__attribute__((address_space(3))) char*)smem != 0u) __builtin_trap();
+    if (p.dq_mode == 1 && dq_tail_hazard(p, bh, qblk)) return;      // no tail masks here: the masked kernel takes this block
     const bf16_t* Kg = p.k + bh * p.S_pad * 64;
     const bf16_t* Vg = p.v + bh * p.S_pad * 64;
     const int q0 = qblk * QB + wave * 64 + lq, q1 = q0 + 32;
@@ -726,6 +746,18 @@ hipError_t launch_attention_bwd(const AttnBwdParams& p, hipStream_t stream) {
         attr_set = true;
     }
     const int nb = (p.S + 32 * NWAVES - 1) / (32 * NWAVES);
+    // the un-masked dQ pass + (only where the last key tile has padding: dq_tail_hazard) the masked round-3 kernel for the blocks it leaves out
+    auto launch_dq_split = [&](void (*dq)(AttnBwdParams), int nblk, int rows) {
+        AttnBwdParams a = p;
+        a.dq_rows = rows;
+        a.dq_mode = p.S % TB != 0 ? 1 : 0;
+        hipLaunchKernelGGL(dq, dim3(nblk * p.H * p.B), dim3(NWAVES * 64), NST2 * ST2T, stream, a);
+        if (a.dq_mode) {
+            a.dq_mode = 2;
+            hipLaunchKernelGGL(attn_bwd_dq_tr_kernel, dim3(nb * p.H * p.B), dim3(NWAVES * 64), NST2 * ST2T, stream, a);
+        }
+        return hipGetLastError();
+    };
     if (g_attn_bwd_pipe == 6) {      // two 32-row blocks per wave, one workgroup per CU
         static bool attr_set3 = false;
         if (!attr_set3) {
@@ -735,8 +767,7 @@ hipError_t launch_attention_bwd(const AttnBwdParams& p, hipStream_t stream) {
         }
         const int nb2 = (p.S + 64 * NWAVES - 1) / (64 * NWAVES);
         hipLaunchKernelGGL(attn_bwd_dkv_pipe2_kernel, dim3(nb2 * p.H * p.B), dim3(NWAVES * 64), NST1 * ST1T, stream, p);
-        hipLaunchKernelGGL(attn_bwd_dq_pipe2_kernel, dim3(nb2 * p.H * p.B), dim3(NWAVES * 64), NST2 * ST2T, stream, p);
-        return hipGetLastError();
+        return launch_dq_split(attn_bwd_dq_pipe2_kernel, nb2, 64 * NWAVES);
     }
     if (g_attn_bwd_pipe) {
         void (*dkv)(AttnBwdParams) = g_attn_bwd_pipe == 2 ? attn_bwd_dkv_pipe_kernel<1> : g_attn_bwd_pipe == 3 ? attn_bwd_dkv_pipe_kernel<2>
@@ -750,8 +781,7 @@ hipError_t launch_attention_bwd(const AttnBwdParams& p, hipStream_t stream) {
             attr_set2[vi] = true;
         }
         hipLaunchKernelGGL(dkv, dim3(nb * p.H * p.B), dim3(NWAVES * 64), NST1 * ST1T, stream, p);
-        hipLaunchKernelGGL(attn_bwd_dq_pipe_kernel, dim3(nb * p.H * p.B), dim3(NWAVES * 64), NST2 * ST2T, stream, p);
-        return hipGetLastError();
+        return launch_dq_split(attn_bwd_dq_pipe_kernel, nb, 32 * NWAVES);
     }
     hipLaunchKernelGGL(attn_bwd_dkv_tr_kernel, dim3(nb * p.H * p.B), dim3(NWAVES * 64), NST1 * ST1T, stream, p);
     hipLaunchKernelGGL(attn_bwd_dq_tr_kernel, dim3(nb * p.H * p.B), dim3(NWAVES * 64), NST2 * ST2T, stream, p);

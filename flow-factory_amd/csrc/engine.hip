@@ -1028,6 +1028,23 @@ extern "C" int mi355_op_attention(void* stream, const void* q, const void* k, co
     return 0;
 }
 
+// mi355_op_attention with the fields it pins exposed (unit tests of the kernel edges): q_prescaled, the |score| bound as an argument
+// (0 = none: running-max kernel; (0, 60] = static softmax) and the optional per-query log2-sum-exp [B][H][S_pad] of the training-mode forward
+extern "C" int mi355_op_attention_ex(void* stream, const void* q, const void* k, const void* vT, void* o_img, void* o_ctx, int B, int H, int S,
+                                     int S_pad, int n_img, int q_prescaled, float score_bound, float* lse) {
+    if (!q || !k || !vT) return errorf("mi355_op_attention_ex: null argument");
+    if (B <= 0 || H <= 0 || S <= 0 || S_pad < S || S_pad % 64) return errorf("mi355_op_attention_ex: bad shape (S %d, S_pad %d)", S, S_pad);
+    if (n_img < 0 || n_img > S) return errorf("mi355_op_attention_ex: n_img %d outside [0, S = %d]", n_img, S);
+    if (n_img > 0 && !o_img) return errorf("mi355_op_attention_ex: o_img is NULL but n_img > 0");
+    if (n_img < S && !o_ctx) return errorf("mi355_op_attention_ex: o_ctx is NULL but S > n_img");
+    if (!(score_bound >= 0.f)) return errorf("mi355_op_attention_ex: negative score_bound");
+    if (get_attn_variant() == 0 && q_prescaled) return errorf("mi355_op_attention_ex: the plain kernel (mi355_tune_set(1, 0)) scales the scores itself: q_prescaled must be 0");
+    AttnParams a{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)vT, (bf16_t*)o_img, (bf16_t*)o_ctx, B, H, S, S_pad, n_img, q_prescaled, score_bound,
+                 lse};
+    HIPCHK(attn_p(a, (hipStream_t)stream));
+    return 0;
+}
+
 extern "C" int mi355_op_ln_modulate(void* stream, const void* x, const void* shift, const void* scale, void* out, int M, int D,
                                     int rows_per_sample, float eps) {
     if (!x || !shift || !scale || !out) return errorf("mi355_op_ln_modulate: null argument");

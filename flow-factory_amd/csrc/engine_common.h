@@ -135,13 +135,18 @@ struct Carver {
         recs.push_back(Rec{&dst, off});
         off += ((size_t)elems * sizeof(T) + 255) & ~(size_t)255;
     }
-    // `zero`: hipMemset of the whole workspace.  A failure leaves *base null; the message reads "<who>: hipMalloc of N bytes<what> failed".
+    // `zero`: hipMemset of the whole workspace, complete on return.  A failure leaves *base null; the message reads "<who>: hipMalloc of N bytes<what> failed".
     int alloc(char** base, size_t* bytes, bool zero, const char* who, const char* what = "") {
         if (hipMalloc((void**)base, off) != hipSuccess) {
             *base = nullptr;
             return errorf("%s: hipMalloc of %zu bytes%s failed", who, off, what);
         }
-        if (zero && hipMemset(*base, 0, off) != hipSuccess) {
+        // (hipMemset on device memory may return before the fill has run, and it runs on the NULL stream, which the engines' non-blocking streams do
+        //  not wait for -- gemm_tn.hip met exactly that.  The zero padding of these workspaces is a CONTRACT of the attention backward passes
+        //  (attention_bwd.hip), so the fill has completed before any pointer is handed out.  Plans and training states are created outside stream
+        //  capture: every zeroed workspace belongs to a *_plan_create or to the first training call of a plan, and RolloutGraph captures only the
+        //  rollout loop of an existing plan.  So a device synchronise is legal here, and it is paid once per workspace, never per step.)
+        if (zero && (hipMemset(*base, 0, off) != hipSuccess || hipDeviceSynchronize() != hipSuccess)) {
             (void)hipFree(*base);
             *base = nullptr;
             return errorf("%s: hipMemset failed", who);

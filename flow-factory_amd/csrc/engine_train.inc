@@ -854,3 +854,41 @@ extern "C" int mi355_op_attention_fwd_bwd(void* stream, const void* q, const voi
     if (err != hipSuccess) return errorf("mi355_op_attention_fwd_bwd: %s", hipGetErrorString(err));
     return 0;
 }
+
+// The same with the fields the helper above pins exposed: the image / context split of o and dO (AttnBwdPrepParams::n_img; do_ctx may be NULL:
+// that part of the output has no consumer), the |score| bound as an argument, and optional copies of the forward's log2-sum-exp and of the
+// backward's delta = rowsum(dO * O), both [B][H][S_pad] fp32 (rows >= S: zero, as the zeroed scratch holds them).
+extern "C" int mi355_op_attention_fwd_bwd_ex(void* stream, const void* q, const void* k, const void* vT, const void* do_img, const void* do_ctx,
+                                             void* o_img, void* o_ctx, void* dq, void* dk, void* dv, int B, int H, int S, int S_pad, int n_img,
+                                             float score_bound, float* lse_out, float* delta_out) {
+    if (!q || !k || !vT || !dq || !dk || !dv) return errorf("mi355_op_attention_fwd_bwd_ex: null argument");
+    if (B <= 0 || H <= 0 || S <= 0 || S_pad < S || S_pad % 64) return errorf("mi355_op_attention_fwd_bwd_ex: bad shape (S %d, S_pad %d)", S, S_pad);
+    if (n_img < 0 || n_img > S) return errorf("mi355_op_attention_fwd_bwd_ex: n_img %d outside [0, S = %d]", n_img, S);
+    if (n_img > 0 && (!o_img || !do_img)) return errorf("mi355_op_attention_fwd_bwd_ex: o_img / do_img is NULL but n_img > 0");
+    if (n_img < S && !o_ctx) return errorf("mi355_op_attention_fwd_bwd_ex: o_ctx is NULL but S > n_img");
+    if (!(score_bound >= 0.f)) return errorf("mi355_op_attention_fwd_bwd_ex: negative score_bound");
+    if (get_attn_variant() == 0) return errorf("mi355_op_attention_fwd_bwd_ex: q is pre-scaled here, which the plain forward (mi355_tune_set(1, 0)) does not take");
+    hipStream_t st = (hipStream_t)stream;
+    const size_t bhs = (size_t)B * H * S_pad, el = bhs * 64;
+    char* ws = nullptr;
+    const size_t bytes = el * 2 * 2 + bhs * 4 * 4;
+    HIPCHK(hipMalloc((void**)&ws, bytes));
+    hipError_t err = hipMemsetAsync(ws, 0, bytes, st);       // the zero-padding contract of the backward, on the caller's stream
+    bf16_t* doh = (bf16_t*)ws; bf16_t* v = doh + el;
+    float* lse = (float*)(v + el); float* delta = lse + bhs; float* nld = delta + bhs;
+    AttnParams a{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)vT, (bf16_t*)o_img, (bf16_t*)o_ctx, B, H, S, S_pad, n_img, 1, score_bound, lse};
+    if (err == hipSuccess) err = launch_attention(a, st);
+    AttnBwdPrepParams pp{(const bf16_t*)o_img, (const bf16_t*)o_ctx, (const bf16_t*)do_img, (const bf16_t*)do_ctx, lse, doh, delta, nld, B, H, S, S_pad,
+                         n_img};
+    if (err == hipSuccess) err = launch_attn_bwd_prep(pp, st);
+    const long hs = (long)S_pad * 64;
+    if (err == hipSuccess) err = launch_transpose((const bf16_t*)vT, S_pad, hs, v, 64, hs, 64, S_pad, 64, B * H, st);
+    AttnBwdParams ab{(const bf16_t*)q, (const bf16_t*)k, v, doh, lse, delta, nld, (bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv, B, H, S, S_pad};
+    if (err == hipSuccess) err = launch_attention_bwd(ab, st);
+    if (err == hipSuccess && lse_out) err = hipMemcpyAsync(lse_out, lse, bhs * 4, hipMemcpyDeviceToDevice, st);
+    if (err == hipSuccess && delta_out) err = hipMemcpyAsync(delta_out, delta, bhs * 4, hipMemcpyDeviceToDevice, st);
+    if (err == hipSuccess) err = hipStreamSynchronize(st);
+    (void)hipFree(ws);
+    if (err != hipSuccess) return errorf("mi355_op_attention_fwd_bwd_ex: %s", hipGetErrorString(err));
+    return 0;
+}

@@ -643,6 +643,39 @@ extern "C" int mi355_op_attention128(void* stream, const void* q, const void* k,
     return 0;
 }
 
+// mi355_op_attention128 with every field of Attn128Params the engines use (unit tests of the kernel edges): cross-attention (S_kv, S_kv_pad; 0 =
+// self), ragged keys (kv_len: device int32 [kv_len_n], kv_len_n = B; kv_len_n = 0 = not ragged), the data-dependent static / running-max split
+// (qmax2, kmax2: device uint32 [B*H], both or neither), the |score| bound as an argument and the optional log2-sum-exp [B][H][S_pad] fp32.
+static int attn128_ex_check(const char* who, int B, int H, int S, int S_pad, int n_first, int S_kv, int S_kv_pad, const void* kv_len, int kv_len_n,
+                            float score_bound) {
+    if (B <= 0 || H <= 0 || S <= 0 || S_pad < S || S_pad % 64) return errorf("%s: bad shape (S %d, S_pad %d)", who, S, S_pad);
+    if (n_first < 0 || n_first > S) return errorf("%s: n_first %d outside [0, S = %d]", who, n_first, S);
+    if (S_kv < 0 || (S_kv == 0 && S_kv_pad != 0)) return errorf("%s: bad S_kv %d / S_kv_pad %d", who, S_kv, S_kv_pad);
+    if (S_kv > 0 && (S_kv_pad < S_kv || S_kv_pad % 64)) return errorf("%s: S_kv_pad %d does not hold S_kv %d keys in 64-key tiles", who, S_kv_pad, S_kv);
+    if (kv_len_n != 0 && kv_len_n != B) return errorf("%s: kv_len_n %d is neither 0 nor B = %d", who, kv_len_n, B);
+    if ((kv_len_n != 0) != (kv_len != nullptr)) return errorf("%s: kv_len %s but kv_len_n = %d", who, kv_len ? "given" : "is NULL", kv_len_n);
+    if (!(score_bound >= 0.f)) return errorf("%s: negative score_bound", who);
+    return 0;
+}
+
+extern "C" int mi355_op_attention128_ex(void* stream, const void* q, const void* k, const void* vT, void* o_first, int64_t ld_first, int n_first,
+                                        void* o_rest, int64_t ld_rest, int B, int H, int S, int S_pad, int q_prescaled, int S_kv, int S_kv_pad,
+                                        const void* kv_len, int kv_len_n, const void* qmax2, const void* kmax2, float score_bound, float* lse) {
+    if (!q || !k || !vT) return errorf("mi355_op_attention128_ex: null argument");
+    if (attn128_ex_check("mi355_op_attention128_ex", B, H, S, S_pad, n_first, S_kv, S_kv_pad, kv_len, kv_len_n, score_bound)) return 1;
+    if (n_first > 0 && (!o_first || ld_first < (int64_t)H * 128)) return errorf("mi355_op_attention128_ex: o_first is NULL or ld_first < H * 128");
+    if (n_first < S && (!o_rest || ld_rest < (int64_t)H * 128)) return errorf("mi355_op_attention128_ex: o_rest is NULL or ld_rest < H * 128");
+    if ((qmax2 != nullptr) != (kmax2 != nullptr)) return errorf("mi355_op_attention128_ex: qmax2 and kmax2 go together");
+    Attn128Params a;
+    memset(&a, 0, sizeof(a));
+    a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.vT = (const bf16_t*)vT; a.o_first = (bf16_t*)o_first; a.ld_first = ld_first;
+    a.n_first = n_first; a.o_rest = (bf16_t*)o_rest; a.ld_rest = ld_rest; a.B = B; a.H = H; a.S = S; a.S_pad = S_pad;
+    a.q_prescaled = q_prescaled; a.score_bound = score_bound; a.S_kv = S_kv; a.S_kv_pad = S_kv_pad; a.kv_len = (const int*)kv_len;
+    a.qmax2 = (const unsigned*)qmax2; a.kmax2 = (const unsigned*)kmax2; a.lse = lse;
+    HIPCHK(launch_attention128(a, (hipStream_t)stream));
+    return 0;
+}
+
 extern "C" int mi355_op_rope_norm(void* stream, const void* src, int64_t src_ld, int q_col, int k_col, const float* nw_q,
                                   const float* nw_k, const float* cos_sin, void* q_out, void* k_out, int M, int H,
                                   int rows_per_sample, int s_off, int S_pad, float eps, float q_scale) {

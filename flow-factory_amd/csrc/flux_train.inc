@@ -559,6 +559,53 @@ extern "C" int mi355_op_attention128_fwd_bwd(void* stream, const void* q, const 
     return 0;
 }
 
+// The same with the fields the helper above pins exposed: cross-attention and ragged keys (as mi355_op_attention128_ex; k, vT, dk, dv are then
+// [B][H][S_kv_pad][128] / [B][H][128][S_kv_pad]), the first / rest split of o and dO with their row strides (Attn128BwdPrepParams; do_rest may be
+// NULL: that part of the output has no consumer), the |score| bound as an argument, and optional copies of the forward's log2-sum-exp and of the
+// backward's delta = rowsum(dO * O), both [B][H][S_pad] fp32 (rows >= S: zero, as the zeroed scratch holds them).
+extern "C" int mi355_op_attention128_fwd_bwd_ex(void* stream, const void* q, const void* k, const void* vT, const void* do_first, const void* do_rest,
+                                                void* o_first, void* o_rest, int64_t ld_first, int64_t ld_rest, int n_first, void* dq, void* dk, void* dv,
+                                                int B, int H, int S, int S_pad, int S_kv, int S_kv_pad, const void* kv_len, int kv_len_n,
+                                                float score_bound, float* lse_out, float* delta_out) {
+    const char* who = "mi355_op_attention128_fwd_bwd_ex";
+    if (!q || !k || !vT || !dq || !dk || !dv) return errorf("%s: null argument", who);
+    if (attn128_ex_check(who, B, H, S, S_pad, n_first, S_kv, S_kv_pad, kv_len, kv_len_n, score_bound)) return 1;
+    if (n_first > 0 && (!o_first || !do_first || ld_first < (int64_t)H * 128)) return errorf("%s: o_first / do_first is NULL or ld_first < H * 128", who);
+    if (n_first < S && (!o_rest || ld_rest < (int64_t)H * 128)) return errorf("%s: o_rest is NULL or ld_rest < H * 128", who);
+    hipStream_t st = (hipStream_t)stream;
+    const int Skp = S_kv > 0 ? S_kv_pad : S_pad;
+    const size_t el = (size_t)B * H * S_pad * 128, elk = (size_t)B * H * Skp * 128, bhs = (size_t)B * H * S_pad;
+    char* ws = nullptr;
+    const size_t bytes = (el + elk) * 2 + bhs * 4 * 4;
+    HIPCHK(hipMalloc((void**)&ws, bytes));
+    hipError_t err = hipMemsetAsync(ws, 0, bytes, st);       // zero padding of doh / v / lse / delta, on the caller's stream
+    bf16_t* doh = (bf16_t*)ws; bf16_t* v = doh + el;
+    float* lse = (float*)(v + elk); float* delta = lse + bhs; float* nld = delta + bhs;
+    Attn128Params a;
+    memset(&a, 0, sizeof(a));
+    a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.vT = (const bf16_t*)vT; a.o_first = (bf16_t*)o_first; a.ld_first = ld_first; a.n_first = n_first;
+    a.o_rest = (bf16_t*)o_rest; a.ld_rest = ld_rest; a.B = B; a.H = H; a.S = S; a.S_pad = S_pad; a.q_prescaled = 1; a.score_bound = score_bound;
+    a.S_kv = S_kv; a.S_kv_pad = S_kv_pad; a.kv_len = (const int*)kv_len; a.lse = lse;
+    if (err == hipSuccess) err = launch_attention128(a, st);
+    Attn128BwdPrepParams pp;
+    memset(&pp, 0, sizeof(pp));
+    pp.o_first = (const bf16_t*)o_first; pp.ld_o_first = ld_first; pp.o_rest = (const bf16_t*)o_rest; pp.ld_o_rest = ld_rest;
+    pp.do_first = (const bf16_t*)do_first; pp.ld_do_first = ld_first; pp.do_rest = (const bf16_t*)do_rest; pp.ld_do_rest = ld_rest; pp.n_first = n_first;
+    pp.lse = lse; pp.doh = doh; pp.delta = delta; pp.nld = nld; pp.B = B; pp.H = H; pp.S = S; pp.S_pad = S_pad;
+    if (err == hipSuccess) err = launch_attn128_bwd_prep(pp, st);
+    const long hs = (long)Skp * 128;
+    if (err == hipSuccess) err = launch_transpose((const bf16_t*)vT, Skp, hs, v, 128, hs, 128, Skp, 128, B * H, st);
+    AttnBwdParams ab{(const bf16_t*)q, (const bf16_t*)k, v, doh, lse, delta, nld, (bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv, B, H, S, S_pad};
+    ab.kv_len = (const int*)kv_len; ab.S_kv = S_kv; ab.S_kv_pad = S_kv_pad;
+    if (err == hipSuccess) err = launch_attention128_bwd(ab, st);
+    if (err == hipSuccess && lse_out) err = hipMemcpyAsync(lse_out, lse, bhs * 4, hipMemcpyDeviceToDevice, st);
+    if (err == hipSuccess && delta_out) err = hipMemcpyAsync(delta_out, delta, bhs * 4, hipMemcpyDeviceToDevice, st);
+    if (err == hipSuccess) err = hipStreamSynchronize(st);
+    (void)hipFree(ws);
+    if (err != hipSuccess) return errorf("%s: %s", who, hipGetErrorString(err));
+    return 0;
+}
+
 // q | k producer forward (mi355_op_rope_norm + the 1/rms side output) and its backward: dq / dk / dv [B][H][S_pad][128] (dq w.r.t. the stored,
 // scaled q) -> out [M][3 H 128] = [dq_pre | dk_pre | dv]; rstd [M][2H] fp32 scratch / output
 extern "C" int mi355_op_rope_norm_fwd_bwd(void* stream, const void* src, int64_t src_ld, int q_col, int k_col, const float* nw_q, const float* nw_k,

@@ -137,7 +137,10 @@ struct AttnParams {
     const bf16_t* q; const bf16_t* k; const bf16_t* vT;
     bf16_t* o_img; bf16_t* o_ctx;
     int B, H, S, S_pad, n_img;
-    int q_prescaled;   // 1: q already carries the softmax scale 0.125*log2(e) (folded into the q RMSNorm epilogue)
+    int q_prescaled;   // 1: q already carries the softmax scale 0.125*log2(e) (folded into the q RMSNorm epilogue).  CONTRACT: the plain kernel
+                       // (set_attn_variant(0), A/B only) multiplies the scores by that scale itself and does not read this field, so its callers
+                       // pass UNSCALED q: the engine sets q_prescaled = (variant >= 1) and folds the scale accordingly; the operator helpers that
+                       // take a pre-scaled q refuse variant 0
     float score_bound; // > 0: proven bound on |q.k| * scale * log2(e); <= 60 selects the no-running-max kernel (0 = unknown)
     float* lse;        // optional [B][H][S_pad] fp32: log2-sum-exp of the scaled scores per query (training-mode forward; nullptr = not written)
 };
@@ -368,6 +371,9 @@ struct AttnBwdParams {
     const int* kv_len;        // head_dim-128 kernels only: optional device [B], sample b attends to keys [0, kv_len[b]) (ragged text at the END of
                               // the joint sequence, like Attn128Params::kv_len); dk / dv of the masked keys are written as zeros
     int S_kv = 0, S_kv_pad = 0;   // head_dim-128 kernels only: cross-attention -- k, v, dk, dv are [B][H][S_kv_pad][128] over S_kv keys (0 = self)
+    // head_dim-64 dQ pass, set by launch_attention_bwd when S % 64 != 0 (attention_bwd.hip, "tail hazard"): 0 = every workgroup runs, 1 = only the
+    // blocks of `dq_rows` queries none of which has a log-sum-exp below -60, 2 = only the others
+    int dq_mode = 0, dq_rows = 0;
 };
 hipError_t launch_attention_bwd(const AttnBwdParams& p, hipStream_t stream);
 void set_attn_bwd_pipe(int v);

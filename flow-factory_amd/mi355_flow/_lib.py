@@ -103,6 +103,7 @@ SIGNATURES = {
     "mi355_denoise_step_train": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _F, _P, _I, _P, _P, _P, _I, _F, _I, _I, _P, _P, _P, _P, _P, _P]),
     "mi355_denoise_step_backward": (_I, [_P, _P, _P, _I, _F, _P, _I, _P, _P, _P, _I, _F, _I, _I, _P, _P, _P]),
     "mi355_op_attention_fwd_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I]),
+    "mi355_op_attention_fwd_bwd_ex": (_I, [_P] * 11 + [_I, _I, _I, _I, _I, _F, _P, _P]),
     "mi355_op_linear": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I]),
     "mi355_unipc_convert": (_I, [_P, _P, _P, _I, _F, _P, _I, _F, _P, _L]),
     "mi355_op_lincomb": (_I, [_P, _I, C.POINTER(_P), C.POINTER(_I), C.POINTER(_F), _P, _I, _L]),
@@ -113,6 +114,7 @@ SIGNATURES = {
     "mi355_op_wgrad": (_I, [_P, _P, C.c_int64, _P, C.c_int64, _P, _I, _I, _I, _I, _I, _P, _P]),
     "mi355_clock_probe": (_I, [_P, _P, _I, _I]),
     "mi355_op_attention": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I]),
+    "mi355_op_attention_ex": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P]),
     "mi355_op_ln_modulate": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _F]),
     "mi355_vae_create": (_I, [C.POINTER(VaeCfg), C.POINTER(_P)]),
     "mi355_vae_destroy": (_I, [_P]),
@@ -144,8 +146,10 @@ SIGNATURES = {
     "mi355_flux_forward_train": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P]),
     "mi355_flux_backward": (_I, [_P, _P, _P]),
     "mi355_op_attention128_fwd_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I]),
+    "mi355_op_attention128_fwd_bwd_ex": (_I, [_P] * 8 + [_L, _L, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _F, _P, _P]),
     "mi355_op_rope_norm_fwd_bwd": (_I, [_P, _P, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F]),
     "mi355_op_attention128": (_I, [_P, _P, _P, _P, _P, _L, _I, _P, _L, _I, _I, _I, _I, _I]),
+    "mi355_op_attention128_ex": (_I, [_P, _P, _P, _P, _P, _L, _I, _P, _L, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P, _F, _P]),
     "mi355_op_rope_norm": (_I, [_P, _P, _L, _I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F]),
     "mi355_op_norm_rope_full": (_I, [_P, _P, _L, _I, _P, _P, _P, _I, _I, _I, _I, _F, _F, _P]),
     "mi355_wan_create": (_I, [C.POINTER(WanCfg), C.POINTER(_P)]),

@@ -526,6 +526,37 @@ def op_attention(q: torch.Tensor, k: torch.Tensor, vT: torch.Tensor, S: int, n_i
     return o_img, o_ctx[: B * (S - n_img)]
 
 
+def op_attention_ex(q: torch.Tensor, k: torch.Tensor, vT: torch.Tensor, S: int, n_img: int, q_prescaled: bool = False, score_bound: float = 0.0,
+                    lse: Optional[torch.Tensor] = None, o_img: Optional[torch.Tensor] = None, o_ctx: Optional[torch.Tensor] = None):
+    """`op_attention` with q_prescaled, the |score| bound as an argument (0: running-max kernel, (0, 60]: static softmax) and the optional
+    log2-sum-exp output [B, H, S_pad] fp32.  o_img / o_ctx may be passed in (contiguous [rows, H*64]) and are returned."""
+    lib = _lib.load()
+    B, H, S_pad, hd = q.shape
+    assert hd == 64 and vT.shape == (B, H, 64, S_pad)
+    if o_img is None and n_img > 0:
+        o_img = torch.empty((B * n_img, H * 64), device=q.device, dtype=torch.bfloat16)
+    if o_ctx is None and n_img < S:
+        o_ctx = torch.empty((B * (S - n_img), H * 64), device=q.device, dtype=torch.bfloat16)
+    _lib.check(lib.mi355_op_attention_ex(_stream(), _ptr(q), _ptr(k), _ptr(vT), _ptr(o_img) if o_img is not None else None,
+                                         _ptr(o_ctx) if o_ctx is not None else None, B, H, S, S_pad, n_img, int(q_prescaled), float(score_bound),
+                                         _ptr(lse) if lse is not None else None), "op_attention_ex")
+    return o_img, o_ctx
+
+
+def op_attention_fwd_bwd_ex(q: torch.Tensor, k: torch.Tensor, vT: torch.Tensor, S: int, n_img: int, do_img: Optional[torch.Tensor],
+                            do_ctx: Optional[torch.Tensor], o_img: Optional[torch.Tensor], o_ctx: Optional[torch.Tensor], dq: torch.Tensor,
+                            dk: torch.Tensor, dv: torch.Tensor, score_bound: float = 0.0, lse: Optional[torch.Tensor] = None,
+                            delta: Optional[torch.Tensor] = None):
+    """Training-mode forward + backward, head_dim 64, on caller-provided tensors (q pre-scaled by log2(e)/8; padding rows of q, k and padding
+    columns of vT ZERO: the contract of the software-pipelined backward).  o / dO are split at n_img into image and context rows."""
+    lib = _lib.load()
+    B, H, S_pad, hd = q.shape
+    assert hd == 64 and vT.shape == (B, H, 64, S_pad)
+    o = lambda t: _ptr(t) if t is not None else None      # noqa: E731
+    _lib.check(lib.mi355_op_attention_fwd_bwd_ex(_stream(), _ptr(q), _ptr(k), _ptr(vT), o(do_img), o(do_ctx), o(o_img), o(o_ctx), _ptr(dq), _ptr(dk),
+                                                 _ptr(dv), B, H, S, S_pad, n_img, float(score_bound), o(lse), o(delta)), "op_attention_fwd_bwd_ex")
+
+
 def op_ln_modulate(x: torch.Tensor, shift: torch.Tensor, scale: torch.Tensor, rows_per_sample: int, eps: float = 1e-6):
     lib = _lib.load()
     M, D = x.shape

@@ -582,6 +582,51 @@ def op_attention128(q: torch.Tensor, k: torch.Tensor, vT: torch.Tensor, S: int, 
     return o1, o2
 
 
+def _opt(t):
+    return _ptr(t) if t is not None else None
+
+
+def op_attention128_ex(q: torch.Tensor, k: torch.Tensor, vT: torch.Tensor, S: int, n_first: Optional[int] = None, q_prescaled: bool = False,
+                       S_kv: int = 0, kv_len: Optional[torch.Tensor] = None, qmax2: Optional[torch.Tensor] = None,
+                       kmax2: Optional[torch.Tensor] = None, score_bound: float = 0.0, lse: Optional[torch.Tensor] = None,
+                       o_first: Optional[torch.Tensor] = None, o_rest: Optional[torch.Tensor] = None):
+    """`op_attention128` with every field the engines use.  q [B, H, S_pad, 128]; k [B, H, S_kv_pad, 128], vT [B, H, 128, S_kv_pad] when S_kv > 0
+    (cross-attention), else as q; kv_len int32 [B]; qmax2 / kmax2 uint32-as-int32 [B*H]; lse fp32 [B, H, S_pad] (written for rows < S).
+    o_first / o_rest may be passed in (2-D, any row stride >= H*128: the stride is taken from the tensor) and are returned."""
+    lib = _lib.load()
+    B, H, S_pad, _ = q.shape
+    n_first = S if n_first is None else n_first
+    D = H * 128
+    if o_first is None and n_first > 0:
+        o_first = torch.empty((B * n_first, D), device=q.device, dtype=torch.bfloat16)
+    if o_rest is None and n_first < S:
+        o_rest = torch.empty((B * (S - n_first), D), device=q.device, dtype=torch.bfloat16)
+    _lib.check(lib.mi355_op_attention128_ex(_stream(), _ptr(q), _ptr(k), _ptr(vT), _opt(o_first), o_first.stride(0) if o_first is not None else D, n_first,
+                                            _opt(o_rest), o_rest.stride(0) if o_rest is not None else D, B, H, S, S_pad, int(q_prescaled), S_kv,
+                                            k.shape[2] if S_kv > 0 else 0, _opt(kv_len), 0 if kv_len is None else int(kv_len.numel()), _opt(qmax2),
+                                            _opt(kmax2), float(score_bound), _opt(lse)), "op_attention128_ex")
+    return o_first, o_rest
+
+
+def op_attention128_fwd_bwd_ex(q: torch.Tensor, k: torch.Tensor, vT: torch.Tensor, S: int, do_first: Optional[torch.Tensor],
+                               do_rest: Optional[torch.Tensor], o_first: Optional[torch.Tensor], o_rest: Optional[torch.Tensor], n_first: int,
+                               dq: torch.Tensor, dk: torch.Tensor, dv: torch.Tensor, S_kv: int = 0, kv_len: Optional[torch.Tensor] = None,
+                               score_bound: float = 0.0, lse: Optional[torch.Tensor] = None, delta: Optional[torch.Tensor] = None):
+    """Training-mode forward + backward on caller-provided tensors (q pre-scaled by log2(e)/sqrt(128)).  o / dO are split at n_first like the
+    forward's output; o_first and do_first share a row stride, o_rest and do_rest another.  dq [B, H, S_pad, 128], dk / dv like k."""
+    lib = _lib.load()
+    B, H, S_pad, _ = q.shape
+    D = H * 128
+    ld1 = o_first.stride(0) if o_first is not None else D
+    ld2 = o_rest.stride(0) if o_rest is not None else D
+    assert do_first is None or do_first.stride(0) == ld1
+    assert do_rest is None or do_rest.stride(0) == ld2
+    _lib.check(lib.mi355_op_attention128_fwd_bwd_ex(_stream(), _ptr(q), _ptr(k), _ptr(vT), _opt(do_first), _opt(do_rest), _opt(o_first), _opt(o_rest), ld1,
+                                                    ld2, n_first, _ptr(dq), _ptr(dk), _ptr(dv), B, H, S, S_pad, S_kv, k.shape[2] if S_kv > 0 else 0,
+                                                    _opt(kv_len), 0 if kv_len is None else int(kv_len.numel()), float(score_bound), _opt(lse),
+                                                    _opt(delta)), "op_attention128_fwd_bwd_ex")
+
+
 def op_rope_norm(src: torch.Tensor, q_col: int, k_col: int, nw_q: torch.Tensor, nw_k: torch.Tensor, cos_sin: torch.Tensor, B: int, H: int,
                  rows_per_sample: int, s_off: int, S_pad: int, eps: float = 1e-6, q_scale: float = 1.0):
     """src [M, ld] bf16 (q at q_col, k at k_col); cos_sin [S, 64, 2] fp32 -> q, k [B, H, S_pad, 128] bf16 (zero elsewhere)."""

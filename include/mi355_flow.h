@@ -186,6 +186,13 @@ int mi355_op_lincomb(void* stream, int n_terms, const void* const* tensors, cons
  * zero-initialised and only written below S; a caller of this helper zero-fills its tensors. */
 int mi355_op_attention_fwd_bwd(void* stream, const void* q, const void* k, const void* vT, const void* d_o, void* o, void* dq, void* dk,
                                void* dv, int B, int H, int S, int S_pad);
+/* the same with the image / context split of o and d_o (query s < n_img of sample b at row b * n_img + s of o_img / do_img, the others in
+ * o_ctx / do_ctx; do_ctx may be NULL: zeros), the |score| bound as an argument (0 = none: running-max forward; (0, 60] = static softmax) and
+ * optional copies of the forward's log2-sum-exp and the backward's delta = rowsum(dO * O), [B][H][S_pad] fp32 each (rows >= S: zero).
+ * Bad shapes (S_pad < S, S_pad % 64, n_img outside [0, S], a NULL tensor the split needs) return an error before anything is launched. */
+int mi355_op_attention_fwd_bwd_ex(void* stream, const void* q, const void* k, const void* vT, const void* do_img, const void* do_ctx,
+                                  void* o_img, void* o_ctx, void* dq, void* dk, void* dv, int B, int H, int S, int S_pad, int n_img,
+                                  float score_bound, float* lse_out, float* delta_out);
 
 /* ---- operator-level entry points (unit tests, per-kernel profiling) ------------------------- */
 /* out[M][N] (bf16, ld = N) = A[M][K] . W[N][K]^T + bias[N] (fp32 bias); act: 0 none, 1 silu, 2 gelu-tanh */
@@ -218,6 +225,10 @@ int mi355_clock_probe(void* stream, void* out, int n, int sleep_iters);
 /* q,k : [B][H][S_pad][64] bf16, vT : [B][H][64][S_pad] bf16 -> o_img [B*n_img][H*64], o_ctx [B*(S-n_img)][H*64] */
 int mi355_op_attention(void* stream, const void* q, const void* k, const void* vT, void* o_img, void* o_ctx, int B,
                        int H, int S, int S_pad, int n_img);
+/* the same with q_prescaled (1: q carries log2(e)/8 already), the |score| bound as an argument (as above) and the optional log2-sum-exp
+ * output [B][H][S_pad] fp32 of the training-mode forward (NULL: not written) */
+int mi355_op_attention_ex(void* stream, const void* q, const void* k, const void* vT, void* o_img, void* o_ctx, int B, int H, int S,
+                          int S_pad, int n_img, int q_prescaled, float score_bound, float* lse);
 /* out = LayerNorm(x)*(1+scale[b]) + shift[b]; x,out [M][D] bf16; shift,scale [M/rows_per_sample][D] bf16 */
 int mi355_op_ln_modulate(void* stream, const void* x, const void* shift, const void* scale, void* out, int M, int D,
                          int rows_per_sample, float eps);
@@ -312,12 +323,28 @@ int mi355_flux_backward(mi355_flux_plan* plan, void* stream, const float* dv);
  * and backward: dq / dk / dv head-major -> out [M][3*H*128] = [dq_pre | dk_pre | dv] */
 int mi355_op_attention128_fwd_bwd(void* stream, const void* q, const void* k, const void* vT, const void* d_o, void* o, void* dq, void* dk,
                                   void* dv, int B, int H, int S, int S_pad);
+/* the same with cross-attention / ragged keys (as mi355_op_attention128_ex below; k, dk, dv are then [B][H][S_kv_pad][128]), the first / rest
+ * split of o and d_o with their row strides (do_rest may be NULL: zeros), the |score| bound as an argument, and optional copies of the
+ * forward's log2-sum-exp and the backward's delta, [B][H][S_pad] fp32 each.  dk / dv rows of keys at or beyond kv_len[b] are written as zeros. */
+int mi355_op_attention128_fwd_bwd_ex(void* stream, const void* q, const void* k, const void* vT, const void* do_first, const void* do_rest,
+                                     void* o_first, void* o_rest, int64_t ld_first, int64_t ld_rest, int n_first, void* dq, void* dk, void* dv,
+                                     int B, int H, int S, int S_pad, int S_kv, int S_kv_pad, const void* kv_len, int kv_len_n,
+                                     float score_bound, float* lse_out, float* delta_out);
 int mi355_op_rope_norm_fwd_bwd(void* stream, const void* src, int64_t src_ld, int q_col, int k_col, const float* nw_q, const float* nw_k,
                                const float* cos_sin, void* q_out, void* k_out, float* rstd, const void* dq, const void* dk, const void* dv,
                                void* out, int M, int H, int rows_per_sample, int s_off, int S_pad, float eps, float q_scale);
 /* head_dim-128 attention / RMSNorm+RoPE operators (unit tests) */
 int mi355_op_attention128(void* stream, const void* q, const void* k, const void* vT, void* o_first, int64_t ld_first,
                           int n_first, void* o_rest, int64_t ld_rest, int B, int H, int S, int S_pad, int q_prescaled);
+/* the same with every field the engines use: cross-attention (S_kv keys in k [B][H][S_kv_pad][128], vT [B][H][128][S_kv_pad]; 0, 0 = self),
+ * ragged keys (kv_len: device int32 [kv_len_n], kv_len_n = B, sample b attends to keys [0, max(1, kv_len[b])); kv_len_n = 0 and NULL = not
+ * ragged), the data-dependent static / running-max split (qmax2, kmax2: device uint32 [B*H], float bits of the largest squared row norms as
+ * mi355_op_norm_rope_full measures them; both or neither), the |score| bound as an argument (0 = none; (0, 60] = static softmax) and the
+ * optional log2-sum-exp output [B][H][S_pad] fp32.  S_kv_pad < S_kv, kv_len_n != 0 with kv_len == NULL (or the reverse), n_first outside
+ * [0, S] and a row stride below H * 128 return an error before anything is launched. */
+int mi355_op_attention128_ex(void* stream, const void* q, const void* k, const void* vT, void* o_first, int64_t ld_first, int n_first,
+                             void* o_rest, int64_t ld_rest, int B, int H, int S, int S_pad, int q_prescaled, int S_kv, int S_kv_pad,
+                             const void* kv_len, int kv_len_n, const void* qmax2, const void* kmax2, float score_bound, float* lse);
 int mi355_op_rope_norm(void* stream, const void* src, int64_t src_ld, int q_col, int k_col, const float* nw_q,
                        const float* nw_k, const float* cos_sin, void* q_out, void* k_out, int M, int H, int rows_per_sample,
                        int s_off, int S_pad, float eps, float q_scale);
