@@ -156,60 +156,56 @@ class WeightHolder:
         _lib.check(self._fn("weights_ready")(self._h), f"{self._ABI}_weights_ready")
 
 
-class Engine(WeightHolder):
-    """Owns the packed bf16 copy of the transformer weights (mi355_engine)."""
+class EngineBase(WeightHolder):
+    """Host half the four transformer engines share (SD3.5 `Engine`, `FluxEngine`, `QwenEngine`, `WanEngine`): the C handle, the plan
+    cache and the gradient-buffer registry, every symbol resolved as `mi355_{_ABI}_*`.  A family engine names its `_ABI` / `_WHAT` and its
+    plan class (`_PLAN`, set below that class) and adds what is really its own."""
 
-    def __init__(self, cfg: TransformerConfig):
+    _PLAN = None         # plan class: constructed as `_PLAN(engine, *shape, max_steps)`
+
+    def __init__(self, cfg):
         self.lib = _lib.load()
         self.cfg = cfg
         h = C.c_void_p()
         c = cfg.to_c()
-        _lib.check(self.lib.mi355_engine_create(C.byref(c), C.byref(h)), "engine_create")
+        _lib.check(self._fn("create")(C.byref(c), C.byref(h)), f"{self._ABI}_create")
         self._h = h
-        self._plans: Dict[tuple, "Plan"] = {}
-        self.train_scope = False
+        self._plans: Dict[tuple, "PlanBase"] = {}
+
+    def plan(self, *shape_and_max_steps: int):
+        """`plan(*shape, max_steps)`: the cached workspace for one shape (the positional arguments of the family's plan class), replaced by a
+        larger one when `max_steps` grew."""
+        *shape, max_steps = shape_and_max_steps
+        key = tuple(shape)
+        p = self._plans.get(key)
+        if p is None or p.max_steps < max_steps:
+            if p is not None:
+                p.close()
+            p = self._PLAN(self, *shape, max_steps)
+            self._plans[key] = p
+        return p
 
     # ---------------------------------------------------------------- weight gradients (mi355_flow/autograd.py)
     def grad_supported(self, name: str) -> int:
-        """0 = no gradient for this parameter, 1 = in the default scope (the blocks' linear layers), 2 = in the full scope only."""
-        return {0: 1, 2: 2}.get(self.lib.mi355_engine_grad_supported(self._h, name.encode()), 0)
-
-    def set_train_scope(self, full: bool) -> None:
-        _lib.check(self.lib.mi355_engine_set_train_scope(self._h, int(bool(full))), "set_train_scope")
-        self.train_scope = bool(full)
+        """1 = the native backward produces a gradient for this parameter (the linear layers inside the transformer blocks), 0 = it does not."""
+        return 1 if self._fn("grad_supported")(self._h, name.encode()) == 0 else 0
 
     def set_grad(self, name: str, grad: torch.Tensor) -> None:
         """Register the buffer the next backward writes d loss / d `name` into (same shape as the parameter): fp32, or bf16 for the weights /
         biases of the linear layers inside the blocks (`grad_supported(name) == 1`) -- the engine then rounds its fp32 sums to bf16 itself."""
         if grad.dtype not in (torch.float32, torch.bfloat16) or not grad.is_contiguous():
             raise ValueError("mi355_flow: gradient buffers are contiguous fp32 (or bf16) tensors")
-        _lib.check(self.lib.mi355_engine_set_grad_typed(self._h, name.encode(), _ptr(grad), dtype_code(grad.dtype)), f"set_grad({name})")
+        _lib.check(self._fn("set_grad_typed")(self._h, name.encode(), _ptr(grad), dtype_code(grad.dtype)), f"{self._PLAN._PRE}set_grad({name})")
 
     def clear_grads(self) -> None:
-        _lib.check(self.lib.mi355_engine_clear_grads(self._h), "clear_grads")
-
-    def attention_info(self) -> Dict[str, float]:
-        """{'static': launches of a forward on the static-bound softmax kernel, 'total': attention launches, 'max_bound': ...}"""
-        ns, nt, mb = C.c_int(), C.c_int(), C.c_float()
-        _lib.check(self.lib.mi355_engine_attention_info(self._h, _stream(), C.byref(ns), C.byref(nt), C.byref(mb)), "attention_info")
-        return {"static": ns.value, "total": nt.value, "max_bound": mb.value}
-
-    def plan(self, batch: int, n_cfg: int, latent_h: int, latent_w: int, n_text: int, max_steps: int) -> "Plan":
-        key = (batch, n_cfg, latent_h, latent_w, n_text)
-        p = self._plans.get(key)
-        if p is None or p.max_steps < max_steps:
-            if p is not None:
-                p.close()
-            p = Plan(self, batch, n_cfg, latent_h, latent_w, n_text, max_steps)
-            self._plans[key] = p
-        return p
+        _lib.check(self._fn("clear_grads")(self._h), f"{self._PLAN._PRE}clear_grads")
 
     def close(self) -> None:
         for p in self._plans.values():
             p.close()
         self._plans.clear()
         if self._h:
-            self.lib.mi355_engine_destroy(self._h)
+            self._fn("destroy")(self._h)
             self._h = None
 
     def __del__(self):
@@ -219,26 +215,79 @@ class Engine(WeightHolder):
             pass
 
 
-class Plan:
-    """Workspace for one (batch, n_cfg, latent_h, latent_w, n_text) shape (mi355_plan)."""
+class PlanBase:
+    """Host half the four plan classes share: the workspace handle for one shape, the training-stash serial number, `backward` and the
+    marshalling of the fused `rollout`.  `_PRE` is what follows `mi355_` in the plan's C symbols -- and is the label `_lib.check` reports."""
 
-    def __init__(self, engine: Engine, batch: int, n_cfg: int, latent_h: int, latent_w: int, n_text: int, max_steps: int):
-        self.engine, self.lib = engine, engine.lib
-        self.batch, self.n_cfg, self.h, self.w, self.n_text, self.max_steps = batch, n_cfg, latent_h, latent_w, n_text, max_steps
+    _PRE = ""
+
+    def __init__(self, engine: EngineBase, shape: Tuple[int, ...], max_steps: int):
+        self.engine, self.lib, self.max_steps = engine, engine.lib, max_steps
         self.C = engine.cfg.in_channels
+        self._train_serial = 0        # the plan owns ONE activation stash: every training forward takes a number, the backward checks it
         h = C.c_void_p()
-        _lib.check(self.lib.mi355_plan_create(engine._h, batch, n_cfg, latent_h, latent_w, n_text, max_steps, C.byref(h)),
-                   "plan_create")
+        self._call("plan_create", engine._h, *shape, max_steps, C.byref(h))
         self._h = h
+
+    def _call(self, suffix: str, *args) -> None:
+        _lib.check(getattr(self.lib, f"mi355_{self._PRE}{suffix}")(*args), f"{self._PRE}{suffix}")
 
     @property
     def workspace_bytes(self) -> int:
-        return int(self.lib.mi355_plan_workspace_bytes(self._h))
+        return int(getattr(self.lib, f"mi355_{self._PRE}plan_workspace_bytes")(self._h))
+
+    @property
+    def training_bytes(self) -> int:
+        return int(getattr(self.lib, f"mi355_{self._PRE}plan_training_bytes")(self._h))
 
     def close(self) -> None:
         if self._h:
-            self.lib.mi355_plan_destroy(self._h)
+            getattr(self.lib, f"mi355_{self._PRE}plan_destroy")(self._h)
             self._h = None
+
+    def backward(self, dv: torch.Tensor) -> None:
+        """mi355_*_backward: d loss / d v (fp32, `self.dv_shape`: the network output's) of the LAST `forward_train` -> the buffers registered
+        with the engine's `set_grad`.  (FLUX.1, Qwen-Image, Wan; SD3.5's plan differentiates its fused step: `denoise_step_backward`.)"""
+        dv = dv.to(torch.float32).contiguous()
+        assert tuple(dv.shape) == self.dv_shape, dv.shape
+        self._call("backward", self._h, _stream(), _ptr(dv))
+
+    def _rollout(self, shape: Tuple[int, ...], timesteps: Sequence[float], sigmas: Sequence[float], noise_levels: Sequence[float],
+                 dynamics: str, guidance: float, init_latents: torch.Tensor, storage_dtype: torch.dtype,
+                 step_noise: Optional[torch.Tensor], cond: tuple, keep_positions: Optional[Sequence[int]], compute_log_prob: bool):
+        """The whole N-step rollout in one C call.  `shape`: one latent state; `cond`: the family's conditioning arguments as the C
+        function takes them.  Returns (kept_latents [n_kept, *shape] storage dtype, log_probs [N, B] fp32 (nan where not computed),
+        final_latents [*shape])."""
+        N, B = len(timesteps), self.batch
+        assert len(sigmas) == N + 1 and len(noise_levels) == N
+        dev = init_latents.device
+        keep = list(range(N + 1)) if keep_positions is None else sorted(set(int(k) for k in keep_positions))
+        slots = [-1] * (N + 1)
+        for s, pos in enumerate(keep):
+            slots[pos] = s
+        out_lat = torch.empty((len(keep),) + shape, device=dev, dtype=storage_dtype)
+        out_lp = torch.full((N, B), float("nan"), device=dev, dtype=torch.float32)
+        out_fin = torch.empty(shape, device=dev, dtype=storage_dtype)
+        fa = C.c_float * N
+        ts_c, nl_c = fa(*[float(t) for t in timesteps]), fa(*[float(e) for e in noise_levels])
+        sg_c = (C.c_float * (N + 1))(*[float(s) for s in sigmas])
+        sl_c = (C.c_int32 * (N + 1))(*slots)
+        init_latents = init_latents.contiguous()
+        if step_noise is not None:
+            step_noise = step_noise.contiguous()
+            assert step_noise.dtype == torch.float32 and tuple(step_noise.shape) == (N,) + shape, step_noise.shape
+        self._call("rollout", self._h, _stream(), N, ts_c, sg_c, nl_c, DYNAMICS[dynamics], float(guidance), _ptr(init_latents),
+                   dtype_code(init_latents.dtype), dtype_code(storage_dtype), _ptr(step_noise), *cond, sl_c, _ptr(out_lat), _ptr(out_lp),
+                   _ptr(out_fin), int(bool(compute_log_prob)))
+        return out_lat, out_lp, out_fin
+
+
+class Plan(PlanBase):
+    """Workspace for one (batch, n_cfg, latent_h, latent_w, n_text) shape (mi355_plan)."""
+
+    def __init__(self, engine: Engine, batch: int, n_cfg: int, latent_h: int, latent_w: int, n_text: int, max_steps: int):
+        self.batch, self.n_cfg, self.h, self.w, self.n_text = batch, n_cfg, latent_h, latent_w, n_text
+        super().__init__(engine, (batch, n_cfg, latent_h, latent_w, n_text), max_steps)
 
     # ---------------------------------------------------------------- denoiser forward
     def transformer_forward(self, latents, timestep, enc_a, pooled_a, enc_b=None, pooled_b=None, t_round_dtype=None):
@@ -255,9 +304,8 @@ class Plan:
         enc_b = _bf16c(enc_b) if enc_b is not None else None
         pooled_b = _bf16c(pooled_b) if pooled_b is not None else None
         latents = latents.contiguous()
-        _lib.check(self.lib.mi355_transformer_forward(self._h, _stream(), _ptr(latents), dtype_code(latents.dtype), _ptr(t), rd,
-                                                      _ptr(enc_a), _ptr(pooled_a), _ptr(enc_b), _ptr(pooled_b), _ptr(out)),
-                   "transformer_forward")
+        self._call("transformer_forward", self._h, _stream(), _ptr(latents), dtype_code(latents.dtype), _ptr(t), rd, _ptr(enc_a), _ptr(pooled_a),
+                   _ptr(enc_b), _ptr(pooled_b), _ptr(out))
         return out
 
     # ---------------------------------------------------------------- one denoise step (forward + CFG + SDE step)
@@ -280,11 +328,11 @@ class Plan:
         pooled_b = _bf16c(pooled_b) if pooled_b is not None else None
         noise = noise.contiguous() if noise is not None else None
         nxt_in = next_latents.contiguous() if next_latents is not None else None
-        _lib.check(self.lib.mi355_denoise_step(
-            self._h, _stream(), _ptr(latents), dtype_code(latents.dtype), _ptr(t), _ptr(enc_a), _ptr(pooled_a),
-            _ptr(enc_b), _ptr(pooled_b), float(guidance), _ptr(noise), _ptr(nxt_in),
-            dtype_code(nxt_in.dtype) if nxt_in is not None else 0, _ptr(sig), _ptr(sig_n), _ptr(et), stride,
-            float(sigma_max), DYNAMICS[dynamics], int(bool(compute_log_prob)), *outs.ptrs()), "denoise_step")
+        self._call("denoise_step",
+                   self._h, _stream(), _ptr(latents), dtype_code(latents.dtype), _ptr(t), _ptr(enc_a), _ptr(pooled_a),
+                   _ptr(enc_b), _ptr(pooled_b), float(guidance), _ptr(noise), _ptr(nxt_in),
+                   dtype_code(nxt_in.dtype) if nxt_in is not None else 0, _ptr(sig), _ptr(sig_n), _ptr(et), stride,
+                   float(sigma_max), DYNAMICS[dynamics], int(bool(compute_log_prob)), *outs.ptrs())
         return outs
 
     # ---------------------------------------------------------------- differentiable replay step (optimize())
@@ -317,19 +365,19 @@ class Plan:
     def _train_forward(self, k: dict, outs) -> None:
         """One launch of mi355_denoise_step_train on prepared tensors.  The plan owns ONE activation stash (per-block buffers, modulation
         rows, LSE, ...), overwritten by every training forward: each forward takes a serial number that the matching backward checks."""
-        _lib.check(self.lib.mi355_denoise_step_train(
-            self._h, _stream(), _ptr(k["latents"]), dtype_code(k["latents"].dtype), _ptr(k["t"]), _ptr(k["enc_a"]), _ptr(k["pooled_a"]),
-            _ptr(k["enc_b"]), _ptr(k["pooled_b"]), k["guidance"], _ptr(k["nxt"]), dtype_code(k["nxt"].dtype), _ptr(k["sig"]), _ptr(k["sig_n"]),
-            _ptr(k["et"]), k["stride"], k["sigma_max"], k["dynamics"], k["clp"], None, _ptr(outs.next_latents_mean), _ptr(outs.noise_pred),
-            _ptr(outs.log_prob), _ptr(outs.std_dev_t), _ptr(outs.dt)), "denoise_step_train")
-        self._train_serial = getattr(self, "_train_serial", 0) + 1
+        self._call("denoise_step_train",
+                   self._h, _stream(), _ptr(k["latents"]), dtype_code(k["latents"].dtype), _ptr(k["t"]), _ptr(k["enc_a"]), _ptr(k["pooled_a"]),
+                   _ptr(k["enc_b"]), _ptr(k["pooled_b"]), k["guidance"], _ptr(k["nxt"]), dtype_code(k["nxt"].dtype), _ptr(k["sig"]), _ptr(k["sig_n"]),
+                   _ptr(k["et"]), k["stride"], k["sigma_max"], k["dynamics"], k["clp"], None, _ptr(outs.next_latents_mean), _ptr(outs.noise_pred),
+                   _ptr(outs.log_prob), _ptr(outs.std_dev_t), _ptr(outs.dt))
+        self._train_serial += 1
         k["serial"] = self._train_serial
 
     def denoise_step_backward(self, call: dict, g_log_prob, g_noise_pred, g_mean) -> None:
         """mi355_denoise_step_backward for the step recorded in `call['_keep']`; gradients go to the buffers registered with
         `Engine.set_grad`."""
         k = call["_keep"]
-        if k["serial"] != getattr(self, "_train_serial", 0):
+        if k["serial"] != self._train_serial:
             # another training forward ran on this plan since (DPO's chosen / rejected pair, trainers/dpo.py:587-588; any loss that sums
             # several grad forwards before one backward): the stash holds ITS activations.  Re-run this step's forward on the kept
             # inputs -- same kernels, same weights (the caller re-bound them), bit-identical stash -- then differentiate it.
@@ -338,14 +386,10 @@ class Plan:
             self._train_forward(k, _StepOutputs(self.batch, k["latents"], ("next_latents_mean", "noise_pred", "std_dev_t", "dt"), True))
         f32 = lambda g: None if g is None else g.to(torch.float32).contiguous()
         g_lp, g_np, g_mn = f32(g_log_prob), f32(g_noise_pred), f32(g_mean)
-        _lib.check(self.lib.mi355_denoise_step_backward(
-            self._h, _stream(), _ptr(k["latents"]), dtype_code(k["latents"].dtype), k["guidance"], _ptr(k["nxt"]), dtype_code(k["nxt"].dtype),
-            _ptr(k["sig"]), _ptr(k["sig_n"]), _ptr(k["et"]), k["stride"], k["sigma_max"], k["dynamics"], k["clp"], _ptr(g_lp), _ptr(g_np),
-            _ptr(g_mn)), "denoise_step_backward")
-
-    @property
-    def training_bytes(self) -> int:
-        return int(self.lib.mi355_plan_training_bytes(self._h))
+        self._call("denoise_step_backward",
+                   self._h, _stream(), _ptr(k["latents"]), dtype_code(k["latents"].dtype), k["guidance"], _ptr(k["nxt"]), dtype_code(k["nxt"].dtype),
+                   _ptr(k["sig"]), _ptr(k["sig_n"]), _ptr(k["et"]), k["stride"], k["sigma_max"], k["dynamics"], k["clp"], _ptr(g_lp), _ptr(g_np),
+                   _ptr(g_mn))
 
     # ---------------------------------------------------------------- whole rollout
     def rollout(self, timesteps: Sequence[float], sigmas: Sequence[float], noise_levels: Sequence[float], dynamics: str,
@@ -354,33 +398,35 @@ class Plan:
                 compute_log_prob: bool = True):
         """Returns (kept_latents [n_kept,B,C,h,w] storage dtype, log_probs [N,B] fp32 (nan where not
         computed), final_latents [B,C,h,w])."""
-        N, B = len(timesteps), self.batch
-        assert len(sigmas) == N + 1 and len(noise_levels) == N
-        dev = init_latents.device
-        keep = list(range(N + 1)) if keep_positions is None else sorted(set(int(k) for k in keep_positions))
-        slots = [-1] * (N + 1)
-        for s, pos in enumerate(keep):
-            slots[pos] = s
-        shape = (B, self.C, self.h, self.w)
-        out_lat = torch.empty((len(keep),) + shape, device=dev, dtype=storage_dtype)
-        out_lp = torch.full((N, B), float("nan"), device=dev, dtype=torch.float32)
-        out_fin = torch.empty(shape, device=dev, dtype=storage_dtype)
-        fa = C.c_float * N
-        ts_c, nl_c = fa(*[float(t) for t in timesteps]), fa(*[float(e) for e in noise_levels])
-        sg_c = (C.c_float * (N + 1))(*[float(s) for s in sigmas])
-        sl_c = (C.c_int32 * (N + 1))(*slots)
-        init_latents = init_latents.contiguous()
-        step_noise = step_noise.contiguous() if step_noise is not None else None
-        if step_noise is not None:
-            assert step_noise.dtype == torch.float32 and step_noise.shape == (N,) + shape, step_noise.shape
         pe, pp = _bf16c(prompt_embeds), _bf16c(pooled)
         ne = _bf16c(neg_embeds) if neg_embeds is not None else None
         npl = _bf16c(neg_pooled) if neg_pooled is not None else None
-        _lib.check(self.lib.mi355_rollout(
-            self._h, _stream(), N, ts_c, sg_c, nl_c, DYNAMICS[dynamics], float(guidance), _ptr(init_latents),
-            dtype_code(init_latents.dtype), dtype_code(storage_dtype), _ptr(step_noise), _ptr(pe), _ptr(pp), _ptr(ne),
-            _ptr(npl), sl_c, _ptr(out_lat), _ptr(out_lp), _ptr(out_fin), int(bool(compute_log_prob))), "rollout")
-        return out_lat, out_lp, out_fin
+        return self._rollout((self.batch, self.C, self.h, self.w), timesteps, sigmas, noise_levels, dynamics, guidance, init_latents,
+                             storage_dtype, step_noise, (_ptr(pe), _ptr(pp), _ptr(ne), _ptr(npl)), keep_positions, compute_log_prob)
+
+
+class Engine(EngineBase):
+    """Owns the packed bf16 copy of the transformer weights (mi355_engine).  `plan(batch, n_cfg, latent_h, latent_w, n_text, max_steps)`."""
+
+    _PLAN = Plan
+
+    def __init__(self, cfg: TransformerConfig):
+        super().__init__(cfg)
+        self.train_scope = False
+
+    def grad_supported(self, name: str) -> int:
+        """0 = no gradient for this parameter, 1 = in the default scope (the blocks' linear layers), 2 = in the full scope only."""
+        return {0: 1, 2: 2}.get(self.lib.mi355_engine_grad_supported(self._h, name.encode()), 0)
+
+    def set_train_scope(self, full: bool) -> None:
+        _lib.check(self.lib.mi355_engine_set_train_scope(self._h, int(bool(full))), "set_train_scope")
+        self.train_scope = bool(full)
+
+    def attention_info(self) -> Dict[str, float]:
+        """{'static': launches of a forward on the static-bound softmax kernel, 'total': attention launches, 'max_bound': ...}"""
+        ns, nt, mb = C.c_int(), C.c_int(), C.c_float()
+        _lib.check(self.lib.mi355_engine_attention_info(self._h, _stream(), C.byref(ns), C.byref(nt), C.byref(mb)), "attention_info")
+        return {"static": ns.value, "total": nt.value, "max_bound": mb.value}
 
 
 def _bf16c(t: torch.Tensor) -> torch.Tensor:

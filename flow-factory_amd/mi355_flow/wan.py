@@ -10,7 +10,6 @@ Not covered (raise): `attention_kwargs`; image-conditioned TI2V (per-token times
 """
 from __future__ import annotations
 
-import ctypes as C
 import os
 from dataclasses import dataclass
 from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple, Union
@@ -18,15 +17,13 @@ from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple, Union
 import numpy as np
 import torch
 
-from . import _lib
-from ._lib import DYNAMICS, WanCfg
-from .engine import WeightHolder, _bf16c, _ptr, _stream, dtype_code, sde_step
+from ._lib import WanCfg
+from .engine import EngineBase, PlanBase, _bf16c, _ptr, _stream, dtype_code, sde_step
+from .host import RolloutMixinBase, StandaloneAdapterBase
 from .samples import WanT2VSample
-from .scheduler import FlowMatchEulerDiscreteSDEScheduler, SDESchedulerOutput, host_noise_levels, randn_tensor
-from .trajectory import TrajectoryIndicesType, _resolve, collect_rollout
+from .scheduler import FlowMatchEulerDiscreteSDEScheduler, SDESchedulerOutput, randn_tensor
+from .trajectory import TrajectoryIndicesType
 
-_DTYPE_MAP = {"bf16": torch.bfloat16, "bfloat16": torch.bfloat16, "fp16": torch.float16, "float16": torch.float16,
-              "fp32": torch.float32, "float32": torch.float32}
 VAE_SCALE_SPATIAL, VAE_SCALE_TEMPORAL = 8, 4
 
 
@@ -76,159 +73,69 @@ class UniPCMultistepSDEScheduler(FlowMatchEulerDiscreteSDEScheduler):
         self._host_timesteps = [float(x) for x in ts.tolist()]
 
 
-class WanEngine(WeightHolder):
-    def __init__(self, cfg: WanConfig = WanConfig()):
-        self.lib = _lib.load()
-        self.cfg = cfg
-        h = C.c_void_p()
-        c = cfg.to_c()
-        _lib.check(self.lib.mi355_wan_create(C.byref(c), C.byref(h)), "wan_create")
-        self._h = h
-        self._plans: Dict[tuple, "WanPlan"] = {}
+class WanPlan(PlanBase):
+    _PRE = "wan_"
 
-    _ABI, _WHAT = "wan", "Wan transformer"
-
-    def plan(self, batch: int, n_cfg: int, T: int, h: int, w: int, n_text: int, max_steps: int) -> "WanPlan":
-        key = (batch, n_cfg, T, h, w, n_text)
-        p = self._plans.get(key)
-        if p is None or p.max_steps < max_steps:
-            if p is not None:
-                p.close()
-            p = WanPlan(self, batch, n_cfg, T, h, w, n_text, max_steps)
-            self._plans[key] = p
-        return p
-
-    # ---------------------------------------------------------------- weight gradients (mi355_flow/autograd.py: wan_replay)
-    #: the native backward (end of round 4; its seven GPU tests are green on MI355X: profiles/r04u_*, r04v_*).  MI355_WAN_NATIVE_BACKWARD=0 keeps
-    #: grad-mode forward() on the engine-valued replay (value = engine, gradient = the reference's torch path)
-    native_backward_enabled = os.environ.get("MI355_WAN_NATIVE_BACKWARD", "1") != "0"
-
-    def grad_supported(self, name: str) -> int:
-        """1 = the native backward produces a gradient for this parameter (the linear layers inside the transformer blocks), 0 = it does not."""
-        if not type(self).native_backward_enabled:
-            return 0
-        return 1 if self.lib.mi355_wan_grad_supported(self._h, name.encode()) == 0 else 0
-
-    def set_grad(self, name: str, grad: torch.Tensor) -> None:
-        if grad.dtype not in (torch.float32, torch.bfloat16) or not grad.is_contiguous():
-            raise ValueError("mi355_flow: gradient buffers are contiguous fp32 (or bf16) tensors")
-        _lib.check(self.lib.mi355_wan_set_grad_typed(self._h, name.encode(), _ptr(grad), dtype_code(grad.dtype)), f"wan_set_grad({name})")
-
-    def clear_grads(self) -> None:
-        _lib.check(self.lib.mi355_wan_clear_grads(self._h), "wan_clear_grads")
-
-    def close(self) -> None:
-        for p in self._plans.values():
-            p.close()
-        self._plans.clear()
-        if self._h:
-            self.lib.mi355_wan_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class WanPlan:
     def __init__(self, engine: WanEngine, batch: int, n_cfg: int, T: int, h: int, w: int, n_text: int, max_steps: int):
-        self.engine, self.lib = engine, engine.lib
-        self.batch, self.n_cfg, self.T, self.h, self.w, self.n_text, self.max_steps = batch, n_cfg, T, h, w, n_text, max_steps
-        self.C = engine.cfg.in_channels
-        hd = C.c_void_p()
-        _lib.check(self.lib.mi355_wan_plan_create(engine._h, batch, n_cfg, T, h, w, n_text, max_steps, C.byref(hd)), "wan_plan_create")
-        self._h = hd
+        self.batch, self.n_cfg, self.T, self.h, self.w, self.n_text = batch, n_cfg, T, h, w, n_text
+        super().__init__(engine, (batch, n_cfg, T, h, w, n_text), max_steps)
+        # d loss / d v arrives as [uncond | text], as `engine.sde_step_bwd` returns it
+        self.dv_shape = (batch * n_cfg, engine.cfg.out_channels, T, h, w)
 
-    @property
-    def workspace_bytes(self) -> int:
-        return int(self.lib.mi355_wan_plan_workspace_bytes(self._h))
-
-    def close(self) -> None:
-        if self._h:
-            self.lib.mi355_wan_plan_destroy(self._h)
-            self._h = None
-
-    def transformer_forward(self, latents: torch.Tensor, t: torch.Tensor, enc_a: torch.Tensor, enc_b: Optional[torch.Tensor] = None):
-        """latents (B, 16, T, h, w); t (B*n_cfg,) or scalar; n_cfg == 2: enc_a = negative, enc_b = positive, output (2B, ...)."""
+    def _forward(self, symbol: str, latents, t, enc_a, enc_b) -> torch.Tensor:
         B, Bp = self.batch, self.batch * self.n_cfg
         assert tuple(latents.shape) == (B, self.C, self.T, self.h, self.w), latents.shape
         dev = latents.device
         t = t.to(device=dev, dtype=torch.float32).reshape(-1)
         t = (t.expand(Bp) if t.numel() == 1 else (t.repeat(self.n_cfg) if t.numel() == B and self.n_cfg == 2 else t)).contiguous()
         assert t.numel() == Bp
-        out = torch.empty((Bp, self.engine.cfg.out_channels, self.T, self.h, self.w), device=dev, dtype=torch.bfloat16)
+        out = torch.empty(self.dv_shape, device=dev, dtype=torch.bfloat16)
         latents = latents.contiguous()
         ea = _bf16c(enc_a)
         eb = _bf16c(enc_b) if enc_b is not None else None
-        _lib.check(self.lib.mi355_wan_forward(self._h, _stream(), _ptr(latents), dtype_code(latents.dtype), _ptr(t), _ptr(ea), _ptr(eb),
-                                              _ptr(out)), "wan_forward")
+        self._call(symbol, self._h, _stream(), _ptr(latents), dtype_code(latents.dtype), _ptr(t), _ptr(ea), _ptr(eb), _ptr(out))
         return out
+
+    def transformer_forward(self, latents: torch.Tensor, t: torch.Tensor, enc_a: torch.Tensor, enc_b: Optional[torch.Tensor] = None):
+        """latents (B, 16, T, h, w); t (B*n_cfg,) or scalar; n_cfg == 2: enc_a = negative, enc_b = positive, output (2B, ...)."""
+        return self._forward("forward", latents, t, enc_a, enc_b)
 
     # ---------------------------------------------------------------- differentiable forward (optimize() replay)
     def forward_train(self, latents: torch.Tensor, t: torch.Tensor, enc_a: torch.Tensor, enc_b: Optional[torch.Tensor] = None) -> torch.Tensor:
         """mi355_wan_forward_train: `transformer_forward` on per-block activation buffers -- the same kernel binaries, so the prediction is
         bit-identical -- keeping what `backward` needs in the plan's training stash (ONE per plan; every call takes a serial number)."""
-        B, Bp = self.batch, self.batch * self.n_cfg
-        assert tuple(latents.shape) == (B, self.C, self.T, self.h, self.w), latents.shape
-        dev = latents.device
-        t = t.to(device=dev, dtype=torch.float32).reshape(-1)
-        t = (t.expand(Bp) if t.numel() == 1 else (t.repeat(self.n_cfg) if t.numel() == B and self.n_cfg == 2 else t)).contiguous()
-        assert t.numel() == Bp
-        out = torch.empty((Bp, self.engine.cfg.out_channels, self.T, self.h, self.w), device=dev, dtype=torch.bfloat16)
-        latents = latents.contiguous()
-        ea = _bf16c(enc_a)
-        eb = _bf16c(enc_b) if enc_b is not None else None
-        _lib.check(self.lib.mi355_wan_forward_train(self._h, _stream(), _ptr(latents), dtype_code(latents.dtype), _ptr(t), _ptr(ea), _ptr(eb),
-                                                    _ptr(out)), "wan_forward_train")
-        self._train_serial = getattr(self, "_train_serial", 0) + 1
+        out = self._forward("forward_train", latents, t, enc_a, enc_b)
+        self._train_serial += 1
         return out
-
-    def backward(self, dv: torch.Tensor) -> None:
-        """mi355_wan_backward: d loss / d v [n_cfg * B, C, T, h, w] fp32 ([uncond | text], as `engine.sde_step_bwd` returns it) of the LAST
-        `forward_train` -> the buffers registered with `WanEngine.set_grad`."""
-        dv = dv.to(torch.float32).contiguous()
-        assert tuple(dv.shape) == (self.batch * self.n_cfg, self.engine.cfg.out_channels, self.T, self.h, self.w), dv.shape
-        _lib.check(self.lib.mi355_wan_backward(self._h, _stream(), _ptr(dv)), "wan_backward")
-
-    @property
-    def training_bytes(self) -> int:
-        return int(self.lib.mi355_wan_plan_training_bytes(self._h))
 
     def rollout(self, timesteps: Sequence[float], sigmas: Sequence[float], noise_levels: Sequence[float], dynamics: str, guidance: float,
                 init_latents: torch.Tensor, storage_dtype: torch.dtype, step_noise: Optional[torch.Tensor], prompt_embeds: torch.Tensor,
                 neg_embeds: Optional[torch.Tensor] = None, keep_positions: Optional[Sequence[int]] = None, compute_log_prob: bool = True):
-        N, B = len(timesteps), self.batch
-        assert len(sigmas) == N + 1 and len(noise_levels) == N
-        dev = init_latents.device
-        keep = list(range(N + 1)) if keep_positions is None else sorted(set(int(k) for k in keep_positions))
-        slots = [-1] * (N + 1)
-        for s, pos in enumerate(keep):
-            slots[pos] = s
-        shape = (B, self.C, self.T, self.h, self.w)
+        shape = (self.batch, self.C, self.T, self.h, self.w)
         assert tuple(init_latents.shape) == shape, init_latents.shape
-        out_lat = torch.empty((len(keep),) + shape, device=dev, dtype=storage_dtype)
-        out_lp = torch.full((N, B), float("nan"), device=dev, dtype=torch.float32)
-        out_fin = torch.empty(shape, device=dev, dtype=storage_dtype)
-        fa = C.c_float * N
-        ts_c, nl_c = fa(*[float(t) for t in timesteps]), fa(*[float(e) for e in noise_levels])
-        sg_c = (C.c_float * (N + 1))(*[float(s) for s in sigmas])
-        sl_c = (C.c_int32 * (N + 1))(*slots)
-        init_latents = init_latents.contiguous()
-        if step_noise is not None:
-            step_noise = step_noise.contiguous()
-            assert step_noise.dtype == torch.float32 and tuple(step_noise.shape) == (N,) + shape, step_noise.shape
         pe = _bf16c(prompt_embeds)
         ne = _bf16c(neg_embeds) if neg_embeds is not None else None
-        _lib.check(self.lib.mi355_wan_rollout(
-            self._h, _stream(), N, ts_c, sg_c, nl_c, DYNAMICS[dynamics], float(guidance), _ptr(init_latents), dtype_code(init_latents.dtype),
-            dtype_code(storage_dtype), _ptr(step_noise), _ptr(pe), _ptr(ne), sl_c, _ptr(out_lat), _ptr(out_lp), _ptr(out_fin),
-            int(bool(compute_log_prob))), "wan_rollout")
-        return out_lat, out_lp, out_fin
+        return self._rollout(shape, timesteps, sigmas, noise_levels, dynamics, guidance, init_latents, storage_dtype, step_noise,
+                             (_ptr(pe), _ptr(ne)), keep_positions, compute_log_prob)
 
 
-class WanRolloutMixin:
+class WanEngine(EngineBase):
+    """Owns the packed bf16 copy of one Wan transformer (mi355_wan).  `plan(batch, n_cfg, T, h, w, n_text, max_steps)`."""
+
+    _ABI, _WHAT, _PLAN = "wan", "Wan transformer", WanPlan
+
+    #: the native backward (end of round 4; its seven GPU tests are green on MI355X: profiles/r04u_*, r04v_*).  MI355_WAN_NATIVE_BACKWARD=0 keeps
+    #: grad-mode forward() on the engine-valued replay (value = engine, gradient = the reference's torch path)
+    native_backward_enabled = os.environ.get("MI355_WAN_NATIVE_BACKWARD", "1") != "0"
+
+    def __init__(self, cfg: WanConfig = WanConfig()):
+        super().__init__(cfg)
+
+    def grad_supported(self, name: str) -> int:
+        return super().grad_supported(name) if type(self).native_backward_enabled else 0
+
+
+class WanRolloutMixin(RolloutMixinBase):
     """`inference()` / `forward()` of `Wan2_T2V_Adapter` (reference models/wan/wan2_t2v.py:234-421, :426-543) on the engine, for the
     single-transformer Wan2.1 configuration.  Host classes provide `engine` (WanEngine), `scheduler`, `device`, `transformer_dtype`,
     `latent_storage_dtype`, `encode_prompt`, `decode_latents(latents, output_type)`.
@@ -239,8 +146,8 @@ class WanRolloutMixin:
     algorithm -- oracle/unipc_ref.py, parity unpinned).  `MI355_WAN_EVAL_REFERENCE=1` routes evaluation to `_eval_inference` instead (the
     Flow-Factory plugin: the reference's own loop; standalone it raises) -- never a silent first-order Euler step."""
 
+    _FAMILY = "Wan"
     _sample_cls = WanT2VSample
-    _output_cls = SDESchedulerOutput
     # Wan2.2 two-expert pipelines (wan2_t2v.py:476-487): `engine` holds the high-noise expert (`pipeline.transformer`, used while
     # t >= boundary_ratio * num_train_timesteps with `guidance_scale`), `engine_2` the low-noise one (`pipeline.transformer_2`, with
     # `guidance_scale_2`).  None = single-transformer Wan2.1.  Per-token timesteps (`expand_timesteps`, TI2V-5B) are not supported.
@@ -262,20 +169,12 @@ class WanRolloutMixin:
             return self.engine, guidance_scale
         return self.engine_2, (guidance_scale_2 if guidance_scale_2 is not None else guidance_scale)
 
-    def _before_engine_call(self) -> None:
-        """Hook run at the top of inference() / forward(): the Flow-Factory plugin re-binds changed weights here."""
+    def _sde_step(self, *a, **k):
+        return sde_step(*a, **k)          # this module's name, looked up per call
 
     def _eval_inference(self, **kwargs):
         raise NotImplementedError("mi355_flow: evaluation-mode sampling for Wan uses diffusers' UniPC multistep solver in the reference "
                                   "(unipc_multistep.py:282-285); the native engine implements the rollout (SDE / Euler) branch only")
-
-    def cast_latents(self, latents: torch.Tensor, default_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
-        target = self.latent_storage_dtype or default_dtype
-        if target is None or latents.dtype == target:
-            return latents
-        if target == torch.float16:
-            latents = latents.clamp(-65504.0, 65504.0)
-        return latents.to(target)
 
     # ------------------------------------------------------------------ rollout (wan2_t2v.py:234-421)
     @torch.no_grad()
@@ -352,41 +251,21 @@ class WanRolloutMixin:
             step_noise = torch.empty((N, B, Cl, T, h, w), device=device, dtype=torch.float32)
             for i in range(N):
                 step_noise[i] = randn_tensor((B, Cl, T, h, w), generator=None, device=device, dtype=torch.float32)
-        ts_host = [float(t) for t in timesteps.tolist()]
-        sig_host = [float(s) for s in self.scheduler.sigmas.tolist()]
-        eta_host = host_noise_levels(self.scheduler, N)
         storage = self.latent_storage_dtype or torch.float32       # cast_latents(latents) with no default: fp32 stays fp32
-        # two experts: per-step engine calls (each step picks its expert and guidance by the boundary rule; still all-HIP)
-        stepwise = two or any(k != "noise_level" for k in extra_call_back_kwargs)
         plan = self.engine.plan(B, 2 if do_cfg else 1, T, h, w, prompt_embeds.shape[1], N)
         plan_2 = self.engine_2.plan(B, 2 if do_cfg else 1, T, h, w, prompt_embeds.shape[1], N) if two else None
-        kept = _resolve(trajectory_indices, N + 1)
-        keep_positions = list(range(N + 1)) if kept is None else sorted(kept)
-        step_outputs = None
+        sampler = None
         if eval_mode:
             if compute_log_prob or any(k != "noise_level" for k in extra_call_back_kwargs):
                 raise NotImplementedError("mi355_flow: evaluation-mode Wan sampling returns latents only (the reference's UniPC step yields neither "
                                           "a log-prob nor per-step callback tensors: unipc_multistep.py:282-285)")
-            lat_kept = self._rollout_eval(plan, ts_host, sig_host, guidance_scale, latents, storage, prompt_embeds,
-                                          negative_prompt_embeds if do_cfg else None, plan_2=plan_2, guidance_2=g2)
-            log_probs = torch.full((N, B), float("nan"), device=device)
-            final = lat_kept[N]
-            pos_to_slot = {p: p for p in range(N + 1)}
-        elif not stepwise:
-            lat_kept, log_probs, final = plan.rollout(ts_host, sig_host, eta_host, self.scheduler.dynamics_type, guidance_scale, latents,
-                                                      storage, step_noise, prompt_embeds, negative_prompt_embeds if do_cfg else None,
-                                                      keep_positions=keep_positions, compute_log_prob=compute_log_prob)
-            pos_to_slot = {p: s for s, p in enumerate(keep_positions)}
-        else:
-            lat_kept, log_probs, step_outputs = self._rollout_stepwise(plan, ts_host, sig_host, eta_host, guidance_scale, latents, storage,
-                                                                       step_noise, prompt_embeds, negative_prompt_embeds if do_cfg else None,
-                                                                       compute_log_prob, extra_call_back_kwargs, plan_2=plan_2,
-                                                                       guidance_2=g2)
-            final = lat_kept[N]
-            pos_to_slot = {p: p for p in range(N + 1)}
-        traj = collect_rollout(trajectory_indices, N, lambda pos: lat_kept[pos_to_slot[pos]], log_probs, eta_host, compute_log_prob,
-                               step_outputs, extra_call_back_kwargs,
-                               captured_noise_levels=host_noise_levels(self.scheduler, N, effective=False), dynamics=self.scheduler.dynamics_type)
+            sampler = self._rollout_eval_stepwise
+        elif two:
+            # two experts: per-step engine calls (each step picks its expert and guidance by the boundary rule; still all-HIP)
+            sampler = self._rollout_stepwise
+        traj, final = self._rollout_and_collect(plan, timesteps, N, guidance_scale, latents, storage, step_noise,
+                                                (prompt_embeds, negative_prompt_embeds if do_cfg else None), compute_log_prob,
+                                                extra_call_back_kwargs, trajectory_indices, sampler=sampler, plan_2=plan_2, guidance_2=g2)
         videos = self.decode_latents(final, output_type="pt")
         return [
             self._sample_cls(
@@ -403,6 +282,12 @@ class WanRolloutMixin:
             )
             for b in range(B)
         ]
+
+    def _rollout_eval_stepwise(self, plan, ts, sig, eta, guidance, latents, storage, step_noise, pe, ne, compute_log_prob, extra_keys,
+                               plan_2=None, guidance_2=None):
+        """`_rollout_eval` as a sampler of `_rollout_stepwise`'s signature: no log-probs, no per-step outputs."""
+        all_lat = self._rollout_eval(plan, ts, sig, guidance, latents, storage, pe, ne, plan_2=plan_2, guidance_2=guidance_2)
+        return all_lat, torch.full((len(ts), latents.shape[0]), float("nan"), device=latents.device), None
 
     def _rollout_eval(self, plan, ts, sig, guidance, latents, storage, pe, ne, plan_2=None, guidance_2=None):
         """Evaluation-mode sampling (reference: the loop of wan2_t2v.py:346-375 with `scheduler.step` in its `is_eval` branch,
@@ -440,35 +325,21 @@ class WanRolloutMixin:
     def _rollout_stepwise(self, plan, ts, sig, eta, guidance, latents, storage, step_noise, pe, ne, compute_log_prob, extra_keys, plan_2=None,
                           guidance_2=None):
         """Per-step engine calls (still all-HIP) for rollouts that ask for per-step callback tensors, and for two-expert pipelines."""
-        N, B = len(ts), latents.shape[0]
-        cur = self.cast_latents(latents, storage)
-        all_lat = [cur]
-        log_probs = torch.full((N, B), float("nan"), device=latents.device)
-        outs = []
-        want = tuple(k for k in extra_keys if k in ("next_latents", "next_latents_mean", "noise_pred", "std_dev_t", "dt"))
-        f32 = lambda v: torch.tensor(float(v), dtype=torch.float32)
-        for i in range(N):
-            t_next = ts[i + 1] if i + 1 < N else 0.0
-            clp = compute_log_prob and eta[i] > 0
+        B = latents.shape[0]
+
+        def predict(i, cur):
             bt = self._boundary_timestep()
             low = plan_2 is not None and bt is not None and ts[i] < bt
             pl, gd = (plan_2, guidance_2) if low else (plan, guidance)
             cfg_i = ne is not None and gd > 1.0          # the reference decides CFG per expert (wan2_t2v.py:489-498)
             if not cfg_i and pl.n_cfg == 2:
                 pl = pl.engine.plan(B, 1, pl.T, pl.h, pl.w, pl.n_text, 1)
-            v = pl.transformer_forward(cur, f32(ts[i]).reshape(1), ne if cfg_i else pe, pe if cfg_i else None)
-            vu, vt = (v[:B], v[B:]) if cfg_i else (None, v)
-            o = sde_step(vt, vu, gd, cur, f32(ts[i]) / f32(1000.0), f32(t_next) / f32(1000.0), eta[i], sig[1],
-                         self.scheduler.dynamics_type, noise=step_noise[i] if step_noise is not None else None, compute_log_prob=clp,
-                         want=want)
-            if clp:
-                log_probs[i] = o.log_prob
-            cur = o.next_storage
-            all_lat.append(cur)
-            outs.append(o)
-        return all_lat, log_probs, outs
+            v = pl.transformer_forward(cur, torch.tensor(float(ts[i]), dtype=torch.float32).reshape(1), ne if cfg_i else pe, pe if cfg_i else None)
+            return (v[B:], v[:B], gd) if cfg_i else (v, None, gd)
 
-    # ------------------------------------------------------------------ single step / replay (wan2_t2v.py:426-543), no-grad
+        return self._stepwise(ts, sig, eta, latents, storage, step_noise, compute_log_prob, extra_keys, predict)
+
+    # ------------------------------------------------------------------ single step / replay (wan2_t2v.py:426-543)
     def forward(
         self,
         t: torch.Tensor,
@@ -488,32 +359,13 @@ class WanRolloutMixin:
         kw = dict(t=t, latents=latents, prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds, guidance_scale=guidance_scale,
                   guidance_scale_2=guidance_scale_2, t_next=t_next, next_latents=next_latents, noise_level=noise_level,
                   attention_kwargs=attention_kwargs, compute_log_prob=compute_log_prob, return_kwargs=return_kwargs, boundary_timestep=boundary_timestep)
-        if torch.is_grad_enabled() and getattr(self, "_live_weights", None) is not None and WanEngine.native_backward_enabled:
-            # optimize() (trainers/grpo.py:263): the replay WITH autograd on the engine's differentiable forward + native backward
-            # (mi355_flow.autograd.wan_replay) when its backward covers the trainable set of the transformer THIS step runs on (Wan2.2: the
-            # expert the timestep selects, wan2_t2v.py:476-487).  MI355_WAN_NATIVE_BACKWARD=0 opts out.
-            from . import autograd as AG
-            self._before_engine_call()
-            t0 = float(torch.as_tensor(t, dtype=torch.float32).reshape(-1)[0])
-            host = self._replay_host(self._expert(t0, guidance_scale, guidance_scale_2, boundary_timestep)[0])
-            why = AG.unsupported_reason(host)
-            sampled = next_latents is None and ("next_latents" in return_kwargs or (compute_log_prob and "log_prob" in return_kwargs))
-            if why is None and sampled:
-                why = "a sampled next state (or its log-prob) was requested with autograd"
-            if why is None:
-                return self._forward_impl(grad=True, host=host, **kw)
-            if not why.startswith("the bound module has no trainable"):
-                return self._grad_fallback(why, kw)
-        return self._forward_nograd(**kw)
-
-    def _forward_nograd(self, **kw) -> SDESchedulerOutput:
-        with torch.no_grad():
-            return self._forward_impl(grad=False, **kw)
-
-    def _grad_fallback(self, why: str, kwargs: Dict[str, Any]):
-        """Grad-mode forward() the native backward cannot serve.  Standalone: there is no other implementation -- raise (the Flow-Factory
-        plugin overrides this with the reference's autograd path)."""
-        raise NotImplementedError(f"mi355_flow: Wan forward() with autograd is not available natively: {why}")
+        if not WanEngine.native_backward_enabled:          # MI355_WAN_NATIVE_BACKWARD=0 opts out of the native backward
+            return self._forward_nograd(**kw)
+        # optimize() (trainers/grpo.py:263): the replay WITH autograd runs on the engine's differentiable forward + native backward
+        # (mi355_flow.autograd.wan_replay) when its backward covers the trainable set of the transformer THIS step runs on (Wan2.2: the
+        # expert the timestep selects, wan2_t2v.py:476-487)
+        return self._forward_dispatch(kw, replay_host=lambda: self._replay_host(self._expert(
+            float(torch.as_tensor(t, dtype=torch.float32).reshape(-1)[0]), guidance_scale, guidance_scale_2, boundary_timestep)[0]))
 
     def _replay_host(self, eng):
         """What `mi355_flow.autograd` differentiates against for a step on `eng`: this adapter (single transformer / the high-noise expert), or
@@ -535,54 +387,26 @@ class WanRolloutMixin:
         B, _, T, h, w = latents.shape
         t = torch.as_tensor(t, device=dev, dtype=torch.float32).reshape(-1)
         t0 = t[0]                                       # `t = t[0] if t.ndim == 1 else t`: one scalar timestep per call
-        sched = self.scheduler
-        if t_next is None:
-            idx = sched.index_for_timestep(t0)
-            t_next = sched.timesteps[idx + 1].float() if idx + 1 < len(sched.timesteps) else torch.zeros(())
-        t_next = torch.as_tensor(t_next, device=dev, dtype=torch.float32).reshape(-1)[0]
+        if t_next is not None:
+            t_next = torch.as_tensor(t_next, device=dev, dtype=torch.float32).reshape(-1)[0]
         eng, guidance_scale = self._expert(float(t0), guidance_scale, guidance_scale_2, boundary_timestep)
         do_cfg = negative_prompt_embeds is not None and guidance_scale > 1.0
         plan = eng.plan(B, 2 if do_cfg else 1, T, h, w, prompt_embeds.shape[1], 1)
         enc_a, enc_b = (negative_prompt_embeds, prompt_embeds) if do_cfg else (prompt_embeds, None)
-        if not grad:
-            v = plan.transformer_forward(latents, t0.reshape(1), enc_a, enc_b)
-            vu, vt = (v[:B], v[B:]) if do_cfg else (None, v)
-        dyn = sched.dynamics_type
-        sigma, sigma_next = (t0.double() / 1000).float(), (t_next.double() / 1000).float()
-        if sched.is_eval or dyn == "ODE":
-            noise_level = 0.0
-        elif noise_level is None:
-            noise_level = sched.get_noise_level_for_timestep(float(t0))
-        noise = None
-        if next_latents is None and dyn != "ODE":
-            noise = randn_tensor(latents.shape, device=dev, dtype=torch.float32)
-        view = (-1, 1, 1, 1, 1)
+        sched = self.scheduler
+        if noise_level is None and not (sched.is_eval or sched.dynamics_type == "ODE"):
+            noise_level = sched.get_noise_level_for_timestep(float(t0))          # Wan's schedulers look the level up by timestep
         if grad:
-            from . import autograd as AG
-            replay = next_latents is not None
-            clp = bool(compute_log_prob) and replay
-            call = dict(latents=latents, train_args=(latents, t0.reshape(1), enc_a, enc_b), cfg_guidance=float(guidance_scale) if do_cfg else None,
-                        sigma=sigma, sigma_next=sigma_next, eta=noise_level, sigma_max=float(sched.sigmas[1]), dynamics=dyn,
-                        next_latents=next_latents if replay else latents, compute_log_prob=clp)
-            lp, npred, mean, std, dtt = AG.wan_replay(host if host is not None else self, plan, call)
-            res = dict(noise_pred=npred, next_latents=next_latents.float() if replay else None, next_latents_mean=mean, std_dev_t=std.view(view),
-                       dt=dtt.view(view), log_prob=lp if clp else None)
-            return self._output_cls.from_dict({k: res[k] for k in return_kwargs if k in res})
-        want = tuple(k for k in return_kwargs if k in ("next_latents", "next_latents_mean", "noise_pred", "std_dev_t", "dt"))
-        o = sde_step(vt, vu, guidance_scale, latents, sigma, sigma_next, noise_level, float(sched.sigmas[1]), dyn, noise=noise,
-                     next_latents=next_latents, compute_log_prob=compute_log_prob, want=want)
-        res = dict(
-            noise_pred=o.noise_pred,
-            next_latents=o.next_latents if next_latents is None else next_latents.float(),
-            next_latents_mean=o.next_latents_mean,
-            std_dev_t=o.std_dev_t.view(view) if o.std_dev_t is not None else None,
-            dt=o.dt.view(view) if o.dt is not None else None,
-            log_prob=o.log_prob if compute_log_prob else None,
-        )
-        return self._output_cls.from_dict({k: res[k] for k in return_kwargs if k in res})
+            from .autograd import wan_replay
+            return self._scheduler_step(t0, latents, t_next, next_latents, noise_level, compute_log_prob, return_kwargs, replay=(
+                wan_replay, host if host is not None else self, plan,
+                dict(train_args=(latents, t0.reshape(1), enc_a, enc_b), cfg_guidance=float(guidance_scale) if do_cfg else None)))
+        v = plan.transformer_forward(latents, t0.reshape(1), enc_a, enc_b)
+        return self._scheduler_step(t0, latents, t_next, next_latents, noise_level, compute_log_prob, return_kwargs,
+                                    v=(v[B:], v[:B], guidance_scale) if do_cfg else (v, None, guidance_scale))
 
 
-class Wan2T2VNativeAdapter(WanRolloutMixin):
+class Wan2T2VNativeAdapter(StandaloneAdapterBase, WanRolloutMixin):
     """Standalone Wan2.1 T2V adapter (no Flow-Factory import): engine + UniPC-SDE scheduler (+ optional video decoder callable)."""
 
     def __init__(self, state_dict: Dict[str, torch.Tensor], config: Optional[WanConfig] = None,
@@ -591,23 +415,11 @@ class Wan2T2VNativeAdapter(WanRolloutMixin):
                  video_decode: Optional[Callable[[torch.Tensor], torch.Tensor]] = None,
                  state_dict_2: Optional[Dict[str, torch.Tensor]] = None, boundary_ratio: Optional[float] = None,
                  vae_state_dict: Optional[Dict[str, torch.Tensor]] = None, vae_config=None, vae_max_batch: int = 1):
-        if not torch.cuda.is_available():
-            raise RuntimeError("mi355_flow: no GPU visible; the native rollout engine has no CPU path")
-        self.device = torch.device(device)
-        self.transformer_dtype = transformer_dtype
-        self._latent_storage = latent_storage_dtype
-        self.scheduler = scheduler or UniPCMultistepSDEScheduler(flow_shift=3.0, sde_steps=[1, 2, 3], num_sde_steps=1)
-        self.engine = WanEngine(config or WanConfig())
-        self._live_weights = None
-        if isinstance(state_dict, torch.nn.Module):
-            # a torch module with HF parameter names (possibly DDP / peft wrapped): its CURRENT parameters are re-bound before every engine
-            # call, and grad-mode forward() differentiates w.r.t. its trainable parameters (mi355_flow/autograd.py: wan_replay)
-            from .binding import LiveWeights
-            module = state_dict
-            self._live_weights = LiveWeights(self.engine, lambda: module)
-            self._sync_weights()
-        else:
-            self.refresh_weights(state_dict)
+        from .vae import WanVAEConfig, WanVAEDecoder
+        self._init_engine(WanEngine, config or WanConfig(),
+                          scheduler or UniPCMultistepSDEScheduler(flow_shift=3.0, sde_steps=[1, 2, 3], num_sde_steps=1),
+                          latent_storage_dtype, transformer_dtype, device)
+        self._bind(state_dict)
         if state_dict_2 is not None:            # Wan2.2: low-noise expert (`transformer_2`), same architecture
             if boundary_ratio is None:
                 raise ValueError("mi355_flow: a two-expert Wan2.2 adapter needs `boundary_ratio` (pipeline.config.boundary_ratio)")
@@ -616,41 +428,7 @@ class Wan2T2VNativeAdapter(WanRolloutMixin):
             self.engine_2.ready()
             self.boundary_ratio = float(boundary_ratio)
         self._video_decode = video_decode
-        self.vae_decoder = None
-        self.vae_max_batch = vae_max_batch
-        if vae_state_dict is not None:
-            from .vae import WanVAEConfig, WanVAEDecoder
-            self.vae_decoder = WanVAEDecoder(vae_config or WanVAEConfig())
-            self.vae_decoder.bind_state_dict(vae_state_dict)
-            self.vae_decoder.ready()
-
-    @property
-    def latent_storage_dtype(self) -> Optional[torch.dtype]:
-        return _DTYPE_MAP.get(self._latent_storage) if self._latent_storage else None
-
-    def refresh_weights(self, state_dict: Dict[str, torch.Tensor]) -> None:
-        self.engine.bind_state_dict(state_dict)
-        self.engine.ready()
-
-    def _sync_weights(self) -> int:
-        if self._live_weights is None:
-            return 0
-        n = self._live_weights.sync()
-        if n:
-            self.engine.ready()
-        return n
-
-    def _before_engine_call(self) -> None:
-        self._sync_weights()
-
-    def rollout(self):
-        self.scheduler.rollout()
-
-    def eval(self):
-        self.scheduler.eval()
-
-    def train(self, mode: bool = True):
-        self.scheduler.train(mode)
+        self._init_vae(WanVAEDecoder, vae_config or WanVAEConfig(), vae_state_dict, vae_max_batch)
 
     def encode_prompt(self, *a, **k):
         raise RuntimeError("mi355_flow standalone adapter has no text encoder: pass prompt_embeds (and negative_prompt_embeds for CFG)")
