@@ -11,13 +11,19 @@ tokens), RNG draws + collectors + sample building included, VAE decode / rewards
 Synthetic prompts (random prompt embeddings) and random-init weights of the SD3.5-medium
 architecture: no checkpoints / datasets exist in this environment.
 
+A plain run does what the headline figure needs and nothing else: set-up, the warm-up steps, the timed steps, `--dump-outputs`, the line.
 Rank 0 prints ONE JSON line; besides the contract keys it carries
   roofline     : the dominant kernel (attention, v_mfma_f32_32x32x16_bf16) -- algorithmic FLOPs per
                  launch / mean launch duration from hipEvents recorded on the launch stream over the
                  timed region, vs the 2.5 PFLOP/s dense bf16 MFMA peak; plus the whole-forward figure
                  the north star asks for (`forward.frac`, target 0.40) and a per-class breakdown.
-  cpu_baseline : the oracle (fp32 PyTorch restatement of the reference path) timed on this box's
-                 host cores on a bounded sample; a reported baseline, not the optimisation target.
+
+`--full` adds everything else this file measures or checks (each leg keeps its own `--no-...` switch): the kernel-variant cross-check of
+one rollout before the timed steps and, after them, the roofline figures that take rollouts of their own (`attention_dynamic`,
+`guaranteed_floor`, `gemm`, `delivered_clock_mhz`), `power`, `graph_vs_eager`, `small_batch`, `vae_decode`, the `optimize_step*` and
+`families` subprocess legs, `optimize_step_ddp` (N > 1) and
+  cpu_baseline : the oracle (fp32 PyTorch restatement of the reference path) timed on the host
+                 cores on a bounded sample; a reported baseline, not the optimisation target.
 
 `--dump-outputs DIR` writes the samples of the last timed step as DIR/<field>.npy (`dump_outputs`), for comparing two builds on the same inputs.
 """
@@ -101,6 +107,16 @@ def cpu_baseline(budget_s=150.0):
     return dict(value=round(1.0 / est, 5), unit="denoise-steps/sec", cores=cores, kind="port", measured=False,
                 sample=f"1 fp32 oracle forward at 256^2 ({t256:.2f} s measured) EXTRAPOLATED x5.5 (measured time ratio 4.3-4.8) to 1024^2 "
                        f"(estimate {est:.0f} s > budget {budget_s:.0f} s)")
+
+
+def skip_rollout_draws(adapter, batch, size, n_steps, device):
+    """Advance the device's global generator by what one `inference()` call draws from it, without running the rollout: the initial
+    latents in the transformer dtype, then one fp32 tensor per denoise step (none under ODE dynamics) -- `NativeRolloutMixin.inference`."""
+    shape = (batch, adapter.engine.cfg.in_channels, size // 8, size // 8)
+    torch.randn(shape, device=device, dtype=adapter.transformer_dtype)
+    if adapter.scheduler.dynamics_type != "ODE":
+        for _ in range(n_steps):
+            torch.randn(shape, device=device, dtype=torch.float32)
 
 
 DUMP_BUDGET_BYTES = 64 * 10**6   # `--dump-outputs` writes at most this much in all
@@ -220,7 +236,7 @@ def dry_run(args, world, rank):
         per_rank = [float(x.item()) for x in allt]
         elapsed = max(per_rank)
     ddp_leg = None
-    if world > 1 and not args.no_ddp_step:
+    if args.full and world > 1 and not args.no_ddp_step:
         # the assembly of the `optimize_step_ddp` leg (wrapper, sync / no_sync timing, MAX over ranks, byte count) on gloo with a stand-in
         # module -- what the real path runs around the engine's autograd node
         from torch.nn.parallel import DistributedDataParallel as DDP
@@ -256,6 +272,11 @@ def main():
     ap.add_argument("--guidance", type=float, default=1.0, help="> 1 enables CFG (2 forwards per denoise step)")
     ap.add_argument("--size", type=int, default=1024)
     ap.add_argument("--denoise-steps", type=int, default=28)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure, run everything else this file measures or checks (all untimed w.r.t. `value`): the "
+                         "kernel-variant cross-check, the roofline figures that take rollouts of their own, power, graph vs eager, small batches, "
+                         "VAE decode, the optimize() steps, the other families, the DDP step (--gpus > 1) and the CPU baseline; the --no-... "
+                         "switches below take single legs out again")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-selfcheck", action="store_true", help="skip the untimed kernel-variant cross-check of one rollout")
     ap.add_argument("--no-kernel-timing", action="store_true")
@@ -377,7 +398,12 @@ def main():
     # (MI355_TUNE="key=value,..." -- A/B of kernel / launch variants -- is applied by _lib.load() itself)
     for _ in range(args.warmup):
         samples = one_rollout()
-    if not args.no_selfcheck and not flux_mode:
+    if not args.full and not args.no_selfcheck and not flux_mode:
+        # a plain run leaves the cross-check below out, but not what it does to the inputs of the timed steps: they have always drawn their
+        # noise from where the check's seeded rollout leaves the global generator, and go on doing so (same samples, same `--dump-outputs`)
+        torch.cuda.manual_seed(1234 + rank)
+        skip_rollout_draws(adapter, B, args.size, N, dev)
+    if args.full and not args.no_selfcheck and not flux_mode:
         # untimed sanity net: the same seeded rollout through the first-correct-path kernels (simple GEMM schedule,
         # plain online softmax, eager launches) must reproduce the shipped kernels' trajectory
         def seeded():
@@ -485,7 +511,7 @@ def main():
                         "flops_per_forward_per_sample": F, "note": "wall-clock of the whole rollout incl. host glue; north-star target 0.40"},
             "by_class": by_class,
         }
-    if timing and rank == 0 and world == 1:
+    if args.full and timing and rank == 0 and world == 1:
         # (a) the running-max ("dynamic") attention kernel on the same rollout: what a checkpoint whose q/k norm weights do not
         #     prove the static bound would run;  (b) graph-replay vs eager wall clock of one rollout (the timed region above runs
         #     eagerly because the event brackets cannot live inside a captured graph)
@@ -587,7 +613,7 @@ def main():
         out["graph_vs_eager"] = {"graph_ms_per_rollout": round(g_s * 1e3, 2), "eager_ms_per_rollout": round(e_s * 1e3, 2),
                                  "graph_denoise_steps_per_s": round(B * N / g_s, 3), "eager_denoise_steps_per_s": round(B * N / e_s, 3),
                                  "note": "untimed w.r.t. `value`; one hipGraph launch replays the whole N-step loop (~7 850 kernels)"}
-    if rank == 0 and world == 1 and not flux_mode and not args.no_small_batch:
+    if args.full and rank == 0 and world == 1 and not flux_mode and not args.no_small_batch:
         # Small-batch configurations of the same engine (hipGraph replay; the text-stream chain of every block on a second stream): the
         # reference's own example shape (examples/grpo/full/sd3_5: 512^2, N = 10, B = 2 with CFG) and B = 2 at the bench resolution.
         # Reported beside the metric, never inside `value`; a failure here is recorded, not raised.
@@ -628,7 +654,7 @@ def main():
         out["roofline"] = {"bound": "mfma", "kernel": "whole FLUX.1 forward (MFMA GEMMs + head_dim-128 attention), wall-clock of the rollout",
                            "achieved": round(fwd_tflops, 1), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": round(fwd_tflops / PEAK_BF16_TFLOPS, 4),
                            "traffic": None, "flops_per_forward_per_sample": F}
-    if rank == 0 and not args.no_vae:
+    if args.full and rank == 0 and not args.no_vae:
         # image decode that closes the reference's rollout (sd3_5.py:307): reported beside the metric,
         # not inside it -- `value` counts denoise steps, the decode is once per sample
         from mi355_flow.vae import VAEConfig, VAEDecoder
@@ -654,7 +680,7 @@ def main():
                              "note": "SD3 AutoencoderKL decoder, synthetic weights; outside the timed region"}
         assert bool(torch.isfinite(img.float()).all())
         dec.close()
-    if rank == 0 and world == 1 and not flux_mode and not args.no_train_step:
+    if args.full and rank == 0 and world == 1 and not flux_mode and not args.no_train_step:
         # the optimize() replay step with gradients (reference trainers/grpo.py:185-342) at B = 2, 1024^2, the reference's
         # default target modules: forward with stash + native backward.  Its own process (its stash and scratch are ~10 GiB; nothing of
         # this process's state is touched), reported beside the metric, never inside it; any failure is recorded, not raised.
@@ -673,7 +699,7 @@ def main():
                                             "replay's; untimed w.r.t. `value`"}
         except Exception as e:  # noqa: BLE001
             out["optimize_step"] = {"error": repr(e)}
-    if rank == 0 and world == 1 and not flux_mode and not args.no_train_step:
+    if args.full and rank == 0 and world == 1 and not flux_mode and not args.no_train_step:
         # the same for FLUX.1 (round 4: native backward, SURVEY.md 8(f) N1 over N3): FLUX.1-dev geometry, B = 1, 1024^2 (4608 joint tokens),
         # the reference's default FLUX.1 target modules (5.4 B trainable parameters); own process (~110 GB of HBM), recorded, never raised
         try:
@@ -689,7 +715,7 @@ def main():
                                                   "torch.equal the no-grad replay's; untimed w.r.t. `value`"}
         except Exception as e:  # noqa: BLE001
             out["optimize_step_flux1"] = {"error": repr(e)}
-    if rank == 0 and world == 1 and not flux_mode and not args.no_train_step:
+    if args.full and rank == 0 and world == 1 and not flux_mode and not args.no_train_step:
         # ... and for Qwen-Image (round 4: native backward, SURVEY.md 8(f) N1 over N4; BASELINE.json configs[4]'s family): 60 layers, B = 1, 1024^2,
         # true CFG (forward batch [negative | positive]), the reference's default target modules (6.8 B trainable parameters); own process
         # (~150 GB of HBM: 41 GB masters + 41 GB engine copy + transposed weights + 37 GB stash), recorded, never raised
@@ -706,7 +732,7 @@ def main():
                                                        "(qwen_image.py:81-89); grad-mode log-prob torch.equal the no-grad replay's; untimed w.r.t. `value`"}
         except Exception as e:  # noqa: BLE001
             out["optimize_step_qwen_image"] = {"error": repr(e)}
-    if rank == 0 and world == 1 and not flux_mode and not args.no_train_step:
+    if args.full and rank == 0 and world == 1 and not flux_mode and not args.no_train_step:
         # ... and for Wan2.1-T2V-1.3B at BASELINE.json configs[3]'s OWN shape: 480 x 832 x 49 frames (20 280 video tokens), B = 1, CFG, all 30 blocks,
         # the reference's default Wan target modules (first timed in round 5's first GPU call: 1092.8 ms, profiles/r05a_wan_train_b1_480p49.json);
         # own process (~83 GiB of HBM), recorded, never raised
@@ -723,7 +749,7 @@ def main():
                                                   "(wan2_t2v.py:74-85); untimed w.r.t. `value`"}
         except Exception as e:  # noqa: BLE001
             out["optimize_step_wan21"] = {"error": repr(e), "stderr_tail": (r.stderr[-400:] if "r" in dir() and hasattr(r, "stderr") else "")}
-    if rank == 0 and world == 1 and not flux_mode and not args.no_families:
+    if args.full and rank == 0 and world == 1 and not flux_mode and not args.no_families:
         # BASELINE.json configs[2..4] on the driver's box: the other engines' rollouts at their own geometries, 2 denoise
         # steps each (the per-step cost does not depend on the step count), each in its own process (24 / 3 / 41 GB of weights), untimed w.r.t.
         # `value`; a failure is recorded under its key, never raised.
@@ -744,7 +770,7 @@ def main():
         fam["note"] = ("real geometries (FLUX.1-dev 11.9 B, Wan2.1-T2V-1.3B, Qwen-Image 60 layers), synthetic weights / prompts, hipGraph / eager as each "
                        "engine ships; denoise-steps/s = samples x steps / wall; forward_frac vs 2.5 PFLOP/s on algorithmic matmul FLOPs")
         out["families"] = fam
-    if (world > 1 or args.ddp_step_world1) and not flux_mode and not args.no_ddp_step:
+    if ((args.full and world > 1) or args.ddp_step_world1) and not flux_mode and not args.no_ddp_step:
         # north star: "gradient all-reduce on RCCL over xGMI for the policy update" -- every rank takes part; a failure on any rank is
         # recorded (and keeps the headline line), never raised
         # This leg is the only part of the file where a rank can wait for another rank that is not coming (one rank failing between two
@@ -814,7 +840,7 @@ def main():
         if rank == 0:
             out["optimize_step_ddp"] = leg
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline and not flux_mode:
+        if args.full and world == 1 and not args.no_cpu_baseline and not flux_mode:
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)
     if world > 1 or (args.ddp_step_world1 and dist.is_initialized()):

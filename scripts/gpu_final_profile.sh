@@ -5,10 +5,10 @@ OUT=$GRAFT_REPO_ROOT/gpurun_out/final
 mkdir -p $OUT; rm -rf $OUT/prof_* $OUT/final_*
 timeout 1500 python -m pytest tests -m gpu -q 2>&1 | tail -3 > $OUT/final_tests.log; cat $OUT/final_tests.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | grep -v amdgpu > $OUT/final_smoke.log; cat $OUT/final_smoke.log
-timeout 900 python bench.py 2>/dev/null > $OUT/final_bench.json; cut -c1-400 $OUT/final_bench.json
-timeout 600 python bench.py --no-cpu-baseline --kernel-timing all 2>/dev/null > $OUT/final_bench_allclasses.json
-timeout 600 python bench.py --no-cpu-baseline --guidance 4.5 --batch 4 2>/dev/null > $OUT/final_bench_cfg.json
-timeout 900 python bench.py --model flux1 --steps 1 --warmup 1 2>/dev/null > $OUT/final_bench_flux.json
+timeout 900 python bench.py --full 2>/dev/null > $OUT/final_bench.json; cut -c1-400 $OUT/final_bench.json
+timeout 600 python bench.py --full --no-cpu-baseline --kernel-timing all 2>/dev/null > $OUT/final_bench_allclasses.json
+timeout 600 python bench.py --full --no-cpu-baseline --guidance 4.5 --batch 4 2>/dev/null > $OUT/final_bench_cfg.json
+timeout 900 python bench.py --full --model flux1 --steps 1 --warmup 1 2>/dev/null > $OUT/final_bench_flux.json
 timeout 600 python scripts/wan_bench.py --batch 2 --denoise-steps 2 2>/dev/null | tail -1 > $OUT/final_bench_wan.json
 timeout 600 python scripts/qwen_bench.py --batch 2 --denoise-steps 2 2>/dev/null | tail -1 > $OUT/final_bench_qwen.json
 timeout 600 python scripts/wan_vae_bench.py 2>/dev/null | tail -2 > $OUT/final_bench_wan_vae.json

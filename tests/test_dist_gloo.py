@@ -71,7 +71,7 @@ def test_bench_self_launches_n_ranks_and_aggregates():
     from conftest import ROOT
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None), env.pop("RANK", None), env.pop("LOCAL_RANK", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "0", "--dry-run",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "0", "--dry-run", "--full",
                         "--batch", "4", "--denoise-steps", "10"], capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -84,7 +84,7 @@ def test_bench_self_launches_n_ranks_and_aggregates():
     assert abs(j["value"] - 4 * 10 * 2 * 2 / wall) < 0.02 * j["value"]      # whole-job aggregate over both ranks
     # the policy-update leg: one optimize() micro-step under DistributedDataParallel, synchronising vs no_sync(), MAX over
     # ranks, bytes handed to the collective -- assembled here on gloo around a stand-in module; the real path wraps the SD3.5 module bound to
-    # the engine (bench.py: `optimize_step_ddp`, world > 1 only)
+    # the engine (bench.py: `optimize_step_ddp`, world > 1 with `--full` only)
     leg = j["optimize_step_ddp"]
     assert leg["world_size"] == 2 and leg["backend"] == "gloo" and len(leg["per_rank_ms"]) == 2 and all(len(r) == 2 for r in leg["per_rank_ms"])
     assert leg["bytes_reduced_per_microstep"] == 4 * (64 * 128 + 128 + 128 * 64 + 64) and leg["trainable_tensors"] == 4
@@ -94,7 +94,7 @@ def test_bench_self_launches_n_ranks_and_aggregates():
 
 
 def test_bench_single_rank_line_has_no_ddp_leg():
-    """N = 1: no process group, no collective -- the leg must not appear (and `--no-ddp-step` removes it at N > 1)."""
+    """N = 1: no process group, no collective -- the leg must not appear (at N > 1 it is part of `--full`, where `--no-ddp-step` removes it)."""
     import json
     import subprocess
     import sys
@@ -106,10 +106,11 @@ def test_bench_single_rank_line_has_no_ddp_leg():
                        timeout=120, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     assert "optimize_step_ddp" not in json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--dry-run", "--no-ddp-step"],
-                       capture_output=True, text=True, timeout=300, env=env)
-    assert r.returncode == 0, r.stderr[-2000:]
-    assert "optimize_step_ddp" not in json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+    for legs in (["--full", "--no-ddp-step"], []):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--dry-run"] + legs,
+                           capture_output=True, text=True, timeout=300, env=env)
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert "optimize_step_ddp" not in json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0]), legs
 
 
 def _ddp_worker(rank, world, port, out_dir):

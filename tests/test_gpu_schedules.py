@@ -48,13 +48,13 @@ def test_forward_at_sd3_5_large_width_vs_oracle():
 
 
 def test_bench_small_batch_legs_report_numbers():
-    """bench.py's untimed small-batch legs (`--small-batch`: B = 2 at 1024^2; the reference's 512^2 B = 2 CFG example shape) produce finite
+    """bench.py's untimed small-batch legs (part of `--full`: B = 2 at 1024^2; the reference's 512^2 B = 2 CFG example shape) produce finite
     figures and do not disturb the headline line (`--no-small-batch` switches them off)."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "1", "--warmup", "1", "--no-vae", "--no-cpu-baseline", "--no-families",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "1", "--warmup", "1", "--no-vae", "--no-cpu-baseline", "--no-families",
                         "--no-train-step", "--no-clock-probe", "--no-selfcheck"],      # (the other legs have their own scripts; this test is about one leg)
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -63,6 +63,29 @@ def test_bench_small_batch_legs_report_numbers():
     assert "error" not in sb, sb
     for tag in ("b2_1024_nocfg_28", "b2_512_cfg4.5_10"):
         assert sb[tag]["denoise_steps_per_s"] > 0 and 0 < sb[tag]["forward_frac"] < 1
+
+
+def test_bench_plain_run_carries_the_headline_figure_only():
+    """Without `--full` bench.py sets up, warms up, times its steps and prints the line: the contract keys and the roofline of the timed
+    region, none of the legs that take rollouts, processes or host-core time of their own."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1"], capture_output=True, text=True,
+                       timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    line = json.loads(lines[0])
+    assert line["value"] > 0 and line["steps"] == 1 and line["warmup"] == 1 and line["unit"] == "denoise-steps/sec" and line["dtype"] == "bf16"
+    assert abs(line["value"] - 8 * 28 / (line["ms_per_step"] * 1e-3)) <= 2e-3 * line["value"]
+    assert 0 < line["roofline"]["frac"] < 1 and line["roofline"]["by_class"]["attention"]["launches"] == 37 * 28
+    legs = {"cpu_baseline", "power", "graph_vs_eager", "small_batch", "vae_decode", "families", "optimize_step", "optimize_step_flux1",
+            "optimize_step_qwen_image", "optimize_step_wan21", "optimize_step_ddp"}
+    assert not legs & set(line), sorted(legs & set(line))
+    own_rollouts = {"attention_dynamic", "guaranteed_floor", "gemm", "by_class_single_stream", "delivered_clock_mhz"}
+    assert not own_rollouts & set(line["roofline"]), sorted(own_rollouts & set(line["roofline"]))
 
 
 def test_qwen_two_stream_and_graph_replay_are_bit_identical():
