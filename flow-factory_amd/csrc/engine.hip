@@ -465,30 +465,32 @@ static int ln_mod(mi355_plan* p, hipStream_t st, const bf16_t* x, bf16_t* out, b
     return 0;
 }
 
-// q/k projection with fused bias + per-head RMSNorm + scatter, and V^T projection (operands swapped)
+// q/k projection with fused bias + per-head RMSNorm + scatter, and V^T projection (operands swapped).  `rstd` (training mode, else null): 1 / rms
+// per (token, head) of q and k for the backward; `qk_only` skips the V^T projection (key 29 bit 4)
 static int qkv_proj(mi355_plan* p, hipStream_t st, const bf16_t* xin, int M, int rps, const bf16_t* w_qk,
                     const float* b_qk, const bf16_t* w_v, const float* b_v, const float* nq, const float* nk,
-                    bf16_t* q, bf16_t* k, bf16_t* vT, int S_pad, int s_off, hipStream_t st_v = nullptr, bool v_only = false,
-                    bool qk_only = false) {
+                    bf16_t* q, bf16_t* k, bf16_t* vT, int S_pad, int s_off, float* rstd, bool qk_only, hipStream_t st_v = nullptr) {
     if (!st_v) st_v = st;                 // the V^T GEMM reads the same input as the q|k GEMM and may run beside it
     mi355_engine* e = p->e;
     const int D = e->D;
     GemmParams g = gp(xin, D, w_qk, D, M, 2 * D, D, EPI_QK_NORM, b_qk, nullptr, 0);
     g.q = q; g.k = k; g.nw_q = nq; g.nw_k = nk; g.H = e->cfg.num_heads; g.S_pad = S_pad; g.s_off = s_off;
-    g.rows_per_sample = rps; g.eps = e->cfg.eps;
+    g.rows_per_sample = rps; g.eps = e->cfg.eps; g.rstd_out = rstd;
     // deferred-rescale attention consumes q with the softmax scale 0.125*log2(e) folded in (same single bf16 rounding)
     if (get_attn_variant() >= 1) g.q_scale = 0.125f * 1.4426950408889634f;
-    if (!v_only) HIPCHK(gemm_p(g, st));
+    HIPCHK(gemm_p(g, st));
     GemmParams gv = gp(w_v, D, xin, D, D, M, D, EPI_VT, b_v, nullptr, 0);
     gv.q = vT; gv.H = e->cfg.num_heads; gv.S_pad = S_pad; gv.s_off = s_off; gv.rows_per_sample = rps;
-    if (!qk_only && !(g_ablate & 4)) HIPCHK(gemm_p(gv, st_v));
+    if (!qk_only) HIPCHK(gemm_p(gv, st_v));
     return 0;
 }
 
+// `y_stash` (full training scope, else null): the un-gated projection, which d gate needs
 static int gate_res(mi355_plan* p, hipStream_t st, const bf16_t* A, int K, const bf16_t* W, const float* bias, bf16_t* x,
-                    int M, int rps, const bf16_t* mod, int gate_off) {
+                    int M, int rps, const bf16_t* mod, int gate_off, bf16_t* y_stash) {
     GemmParams g = gp(A, K, W, K, M, p->e->D, K, EPI_GATE_RES, bias, x, p->e->D);
     g.aux = mod + gate_off; g.ld_aux = p->e->mod_cols; g.rows_per_sample = rps;
+    if (y_stash) { g.stash = y_stash; g.ld_stash = p->e->D; }
     HIPCHK(gemm_p(g, st));
     return 0;
 }
@@ -549,17 +551,90 @@ static int two_stream_init(mi355_plan* p) {
     return 0;
 }
 
-// One transformer forward.  `mod` = this step's rows of mod_all; c0 / pe / conditioning prepared.
-static int forward_core(mi355_plan* p, hipStream_t st, const void* latents, int lat_dt, const bf16_t* mod, bf16_t* v_out) {
-    mi355_engine* e = p->e;
-    const int D = e->D, F = e->F, H = e->cfg.num_heads;
-    const int Mi = p->Mi, Mc = p->Mc, Ni = p->Ni, Nt = p->Nt;
-    const int Ni_pad = (Ni + 63) / 64 * 64;
+// ---- training-mode stash (engine_train.inc owns it; forward_core fills it) ------------------------------------------------------------
+struct TrainBlkFull { bf16_t *y_o, *y_o2, *y_ff, *y_co, *y_cff; };   // un-gated projections (full scope only)
+struct TrainBlk {
+    bf16_t *x_in, *xn, *xn2, *x_mid, *xn_mlp, *pre, *o_img, *o2;          // image stream
+    bf16_t *c_in, *cn, *c_mid, *cn_mlp, *cpre, *o_ctx;                    // context stream
+    bf16_t *q, *k, *vT, *q2, *k2, *vT2;
+    float *lse, *lse2, *rstd_img, *rstd_ctx, *rstd2;
+};
+struct mi355_train {
+    mi355_plan* p;
+    char* ws = nullptr; size_t ws_bytes = 0;
+    std::vector<TrainBlk> blk;
+    bf16_t* x_final;
+    bf16_t *mod, *vnet;        // this step's modulation row block / network output: the plan's own copies may be overwritten by a no-grad
+                               // forward (the KL reference pass of trainers/grpo.py:281-292) between this forward and its backward
+    // backward scratch
+    bf16_t *dx, *dc, *dy, *dyc, *dpre, *hid, *dxn, *dxn2, *dcn, *do_img, *do_ctx, *doh, *v, *dq, *dk, *dv, *dqkv_img, *dqkv_ctx,
+        *aT, *xT, *dproj;
+    float *delta, *nld, *dv32, *part, *csum, *zero_bias;
+    bf16_t* dpre_c;            // the context stream's own d(pre-activation): its MLP backward runs beside the image stream's
+    bf16_t *aT_c, *xT_c, *hid_c;   // ... and its own wgrad scratch (operand transposes, gelu(pre), split-K partials, column-sum partials)
+    float *part_c, *csum_c;
+    size_t part_floats;
+    const bf16_t* xT_holds = nullptr;       // the input whose transpose xT / xT_c currently hold (wgrad: a group sharing X transposes it once)
+    const bf16_t* xT_c_holds = nullptr;
+    int Mi_pad, Mc_pad;
+    // the context-stream chain of the training forward / backward runs on `side` (mi355_tune_set(22, .)); ev[2 i] = join, ev[2 i + 1] = fork
+    hipStream_t side = nullptr;
+    std::vector<hipEvent_t> ev;
+    // full scope (allocated on first use)
+    char* wsf = nullptr; size_t wsf_bytes = 0;
+    bool fwd_full = false;              // the last training-mode forward stashed the full-scope extras
+    std::vector<TrainBlkFull> fblk;
+    bf16_t *xn_out, *patches, *enc, *pool, *tproj, *h1, *p1, *pemb, *semb, *dmod16, *temb, *dtemb, *dh1, *pre1, *dsemb, *wT_small;
+    float *dmod, *dw_part;
+};
+
+// Where the text chain of one forward runs.  The rollout forward fills this from the plan (rollout_sched: keys 8-11), the training forward
+// from the training state (mi355_denoise_step_train: key 22), whose side stream and events the backward shares.
+struct FwdSched {
+    hipStream_t side;                // the text chain's stream; null = the caller's (single stream)
+    const hipEvent_t *join, *fork;   // block i's events at [i * ev_stride]; i = L: the join that ends a forward / the fork that starts it
+    int ev_stride;
+    bool three, late;                // third stream (key 11); fork after a dual block's last attention (key 10)
+    int mid_hint;                    // mid-size-GEMM plan hint (gemm.hip) while the forward is issued
+    int ablate;                      // key 29, bits 1 and 4
+};
+
+// `to` goes on only after everything enqueued on `from` so far
+static int ev_sync(hipEvent_t ev, hipStream_t from, hipStream_t to) {
+    HIPCHK(ev_record(ev, from));
+    HIPCHK(ev_wait(to, ev));
+    return 0;
+}
+
+static int rollout_sched(mi355_plan* p, FwdSched* s) {
+    *s = FwdSched{};
     // The mid-size GEMM kernel (gemm.hip, one 160-KiB workgroup per CU) keeps the text chain's workgroups off the CUs it holds.  Measured
     // in-model (profiles/r06d_*): that pays where the text chain is a real share of the work -- the reference's 512^2 B = 2 CFG example,
     // 1332 text rows beside 4096 image rows: +2.7 % -- and costs where it is a sliver (1024^2 B = 1, 333 rows: -1.6 %).  The choice depends on
     // the PLAN's shape only, never on data, and the kernels are bit-identical: a sample's result does not depend on it.
-    struct MidHint { explicit MidHint(int v) { set_mid_plan_hint(v); } ~MidHint() { set_mid_plan_hint(1); } } mid_hint(4L * Mc >= Mi ? 1 : 0);
+    s->mid_hint = 4L * p->Mc >= p->Mi ? 1 : 0;
+    s->ablate = g_ablate;
+    if (!two_stream_wanted(p)) return 0;
+    CHK(two_stream_init(p));
+    s->side = p->side; s->join = p->ev_join.data(); s->fork = p->ev_fork.data(); s->ev_stride = 1;
+    s->three = three_stream_wanted(p); s->late = late_fork_wanted(p);
+    return 0;
+}
+
+// One transformer forward.  `mod` = this step's rows of mod_all; c0 / pe / conditioning prepared.
+// Training mode (`t` = the plan's training state, else null): the SAME launches with the activations the backward needs written to the block's
+// own buffers instead of the plan's shared ones (+ the block inputs copied aside, the log-sum-exp / 1/rms side outputs switched on, the MLP
+// pre-activations -- full scope: also the un-gated projections -- stashed by the GEMM epilogue): same kernels, same epilogues on the same
+// values, so the replay log-prob is bit-identical to the rollout's.
+static int forward_core(mi355_plan* p, hipStream_t st, const FwdSched& s, const void* latents, int lat_dt, const bf16_t* mod, bf16_t* v_out,
+                        mi355_train* t = nullptr) {
+    mi355_engine* e = p->e;
+    const int D = e->D, F = e->F, H = e->cfg.num_heads;
+    const int Mi = p->Mi, Mc = p->Mc, Ni = p->Ni, Nt = p->Nt;
+    const int Ni_pad = (Ni + 63) / 64 * 64;
+    const size_t xi_b = (size_t)Mi * D * 2, xc_b = (size_t)Mc * D * 2;
+    const bool full = t && t->fwd_full;
+    struct MidHint { explicit MidHint(int v) { set_mid_plan_hint(v); } ~MidHint() { set_mid_plan_hint(1); } } mid_hint(s.mid_hint);
     if (!p->pos_ready) {
         HIPCHK(launch_pos_crop(e->pos_embed, p->pe, e->cfg.pos_embed_max_size, p->hp, p->wp, D, st));
         p->pos_ready = true;
@@ -571,100 +646,107 @@ static int forward_core(mi355_plan* p, hipStream_t st, const void* latents, int 
         g.aux = p->pe; g.ld_aux = D; g.rows_per_sample = Ni;
         HIPCHK(gemm_p(g, st));
     }
-    HIPCHK(copy_d2d(p->c, p->c0, (size_t)Mc * D * 2, st));
-    // `ts` carries the text-stream chain: the caller's stream, or the plan's side stream (see above)
-    const bool two = two_stream_wanted(p);
-    hipStream_t ts = st;
-    if (two) {
-        CHK(two_stream_init(p));
-        ts = p->side;
-        HIPCHK(ev_record(p->ev_fork[e->L], st));           // c, the conditioning and the previous forward are complete on `st`
-        HIPCHK(ev_wait(ts, p->ev_fork[e->L]));
-    }
-    const bool three = two && three_stream_wanted(p);
+    HIPCHK(copy_d2d(p->c, p->c0, xc_b, st));
+    // `ts` carries the text-stream chain: the caller's stream, or the side stream (see above)
+    const bool two = s.side != nullptr;
+    hipStream_t ts = two ? s.side : st;
+    if (two) CHK(ev_sync(s.fork[e->L * s.ev_stride], st, ts));     // c, the conditioning and the previous forward are complete on `st`
+    const bool three = two && s.three;
     hipStream_t vs = three ? p->side_v : st;
+    const bool text = !(s.ablate & 1), qk_only = (s.ablate & 4) != 0;
     bool text_open = false;      // the side stream holds work that `st` has not waited for yet
     for (int i = 0; i < e->L; ++i) {
         const BlockW& b = e->blk[i];
+        const TrainBlk* k = t ? &t->blk[i] : nullptr;
+        const TrainBlkFull* f = full ? &t->fblk[i] : nullptr;
         const int mi = b.mod_img, mc = b.mod_ctx;
+        bf16_t *xn = k ? k->xn : p->xn, *xn2 = k ? k->xn2 : p->xn2, *cn = k ? k->cn : p->cn;
+        bf16_t *q = k ? k->q : p->q, *kk = k ? k->k : p->k, *vT = k ? k->vT : p->vT;
+        bf16_t *q2 = k ? k->q2 : p->q2, *k2 = k ? k->k2 : p->k2, *vT2 = k ? k->vT2 : p->vT2;
+        bf16_t *o_img = k ? k->o_img : p->o_img, *o_ctx = k ? k->o_ctx : p->o_ctx, *o2 = k ? k->o2 : p->o_img;
+        if (k) {
+            HIPCHK(copy_d2d(k->x_in, p->x, xi_b, st));
+            HIPCHK(copy_d2d(k->c_in, p->c, xc_b, ts));
+        }
         // AdaLN-Zero chunk order: shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp[, shift2, scale2, gate2]
-        CHK(ln_mod(p, st, p->x, p->xn, b.dual ? p->xn2 : nullptr, mod, Mi, Ni, mi + 0 * D, mi + 1 * D, mi + 6 * D, mi + 7 * D));
-        const bool text = !(g_ablate & 1);
+        CHK(ln_mod(p, st, p->x, xn, b.dual ? xn2 : nullptr, mod, Mi, Ni, mi + 0 * D, mi + 1 * D, mi + 6 * D, mi + 7 * D));
         if (!text) {}
         else if (b.last)  // AdaLayerNormContinuous: scale first, then shift
-            CHK(ln_mod(p, ts, p->c, p->cn, nullptr, mod, Mc, Nt, mc + 1 * D, mc + 0 * D, 0, 0));
+            CHK(ln_mod(p, ts, p->c, cn, nullptr, mod, Mc, Nt, mc + 1 * D, mc + 0 * D, 0, 0));
         else
-            CHK(ln_mod(p, ts, p->c, p->cn, nullptr, mod, Mc, Nt, mc + 0 * D, mc + 1 * D, 0, 0));
+            CHK(ln_mod(p, ts, p->c, cn, nullptr, mod, Mc, Nt, mc + 0 * D, mc + 1 * D, 0, 0));
         // joint attention: image tokens first, then text
-        if (three) {             // xn / xn2 are complete on `st`; the previous block's attentions (readers of q2 / k2 / vT2) are behind them
-            HIPCHK(ev_record(p->ev_vfork[i], st));
-            HIPCHK(ev_wait(vs, p->ev_vfork[i]));
-        }
-        CHK(qkv_proj(p, st, p->xn, Mi, Ni, b.w_qk, b.b_qk, b.w_v, b.b_v, b.nq, b.nk, p->q, p->k, p->vT, p->S_pad, 0, vs));
-        if (text) CHK(qkv_proj(p, ts, p->cn, Mc, Nt, b.w_cqk, b.b_cqk, b.w_cv, b.b_cv, b.ncq, b.nck, p->q, p->k, p->vT, p->S_pad, Ni));
+        if (three) CHK(ev_sync(p->ev_vfork[i], st, vs));    // xn / xn2 are complete on `st`; the previous block's attentions (readers of q2 / k2 / vT2) are behind them
+        CHK(qkv_proj(p, st, xn, Mi, Ni, b.w_qk, b.b_qk, b.w_v, b.b_v, b.nq, b.nk, q, kk, vT, p->S_pad, 0, k ? k->rstd_img : nullptr, qk_only, vs));
+        if (text) CHK(qkv_proj(p, ts, cn, Mc, Nt, b.w_cqk, b.b_cqk, b.w_cv, b.b_cv, b.ncq, b.nck, q, kk, vT, p->S_pad, Ni, k ? k->rstd_ctx : nullptr, qk_only));
         if (three) {
-            HIPCHK(ev_record(p->ev_vjoin[i], vs));
-            HIPCHK(ev_wait(st, p->ev_vjoin[i]));
+            CHK(ev_sync(p->ev_vjoin[i], vs, st));
             if (b.dual) {        // the dual attention's projections: beside the joint attention instead of behind it
-                CHK(qkv_proj(p, vs, p->xn2, Mi, Ni, b.w_qk2, b.b_qk2, b.w_v2, b.b_v2, b.nq2, b.nk2, p->q2, p->k2, p->vT2, Ni_pad, 0));
+                CHK(qkv_proj(p, vs, xn2, Mi, Ni, b.w_qk2, b.b_qk2, b.w_v2, b.b_v2, b.nq2, b.nk2, q2, k2, vT2, Ni_pad, 0, k ? k->rstd2 : nullptr, qk_only));
                 HIPCHK(ev_record(p->ev_djoin[i], vs));
             }
         }
         if (two) {               // join: the attention reads the text rows of q / k / vT and overwrites o_ctx
-            HIPCHK(ev_record(p->ev_join[i], ts));
-            HIPCHK(ev_wait(st, p->ev_join[i]));
+            CHK(ev_sync(s.join[i * s.ev_stride], ts, st));
             text_open = false;
         }
         {
-            AttnParams a{p->q, p->k, p->vT, p->o_img, p->o_ctx, p->Bp, H, p->S, p->S_pad, Ni, get_attn_variant() >= 1,
-                         g_attn_static ? b.bound_joint : 0.f};
+            AttnParams a{q, kk, vT, o_img, o_ctx, p->Bp, H, p->S, p->S_pad, Ni, get_attn_variant() >= 1,
+                         g_attn_static ? b.bound_joint : 0.f, k ? k->lse : nullptr};
             HIPCHK(attn_p(a, st));
         }
-        // fork: text work follows (never after the final attention: nothing would join it).  The fork point is the block's LAST attention
-        // launch -- the dual (image-only) attention of a dual block also fills every CU, and text-stream GEMMs squeezed in beside it only
-        // stretch it (measured: attention 840 -> 900 us per launch with the fork before it); it touches neither o_ctx nor c.
-        const bool fork_here = two && (!b.last || i + 1 < e->L);
+        // fork: text work follows -- in every block but the last, whose text stream feeds nothing (nothing would join it).  The fork point is the
+        // block's LAST attention launch where `late` -- the dual (image-only) attention of a dual block also fills every CU, and text-stream GEMMs
+        // squeezed in beside it only stretch it (measured: attention 840 -> 900 us per launch with the fork before it); it touches neither o_ctx nor c.
+        const bool fork_here = two && !b.last;
         auto fork = [&]() -> int {
-            HIPCHK(ev_record(p->ev_fork[i], st));
-            HIPCHK(ev_wait(ts, p->ev_fork[i]));
+            CHK(ev_sync(s.fork[i * s.ev_stride], st, ts));
             text_open = true;
             return 0;
         };
-        const bool late = b.dual && late_fork_wanted(p);
+        const bool late = b.dual && s.late;
         if (fork_here && !late) CHK(fork());
-        CHK(gate_res(p, st, p->o_img, D, b.w_o, b.b_o, p->x, Mi, Ni, mod, mi + 2 * D));
-        if (!two && !b.last && text) CHK(gate_res(p, st, p->o_ctx, D, b.w_co, b.b_co, p->c, Mc, Nt, mod, mc + 2 * D));
+        CHK(gate_res(p, st, o_img, D, b.w_o, b.b_o, p->x, Mi, Ni, mod, mi + 2 * D, f ? f->y_o : nullptr));
+        if (!two && !b.last && text) CHK(gate_res(p, st, o_ctx, D, b.w_co, b.b_co, p->c, Mc, Nt, mod, mc + 2 * D, f ? f->y_co : nullptr));
         if (b.dual) {
             if (three) HIPCHK(ev_wait(st, p->ev_djoin[i]));
-            else CHK(qkv_proj(p, st, p->xn2, Mi, Ni, b.w_qk2, b.b_qk2, b.w_v2, b.b_v2, b.nq2, b.nk2, p->q2, p->k2, p->vT2, Ni_pad, 0));
-            // S == n_img: this launch writes o_img only, never o_ctx (which the text chain reads after the fork)
-            AttnParams a{p->q2, p->k2, p->vT2, p->o_img, p->o_ctx, p->Bp, H, Ni, Ni_pad, Ni, get_attn_variant() >= 1,
-                         g_attn_static ? b.bound_dual : 0.f};
+            else CHK(qkv_proj(p, st, xn2, Mi, Ni, b.w_qk2, b.b_qk2, b.w_v2, b.b_v2, b.nq2, b.nk2, q2, k2, vT2, Ni_pad, 0, k ? k->rstd2 : nullptr, qk_only));
+            // S == n_img: this launch writes its image output only, never o_ctx (which the text chain reads after the fork)
+            AttnParams a{q2, k2, vT2, o2, o_ctx, p->Bp, H, Ni, Ni_pad, Ni, get_attn_variant() >= 1,
+                         g_attn_static ? b.bound_dual : 0.f, k ? k->lse2 : nullptr};
             HIPCHK(attn_p(a, st));
             if (fork_here && late) CHK(fork());
-            CHK(gate_res(p, st, p->o_img, D, b.w_o2, b.b_o2, p->x, Mi, Ni, mod, mi + 8 * D));
+            CHK(gate_res(p, st, o2, D, b.w_o2, b.b_o2, p->x, Mi, Ni, mod, mi + 8 * D, f ? f->y_o2 : nullptr));
         }
-        if (two && !b.last && text) CHK(gate_res(p, ts, p->o_ctx, D, b.w_co, b.b_co, p->c, Mc, Nt, mod, mc + 2 * D));
+        if (two && !b.last && text) CHK(gate_res(p, ts, o_ctx, D, b.w_co, b.b_co, p->c, Mc, Nt, mod, mc + 2 * D, f ? f->y_co : nullptr));
         // MLP (image stream)
-        CHK(ln_mod(p, st, p->x, p->xn, nullptr, mod, Mi, Ni, mi + 3 * D, mi + 4 * D, 0, 0));
+        bf16_t* xn_mlp = k ? k->xn_mlp : p->xn;
+        if (k) HIPCHK(copy_d2d(k->x_mid, p->x, xi_b, st));
+        CHK(ln_mod(p, st, p->x, xn_mlp, nullptr, mod, Mi, Ni, mi + 3 * D, mi + 4 * D, 0, 0));
         {
-            GemmParams g = gp(p->xn, D, b.w_ff1, D, Mi, F, D, EPI_BIAS_GELU, b.b_ff1, p->hid, F);
+            GemmParams g = gp(xn_mlp, D, b.w_ff1, D, Mi, F, D, EPI_BIAS_GELU, b.b_ff1, p->hid, F);
+            if (k) { g.stash = k->pre; g.ld_stash = F; }
             HIPCHK(gemm_p(g, st));
         }
-        CHK(gate_res(p, st, p->hid, F, b.w_ff2, b.b_ff2, p->x, Mi, Ni, mod, mi + 5 * D));
+        CHK(gate_res(p, st, p->hid, F, b.w_ff2, b.b_ff2, p->x, Mi, Ni, mod, mi + 5 * D, f ? f->y_ff : nullptr));
         if (!b.last && text) {
-            CHK(ln_mod(p, ts, p->c, p->cn, nullptr, mod, Mc, Nt, mc + 3 * D, mc + 4 * D, 0, 0));
-            GemmParams g = gp(p->cn, D, b.w_cff1, D, Mc, F, D, EPI_BIAS_GELU, b.b_cff1, p->chid, F);
+            bf16_t* cn_mlp = k ? k->cn_mlp : p->cn;
+            if (k) HIPCHK(copy_d2d(k->c_mid, p->c, xc_b, ts));
+            CHK(ln_mod(p, ts, p->c, cn_mlp, nullptr, mod, Mc, Nt, mc + 3 * D, mc + 4 * D, 0, 0));
+            GemmParams g = gp(cn_mlp, D, b.w_cff1, D, Mc, F, D, EPI_BIAS_GELU, b.b_cff1, p->chid, F);
+            if (k) { g.stash = k->cpre; g.ld_stash = F; }
             HIPCHK(gemm_p(g, ts));
-            CHK(gate_res(p, ts, p->chid, F, b.w_cff2, b.b_cff2, p->c, Mc, Nt, mod, mc + 5 * D));
+            CHK(gate_res(p, ts, p->chid, F, b.w_cff2, b.b_cff2, p->c, Mc, Nt, mod, mc + 5 * D, f ? f->y_cff : nullptr));
         }
     }
-    if (two && text_open) {      // a model whose last block keeps its text stream: rejoin before the caller's stream goes on
-        HIPCHK(ev_record(p->ev_join[e->L], ts));
-        HIPCHK(ev_wait(st, p->ev_join[e->L]));
-    }
+    if (two && text_open) CHK(ev_sync(s.join[e->L * s.ev_stride], ts, st));   // a model whose last block keeps its text stream: rejoin before the caller's stream goes on
+    if (t) HIPCHK(copy_d2d(t->x_final, p->x, xi_b, st));
     // norm_out (scale first) + proj_out + unpatchify
     CHK(ln_mod(p, st, p->x, p->xn, nullptr, mod, Mi, Ni, e->mod_out + 1 * D, e->mod_out + 0 * D, 0, 0));
+    if (full) {
+        HIPCHK(copy_d2d(t->xn_out, p->xn, xi_b, st));
+        HIPCHK(copy_d2d(t->patches, p->patches, (size_t)Mi * e->KP * 2, st));
+    }
     {
         const int NO = e->cfg.patch_size * e->cfg.patch_size * e->cfg.out_channels;
         GemmParams g = gp(p->xn, D, e->w_proj, D, Mi, NO, D, EPI_UNPATCH, e->b_proj, v_out, 0);
@@ -684,7 +766,9 @@ extern "C" int mi355_transformer_forward(mi355_plan* p, void* stream, const void
     CHK(prepare_prompt(p, st, enc_a, pooled_a, enc_b, pooled_b));
     HIPCHK(copy_d2d(p->t_dev, t, (size_t)p->Bp * 4, st));
     CHK(prepare_conditioning(p, st, 1, t_round_dtype));
-    return forward_core(p, st, latents, lat_dtype, p->mod_all, (bf16_t*)v_out);
+    FwdSched s;
+    CHK(rollout_sched(p, &s));
+    return forward_core(p, st, s, latents, lat_dtype, p->mod_all, (bf16_t*)v_out);
 }
 
 static int sde_call(hipStream_t st, int batch, int64_t n, const void* v_text, const void* v_uncond, int v_dtype, float guidance,
@@ -788,11 +872,13 @@ static int rollout_body(mi355_plan* p, hipStream_t st, int n_steps, int dynamics
     const size_t lat_bytes = (size_t)p->B * p->n_lat * esz;
     // cast_latents(init) -> trajectory position 0 (sd3_5.py:266-267)
     HIPCHK(launch_convert(p->io_init, init_dtype, p->io_traj, storage_dtype, (long)p->B * p->n_lat, st));
+    FwdSched s;
+    CHK(rollout_sched(p, &s));
     for (int i = 0; i < n_steps; ++i) {
         const bf16_t* mod = p->mod_all + (int64_t)i * Bp * p->e->mod_cols;
         char* cur = p->io_traj + (size_t)i * lat_bytes;
         char* nxt = p->io_traj + (size_t)(i + 1) * lat_bytes;
-        CHK(forward_core(p, st, cur, storage_dtype, mod, p->v));
+        CHK(forward_core(p, st, s, cur, storage_dtype, mod, p->v));
         const bf16_t* vu = p->ncfg == 2 ? p->v : nullptr;
         const bf16_t* vt = p->ncfg == 2 ? p->v + (int64_t)p->B * p->n_lat : p->v;
         // the log-prob of a step is only meaningful (and only read) when its noise level is > 0; the kernel

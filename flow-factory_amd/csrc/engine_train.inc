@@ -2,10 +2,7 @@
 // src/flow_factory/trainers/grpo.py:185-342: forward-with-grad on stored (x_i, x_{i+1}), replay log-prob, backward).
 // Textually included at the end of engine.hip (shares its engine / plan structs and launch helpers).
 //
-//   mi355_denoise_step_train    : the SAME launch sequence as mi355_denoise_step (same kernels, same epilogues => the replay log-prob
-//                                 is bit-identical to the rollout's: ratio == 1 before any update), with per-block activation buffers
-//                                 instead of the shared scratch, plus three side outputs the backward needs (attention log-sum-exp,
-//                                 q/k 1/rms, MLP pre-activation);
+//   mi355_denoise_step_train    : mi355_denoise_step on engine.hip's forward_core with the plan's training stash (see there);
 //   mi355_denoise_step_backward : d loss / d weights from the upstream gradients of (log_prob, noise_pred, next_latents_mean).
 //
 // Scope of the weight gradients.  DEFAULT scope: the linear layers of the transformer blocks -- attn.{to_q,to_k,to_v,to_out.0,add_q_proj,
@@ -32,46 +29,10 @@
 //                                                      reduction; db = column sums
 // dgrad GEMMs reuse the forward kernels (C = A . W'^T with W' = W^T kept in a second weight arena, refreshed after every re-bind).
 
-struct TrainBlkFull { bf16_t *y_o, *y_o2, *y_ff, *y_co, *y_cff; };   // un-gated projections (full scope only)
-struct TrainBlk {
-    bf16_t *x_in, *xn, *xn2, *x_mid, *xn_mlp, *pre, *o_img, *o2;          // image stream
-    bf16_t *c_in, *cn, *c_mid, *cn_mlp, *cpre, *o_ctx;                    // context stream
-    bf16_t *q, *k, *vT, *q2, *k2, *vT2;
-    float *lse, *lse2, *rstd_img, *rstd_ctx, *rstd2;
-};
 struct TrainWT {   // transposed weights of one block (dgrad operands)
     bf16_t *qkv, *o, *cqkv, *co, *qkv2, *o2, *ff1, *ff2, *cff1, *cff2;
 };
 struct GradSlot { float* g = nullptr; };
-
-struct mi355_train {
-    mi355_plan* p;
-    char* ws = nullptr; size_t ws_bytes = 0;
-    std::vector<TrainBlk> blk;
-    bf16_t* x_final;
-    bf16_t *mod, *vnet;        // this step's modulation row block / network output: the plan's own copies may be overwritten by a no-grad
-                               // forward (the KL reference pass of trainers/grpo.py:281-292) between this forward and its backward
-    // backward scratch
-    bf16_t *dx, *dc, *dy, *dyc, *dpre, *hid, *dxn, *dxn2, *dcn, *do_img, *do_ctx, *doh, *v, *dq, *dk, *dv, *dqkv_img, *dqkv_ctx,
-        *aT, *xT, *dproj;
-    float *delta, *nld, *dv32, *part, *csum, *zero_bias;
-    bf16_t* dpre_c;            // the context stream's own d(pre-activation): its MLP backward runs beside the image stream's
-    bf16_t *aT_c, *xT_c, *hid_c;   // ... and its own wgrad scratch (operand transposes, gelu(pre), split-K partials, column-sum partials)
-    float *part_c, *csum_c;
-    size_t part_floats;
-    const bf16_t* xT_holds = nullptr;       // the input whose transpose xT / xT_c currently hold (wgrad: a group sharing X transposes it once)
-    const bf16_t* xT_c_holds = nullptr;
-    int Mi_pad, Mc_pad;
-    // the context-stream chain of the training forward / backward runs on `side` (mi355_tune_set(22, .)); ev[2 i] = join, ev[2 i + 1] = fork
-    hipStream_t side = nullptr;
-    std::vector<hipEvent_t> ev;
-    // full scope (allocated on first use)
-    char* wsf = nullptr; size_t wsf_bytes = 0;
-    bool fwd_full = false;              // the last training-mode forward stashed the full-scope extras
-    std::vector<TrainBlkFull> fblk;
-    bf16_t *xn_out, *patches, *enc, *pool, *tproj, *h1, *p1, *pemb, *semb, *dmod16, *temb, *dtemb, *dh1, *pre1, *dsemb, *wT_small;
-    float *dmod, *dw_part;
-};
 
 struct TrainEngineState {
     char* arenaT = nullptr; size_t bytes = 0;
@@ -285,32 +246,7 @@ extern "C" int64_t mi355_plan_training_bytes(mi355_plan* p) {
     return p && p->train ? (int64_t)(p->train->ws_bytes + p->train->wsf_bytes) : 0;
 }
 
-// ---- training-mode forward: forward_core with per-block buffers ---------------------------------------------------
-static int qkv_proj_train(mi355_plan* p, hipStream_t st, const bf16_t* xin, int M, int rps, const bf16_t* w_qk, const float* b_qk,
-                          const bf16_t* w_v, const float* b_v, const float* nq, const float* nk, bf16_t* q, bf16_t* k, bf16_t* vT, int S_pad,
-                          int s_off, float* rstd) {
-    mi355_engine* e = p->e;
-    const int D = e->D;
-    GemmParams g = gp(xin, D, w_qk, D, M, 2 * D, D, EPI_QK_NORM, b_qk, nullptr, 0);
-    g.q = q; g.k = k; g.nw_q = nq; g.nw_k = nk; g.H = e->cfg.num_heads; g.S_pad = S_pad; g.s_off = s_off;
-    g.rows_per_sample = rps; g.eps = e->cfg.eps; g.rstd_out = rstd;
-    if (get_attn_variant() >= 1) g.q_scale = 0.125f * 1.4426950408889634f;
-    HIPCHK(gemm_p(g, st));
-    GemmParams gv = gp(w_v, D, xin, D, D, M, D, EPI_VT, b_v, nullptr, 0);
-    gv.q = vT; gv.H = e->cfg.num_heads; gv.S_pad = S_pad; gv.s_off = s_off; gv.rows_per_sample = rps;
-    HIPCHK(gemm_p(gv, st));
-    return 0;
-}
-
-static int gate_res_train(mi355_plan* p, hipStream_t st, const bf16_t* A, int K, const bf16_t* W, const float* bias, bf16_t* x, int M, int rps,
-                          const bf16_t* mod, int gate_off, bf16_t* y_stash) {
-    GemmParams g = gp(A, K, W, K, M, p->e->D, K, EPI_GATE_RES, bias, x, p->e->D);
-    g.aux = mod + gate_off; g.ld_aux = p->e->mod_cols; g.rows_per_sample = rps;
-    g.stash = y_stash; g.ld_stash = p->e->D;
-    HIPCHK(gemm_p(g, st));
-    return 0;
-}
-
+// ---- training-mode forward: forward_core (engine.hip) on the per-block stash ------------------------------------------------------------
 // key 22: the context-stream chain of the training forward and of the backward on a side stream (1 = default).  Its GEMMs have 666 rows at
 // B = 2 (72 workgroups of 128 x 128 on 256 CUs, 45-58 us each, ~10 ms of a 112 ms optimize() step when run in line); beside the image
 // stream's launches they cost nothing.  Same kernels and operands either way: the results are bit-identical.
@@ -337,95 +273,7 @@ static int train_side_init(mi355_train* t) {
     t->side = side;
     return 0;
 }
-// `to` goes on only after everything enqueued on `from` so far
-static int train_sync(mi355_train* t, int idx, hipStream_t from, hipStream_t to) {
-    HIPCHK(ev_record(t->ev[idx], from));
-    HIPCHK(ev_wait(to, t->ev[idx]));
-    return 0;
-}
-
-static int forward_train(mi355_plan* p, mi355_train* t, hipStream_t st, const void* latents, int lat_dt, const bf16_t* mod, bf16_t* v_out) {
-    mi355_engine* e = p->e;
-    const bool full = t->fwd_full;
-    const bool two = g_train_two_stream != 0;
-    if (two) CHK(train_side_init(t));
-    hipStream_t ts = two ? t->side : st;
-    const int D = e->D, F = e->F, H = e->cfg.num_heads;
-    const int Mi = p->Mi, Mc = p->Mc, Ni = p->Ni, Nt = p->Nt;
-    const int Ni_pad = (Ni + 63) / 64 * 64;
-    const size_t xi_b = (size_t)Mi * D * 2, xc_b = (size_t)Mc * D * 2;
-    if (!p->pos_ready) {
-        HIPCHK(launch_pos_crop(e->pos_embed, p->pe, e->cfg.pos_embed_max_size, p->hp, p->wp, D, st));
-        p->pos_ready = true;
-    }
-    HIPCHK(launch_patchify(latents, lat_dt, p->patches, p->B, p->ncfg, p->C, p->h, p->w, e->cfg.patch_size, st));
-    {
-        GemmParams g = gp(p->patches, e->KP, e->w_patch, e->KP, Mi, D, e->KP, EPI_POSADD, e->b_patch, p->x, D);
-        g.aux = p->pe; g.ld_aux = D; g.rows_per_sample = Ni;
-        HIPCHK(gemm_p(g, st));
-    }
-    HIPCHK(copy_d2d(p->c, p->c0, xc_b, st));
-    if (two) CHK(train_sync(t, 2 * e->L + 1, st, ts));       // c, the conditioning and everything before this forward are complete on `st`
-    bool text_open = false;
-    for (int i = 0; i < e->L; ++i) {
-        const BlockW& b = e->blk[i];
-        TrainBlk& k = t->blk[i];
-        const int mi = b.mod_img, mc = b.mod_ctx;
-        HIPCHK(copy_d2d(k.x_in, p->x, xi_b, st));
-        HIPCHK(copy_d2d(k.c_in, p->c, xc_b, ts));
-        CHK(ln_mod(p, st, p->x, k.xn, b.dual ? k.xn2 : nullptr, mod, Mi, Ni, mi + 0 * D, mi + 1 * D, mi + 6 * D, mi + 7 * D));
-        if (b.last) CHK(ln_mod(p, ts, p->c, k.cn, nullptr, mod, Mc, Nt, mc + 1 * D, mc + 0 * D, 0, 0));
-        else CHK(ln_mod(p, ts, p->c, k.cn, nullptr, mod, Mc, Nt, mc + 0 * D, mc + 1 * D, 0, 0));
-        CHK(qkv_proj_train(p, st, k.xn, Mi, Ni, b.w_qk, b.b_qk, b.w_v, b.b_v, b.nq, b.nk, k.q, k.k, k.vT, p->S_pad, 0, k.rstd_img));
-        CHK(qkv_proj_train(p, ts, k.cn, Mc, Nt, b.w_cqk, b.b_cqk, b.w_cv, b.b_cv, b.ncq, b.nck, k.q, k.k, k.vT, p->S_pad, Ni, k.rstd_ctx));
-        if (two) { CHK(train_sync(t, 2 * i, ts, st)); text_open = false; }      // join: the attention reads the text rows of q / k / vT
-        {
-            AttnParams a{k.q, k.k, k.vT, k.o_img, k.o_ctx, p->Bp, H, p->S, p->S_pad, Ni, get_attn_variant() >= 1,
-                         g_attn_static ? b.bound_joint : 0.f, k.lse};
-            HIPCHK(attn_p(a, st));
-        }
-        if (two && !b.last) { CHK(train_sync(t, 2 * i + 1, st, ts)); text_open = true; }   // fork: o_ctx is complete
-        CHK(gate_res_train(p, st, k.o_img, D, b.w_o, b.b_o, p->x, Mi, Ni, mod, mi + 2 * D, full ? t->fblk[i].y_o : nullptr));
-        if (!b.last) CHK(gate_res_train(p, ts, k.o_ctx, D, b.w_co, b.b_co, p->c, Mc, Nt, mod, mc + 2 * D, full ? t->fblk[i].y_co : nullptr));
-        if (b.dual) {
-            CHK(qkv_proj_train(p, st, k.xn2, Mi, Ni, b.w_qk2, b.b_qk2, b.w_v2, b.b_v2, b.nq2, b.nk2, k.q2, k.k2, k.vT2, Ni_pad, 0, k.rstd2));
-            AttnParams a{k.q2, k.k2, k.vT2, k.o2, nullptr, p->Bp, H, Ni, Ni_pad, Ni, get_attn_variant() >= 1,
-                         g_attn_static ? b.bound_dual : 0.f, k.lse2};
-            HIPCHK(attn_p(a, st));
-            CHK(gate_res_train(p, st, k.o2, D, b.w_o2, b.b_o2, p->x, Mi, Ni, mod, mi + 8 * D, full ? t->fblk[i].y_o2 : nullptr));
-        }
-        HIPCHK(copy_d2d(k.x_mid, p->x, xi_b, st));
-        CHK(ln_mod(p, st, p->x, k.xn_mlp, nullptr, mod, Mi, Ni, mi + 3 * D, mi + 4 * D, 0, 0));
-        {
-            GemmParams g = gp(k.xn_mlp, D, b.w_ff1, D, Mi, F, D, EPI_BIAS_GELU, b.b_ff1, p->hid, F);
-            g.stash = k.pre; g.ld_stash = F;
-            HIPCHK(gemm_p(g, st));
-        }
-        CHK(gate_res_train(p, st, p->hid, F, b.w_ff2, b.b_ff2, p->x, Mi, Ni, mod, mi + 5 * D, full ? t->fblk[i].y_ff : nullptr));
-        if (!b.last) {
-            HIPCHK(copy_d2d(k.c_mid, p->c, xc_b, ts));
-            CHK(ln_mod(p, ts, p->c, k.cn_mlp, nullptr, mod, Mc, Nt, mc + 3 * D, mc + 4 * D, 0, 0));
-            GemmParams g = gp(k.cn_mlp, D, b.w_cff1, D, Mc, F, D, EPI_BIAS_GELU, b.b_cff1, p->chid, F);
-            g.stash = k.cpre; g.ld_stash = F;
-            HIPCHK(gemm_p(g, ts));
-            CHK(gate_res_train(p, ts, p->chid, F, b.w_cff2, b.b_cff2, p->c, Mc, Nt, mod, mc + 5 * D, full ? t->fblk[i].y_cff : nullptr));
-        }
-    }
-    if (two && text_open) CHK(train_sync(t, 2 * e->L, ts, st));     // (a model whose last block keeps its text stream)
-    HIPCHK(copy_d2d(t->x_final, p->x, xi_b, st));
-    CHK(ln_mod(p, st, p->x, p->xn, nullptr, mod, Mi, Ni, e->mod_out + 1 * D, e->mod_out + 0 * D, 0, 0));
-    if (full) {
-        HIPCHK(copy_d2d(t->xn_out, p->xn, xi_b, st));
-        HIPCHK(copy_d2d(t->patches, p->patches, (size_t)Mi * e->KP * 2, st));
-    }
-    {
-        const int NO = e->cfg.patch_size * e->cfg.patch_size * e->cfg.out_channels;
-        GemmParams g = gp(p->xn, D, e->w_proj, D, Mi, NO, D, EPI_UNPATCH, e->b_proj, v_out, 0);
-        g.hp = p->hp; g.wp = p->wp; g.patch = e->cfg.patch_size; g.out_ch = e->cfg.out_channels;
-        HIPCHK(gemm_p(g, st));
-    }
-    return 0;
-}
+static int train_sync(mi355_train* t, int idx, hipStream_t from, hipStream_t to) { return ev_sync(t->ev[idx], from, to); }
 
 extern "C" int mi355_denoise_step_train(mi355_plan* p, void* stream, const void* latents, int lat_dtype, const float* t, const void* enc_a,
                                         const void* pooled_a, const void* enc_b, const void* pooled_b, float guidance, const void* next_in,
@@ -462,7 +310,15 @@ extern "C" int mi355_denoise_step_train(mi355_plan* p, void* stream, const void*
         HIPCHK(hipMemcpyAsync(tr->pemb, p->pemb, db, hipMemcpyDeviceToDevice, st));
         HIPCHK(hipMemcpyAsync(tr->semb, p->semb, db, hipMemcpyDeviceToDevice, st));
     }
-    CHK(forward_train(p, tr, st, latents, lat_dtype, p->mod_all, p->v));
+    // the text chain on the training state's side stream (shared with the backward), never a third stream or a late fork; the mid-size-GEMM
+    // hint stays at its default and key 29 is honoured only inside ln_mod
+    FwdSched s{};
+    s.mid_hint = 1;
+    if (g_train_two_stream) {
+        CHK(train_side_init(tr));
+        s.side = tr->side; s.join = tr->ev.data(); s.fork = tr->ev.data() + 1; s.ev_stride = 2;
+    }
+    CHK(forward_core(p, st, s, latents, lat_dtype, p->mod_all, p->v, tr));
     HIPCHK(copy_d2d(tr->mod, p->mod_all, (size_t)p->Bp * p->e->mod_cols * 2, st));
     HIPCHK(copy_d2d(tr->vnet, p->v, (size_t)p->Bp * p->n_lat * 2, st));
     const bf16_t* vu = p->ncfg == 2 ? p->v : nullptr;

@@ -40,6 +40,18 @@ struct SingleW {
     int mod;
     float bound = 0.f;
 };
+// training-mode stash of one block (flux_train.inc owns the arrays; forward_core fills them): what the backward needs of the forward
+struct FTrainDbl {
+    bf16_t *x_in, *xn, *x_mid, *xn_mlp, *pre, *o_img;
+    bf16_t *c_in, *cn, *c_mid, *cn_mlp, *cpre, *o_ctx;
+    bf16_t *q, *k, *vT;
+    float *lse, *rstd_img, *rstd_ctx;
+};
+struct FTrainSgl {
+    bf16_t *y_in, *yn, *pre, *o;
+    bf16_t *q, *k, *vT;
+    float *lse, *rstd;
+};
 
 }  // namespace
 
@@ -341,22 +353,23 @@ int ln_mod(mi355_flux_plan* p, hipStream_t st, const bf16_t* x, bf16_t* out, con
     return 0;
 }
 
-// q|k projection (one GEMM) -> RMSNorm + RoPE + scatter; V^T projection with the scatter fused (operands swapped)
+// q|k projection (one GEMM, staged in `qkb`) -> RMSNorm + RoPE + scatter into q / k; V^T projection with the scatter fused (operands swapped).
+// `rstd` (training mode, else null): 1 / rms per (token, head) of q and k for the producer's backward
 int qkv(mi355_flux_plan* p, hipStream_t st, const bf16_t* xin, int M, int rps, int s_off, const bf16_t* w_qk, const float* b_qk,
-        const bf16_t* w_v, const float* b_v, const float* nq, const float* nk, bf16_t* qkb = nullptr) {
+        const bf16_t* w_v, const float* b_v, const float* nq, const float* nk, bf16_t* qkb, bf16_t* q, bf16_t* k, bf16_t* vT, float* rstd) {
     mi355_flux* e = p->e;
     const int D = e->D;
-    if (!qkb) qkb = p->qkbuf;
     GemmParams g = make_gemm(xin, D, w_qk, D, M, 2 * D, D, EPI_BIAS, b_qk, qkb, 2 * D);
     HIPCHK(launch_gemm(g, st));
     RopeNormParams r;
     memset(&r, 0, sizeof(r));
     r.src = qkb; r.src_ld = 2 * D; r.q_col = 0; r.k_col = D; r.nw_q = nq; r.nw_k = nk; r.cs = p->cs;
-    r.q_out = p->q; r.k_out = p->k; r.M = M; r.H = e->H; r.rows_per_sample = rps; r.s_off = s_off; r.S_pad = p->S_pad;
+    r.q_out = q; r.k_out = k; r.M = M; r.H = e->H; r.rows_per_sample = rps; r.s_off = s_off; r.S_pad = p->S_pad;
     r.eps = e->cfg.eps; r.q_scale = 0.08838834764831845f * 1.4426950408889634f;
+    r.rstd_out = rstd;
     HIPCHK(launch_rope_norm(r, st));
     GemmParams gv = make_gemm(w_v, D, xin, D, D, M, D, EPI_VT, b_v, nullptr, 0);
-    gv.q = p->vT; gv.H = e->H; gv.S_pad = p->S_pad; gv.s_off = s_off; gv.rows_per_sample = rps; gv.hd_shift = 7;
+    gv.q = vT; gv.H = e->H; gv.S_pad = p->S_pad; gv.s_off = s_off; gv.rows_per_sample = rps; gv.hd_shift = 7;
     HIPCHK(launch_gemm(gv, st));
     return 0;
 }
@@ -369,12 +382,14 @@ int gate_res(mi355_flux_plan* p, hipStream_t st, const bf16_t* A, long lda, int 
     return 0;
 }
 
-int attention(mi355_flux_plan* p, hipStream_t st, bf16_t* o_first, long ld_first, int n_first, bf16_t* o_rest, long ld_rest, float bound) {
+// `lse` (training mode, else null): log2-sum-exp per (sample, head, query) for the attention backward
+int attention(mi355_flux_plan* p, hipStream_t st, const bf16_t* q, const bf16_t* k, const bf16_t* vT, bf16_t* o_first, long ld_first, int n_first,
+              bf16_t* o_rest, long ld_rest, float bound, float* lse) {
     Attn128Params a;
     memset(&a, 0, sizeof(a));
-    a.q = p->q; a.k = p->k; a.vT = p->vT; a.o_first = o_first; a.ld_first = ld_first; a.n_first = n_first;
+    a.q = q; a.k = k; a.vT = vT; a.o_first = o_first; a.ld_first = ld_first; a.n_first = n_first;
     a.o_rest = o_rest; a.ld_rest = ld_rest; a.B = p->B; a.H = p->e->H; a.S = p->S; a.S_pad = p->S_pad; a.q_prescaled = 1;
-    a.score_bound = bound;
+    a.score_bound = bound; a.lse = lse;
     HIPCHK(launch_attention128(a, st));
     return 0;
 }
@@ -417,10 +432,16 @@ int flux_two_stream_init(mi355_flux_plan* p) {
     return 0;
 }
 
-int forward_core(mi355_flux_plan* p, hipStream_t st, const void* latents, int lat_dt, const bf16_t* mod, bf16_t* v_out) {
+// Training mode (`dbl` / `sgl` = the plan's per-block stash, `x_final`: flux_train.inc; all null for the rollout): the SAME launches with the
+// activations the backward needs written to the block's own buffers instead of the plan's shared ones (+ the block inputs copied aside, the
+// log-sum-exp / 1/rms side outputs switched on, the MLP pre-activations stashed by the GEMM epilogue): the same kernel binaries on the same
+// values -- the velocity is bit-identical, so the replay log-prob equals the rollout's.
+int forward_core(mi355_flux_plan* p, hipStream_t st, const void* latents, int lat_dt, const bf16_t* mod, bf16_t* v_out,
+                 const FTrainDbl* dbl = nullptr, const FTrainSgl* sgl = nullptr, bf16_t* x_final = nullptr) {
     mi355_flux* e = p->e;
     const int D = e->D, F = e->F, C = e->cfg.in_channels;
     const int Ni = p->Ni, Nt = p->Nt, S = p->S;
+    const size_t xi_b = (size_t)p->Mi * D * 2, xc_b = (size_t)p->Mc * D * 2, y_b = (size_t)p->M * D * 2;
     const bool two = flux_two_stream_wanted(p) && e->L > 0;
     hipStream_t ts = st;                               // carries the text chain of the double blocks
     bf16_t *qkb_c = p->qkbuf, *big_c = p->big;
@@ -435,35 +456,49 @@ int forward_core(mi355_flux_plan* p, hipStream_t st, const void* latents, int la
     }
     GemmParams gx = make_gemm(lat, C, e->w_x, C, p->Mi, D, C, EPI_BIAS, e->b_x, p->x, D);
     HIPCHK(launch_gemm(gx, st));
-    HIPCHK(copy_d2d(p->c, p->c0, (size_t)p->Mc * D * 2, st));
+    HIPCHK(copy_d2d(p->c, p->c0, xc_b, st));
     if (two) {          // c, the conditioning (modulation table, prompt) and the previous forward are complete on `st`
         HIPCHK(ev_record(p->ev_fork[e->L], st));
         HIPCHK(ev_wait(ts, p->ev_fork[e->L]));
     }
     for (int i = 0; i < e->L; ++i) {
         const DoubleW& b = e->dbl[i];
+        const FTrainDbl* tb = dbl ? dbl + i : nullptr;
         const int mi = b.mod_img, mc = b.mod_ctx;     // chunks: shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp
-        CHK(ln_mod(p, ts, p->c, p->cn, mod, p->Mc, Nt, mc, mc + D));
-        CHK(qkv(p, ts, p->cn, p->Mc, Nt, 0, b.w_cqk, b.b_cqk, b.w_cv, b.b_cv, b.ncq, b.nck, qkb_c));
-        CHK(ln_mod(p, st, p->x, p->xn, mod, p->Mi, Ni, mi, mi + D));
-        CHK(qkv(p, st, p->xn, p->Mi, Ni, Nt, b.w_qk, b.b_qk, b.w_v, b.b_v, b.nq, b.nk));
+        bf16_t *xn = tb ? tb->xn : p->xn, *cn = tb ? tb->cn : p->cn;
+        bf16_t *q = tb ? tb->q : p->q, *k = tb ? tb->k : p->k, *vT = tb ? tb->vT : p->vT;
+        bf16_t *o_img = tb ? tb->o_img : p->o_img, *o_ctx = tb ? tb->o_ctx : p->o_ctx;
+        if (tb) {
+            HIPCHK(copy_d2d(tb->x_in, p->x, xi_b, st));
+            HIPCHK(copy_d2d(tb->c_in, p->c, xc_b, ts));
+        }
+        CHK(ln_mod(p, ts, p->c, cn, mod, p->Mc, Nt, mc, mc + D));
+        CHK(qkv(p, ts, cn, p->Mc, Nt, 0, b.w_cqk, b.b_cqk, b.w_cv, b.b_cv, b.ncq, b.nck, qkb_c, q, k, vT, tb ? tb->rstd_ctx : nullptr));
+        CHK(ln_mod(p, st, p->x, xn, mod, p->Mi, Ni, mi, mi + D));
+        CHK(qkv(p, st, xn, p->Mi, Ni, Nt, b.w_qk, b.b_qk, b.w_v, b.b_v, b.nq, b.nk, p->qkbuf, q, k, vT, tb ? tb->rstd_img : nullptr));
         if (two) {      // join: the attention reads the text rows of q / k / vT
             HIPCHK(ev_record(p->ev_join[i], ts));
             HIPCHK(ev_wait(st, p->ev_join[i]));
         }
-        CHK(attention(p, st, p->o_ctx, D, Nt, p->o_img, D, b.bound));
+        CHK(attention(p, st, q, k, vT, o_ctx, D, Nt, o_img, D, b.bound, tb ? tb->lse : nullptr));
         if (two) {      // fork: o_ctx is written, and the text rows of q / k / vT are free for the next block's text projections
             HIPCHK(ev_record(p->ev_fork[i], st));
             HIPCHK(ev_wait(ts, p->ev_fork[i]));
         }
-        CHK(gate_res(p, st, p->o_img, D, D, b.w_o, b.b_o, p->x, p->Mi, Ni, mod, mi + 2 * D));
-        CHK(gate_res(p, ts, p->o_ctx, D, D, b.w_co, b.b_co, p->c, p->Mc, Nt, mod, mc + 2 * D));
-        CHK(ln_mod(p, st, p->x, p->xn, mod, p->Mi, Ni, mi + 3 * D, mi + 4 * D));
-        GemmParams f1 = make_gemm(p->xn, D, b.w_ff1, D, p->Mi, F, D, EPI_BIAS_GELU, b.b_ff1, p->big, F);
+        CHK(gate_res(p, st, o_img, D, D, b.w_o, b.b_o, p->x, p->Mi, Ni, mod, mi + 2 * D));
+        CHK(gate_res(p, ts, o_ctx, D, D, b.w_co, b.b_co, p->c, p->Mc, Nt, mod, mc + 2 * D));
+        bf16_t* xn2 = tb ? tb->xn_mlp : p->xn;
+        if (tb) HIPCHK(copy_d2d(tb->x_mid, p->x, xi_b, st));
+        CHK(ln_mod(p, st, p->x, xn2, mod, p->Mi, Ni, mi + 3 * D, mi + 4 * D));
+        GemmParams f1 = make_gemm(xn2, D, b.w_ff1, D, p->Mi, F, D, EPI_BIAS_GELU, b.b_ff1, p->big, F);
+        if (tb) { f1.stash = tb->pre; f1.ld_stash = F; }
         HIPCHK(launch_gemm(f1, st));
         CHK(gate_res(p, st, p->big, F, F, b.w_ff2, b.b_ff2, p->x, p->Mi, Ni, mod, mi + 5 * D));
-        CHK(ln_mod(p, ts, p->c, p->cn, mod, p->Mc, Nt, mc + 3 * D, mc + 4 * D));
-        GemmParams c1 = make_gemm(p->cn, D, b.w_cff1, D, p->Mc, F, D, EPI_BIAS_GELU, b.b_cff1, big_c, F);
+        bf16_t* cn2 = tb ? tb->cn_mlp : p->cn;
+        if (tb) HIPCHK(copy_d2d(tb->c_mid, p->c, xc_b, ts));
+        CHK(ln_mod(p, ts, p->c, cn2, mod, p->Mc, Nt, mc + 3 * D, mc + 4 * D));
+        GemmParams c1 = make_gemm(cn2, D, b.w_cff1, D, p->Mc, F, D, EPI_BIAS_GELU, b.b_cff1, big_c, F);
+        if (tb) { c1.stash = tb->cpre; c1.ld_stash = F; }
         HIPCHK(launch_gemm(c1, ts));
         CHK(gate_res(p, ts, big_c, F, F, b.w_cff2, b.b_cff2, p->c, p->Mc, Nt, mod, mc + 5 * D));
     }
@@ -482,12 +517,22 @@ int forward_core(mi355_flux_plan* p, hipStream_t st, const void* latents, int la
                             hipMemcpyDeviceToDevice, st));
     for (int i = 0; i < e->LS; ++i) {
         const SingleW& b = e->sgl[i];
+        const FTrainSgl* tb = sgl ? sgl + i : nullptr;
         const int m0 = b.mod;                          // chunks: shift, scale, gate
-        CHK(ln_mod(p, st, p->y, p->yn, mod, p->M, S, m0, m0 + D));
-        CHK(qkv(p, st, p->yn, p->M, S, 0, b.w_qk, b.b_qk, b.w_v, b.b_v, b.nq, b.nk));
-        GemmParams gm = make_gemm(p->yn, D, b.w_mlp, D, p->M, F, D, EPI_BIAS_GELU, b.b_mlp, p->big + D, D + F);
+        bf16_t* yn = tb ? tb->yn : p->yn;
+        bf16_t *q = tb ? tb->q : p->q, *k = tb ? tb->k : p->k, *vT = tb ? tb->vT : p->vT;
+        if (tb) HIPCHK(copy_d2d(tb->y_in, p->y, y_b, st));
+        CHK(ln_mod(p, st, p->y, yn, mod, p->M, S, m0, m0 + D));
+        CHK(qkv(p, st, yn, p->M, S, 0, b.w_qk, b.b_qk, b.w_v, b.b_v, b.nq, b.nk, p->qkbuf, q, k, vT, tb ? tb->rstd : nullptr));
+        GemmParams gm = make_gemm(yn, D, b.w_mlp, D, p->M, F, D, EPI_BIAS_GELU, b.b_mlp, p->big + D, D + F);
+        if (tb) { gm.stash = tb->pre; gm.ld_stash = F; }
         HIPCHK(launch_gemm(gm, st));
-        CHK(attention(p, st, p->big, D + F, S, p->big, D + F, b.bound));
+        CHK(attention(p, st, q, k, vT, p->big, D + F, S, p->big, D + F, b.bound, tb ? tb->lse : nullptr));
+        if (tb) {       // the attention half of the concat buffer
+            if (sched_trace_on())
+                sched_trace_launch("copy2d.big->o", st, {tregs(p->big, rowb, (size_t)(D + F) * 2, (size_t)p->M)}, {treg(tb->o, (size_t)p->M * rowb)});
+            HIPCHK(hipMemcpy2DAsync(tb->o, rowb, p->big, (size_t)(D + F) * 2, rowb, (size_t)p->M, hipMemcpyDeviceToDevice, st));
+        }
         CHK(gate_res(p, st, p->big, D + F, D + F, b.w_out, b.b_out, p->y, p->M, S, mod, m0 + 2 * D));
     }
     // image rows back to a contiguous stream, AdaLayerNormContinuous (scale first), proj_out
@@ -495,6 +540,7 @@ int forward_core(mi355_flux_plan* p, hipStream_t st, const void* latents, int la
         sched_trace_launch("copy2d.y->x", st, {tregs(p->y + (size_t)Nt * D, (size_t)Ni * rowb, (size_t)S * rowb, (size_t)p->B)}, {treg(p->x, (size_t)p->B * Ni * rowb)});
     HIPCHK(hipMemcpy2DAsync(p->x, (size_t)Ni * rowb, p->y + (size_t)Nt * D, (size_t)S * rowb, (size_t)Ni * rowb, p->B,
                             hipMemcpyDeviceToDevice, st));
+    if (x_final) HIPCHK(copy_d2d(x_final, p->x, xi_b, st));
     CHK(ln_mod(p, st, p->x, p->xn, mod, p->Mi, Ni, e->mod_out + D, e->mod_out));
     GemmParams go = make_gemm(p->xn, D, e->w_proj, D, p->Mi, C, D, EPI_BIAS, e->b_proj, v_out, C);
     HIPCHK(launch_gemm(go, st));

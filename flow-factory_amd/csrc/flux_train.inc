@@ -2,10 +2,7 @@
 // reference src/flow_factory/trainers/grpo.py:263 (`adapter.forward` WITH autograd), :326-330 (backward) over
 // models/flux/flux1.py:294-346).  Textually included at the end of flux_engine.hip (shares its engine / plan structs and launch helpers).
 //
-//   mi355_flux_forward_train : the launch sequence of mi355_flux_forward / forward_core -- same kernels, same epilogues, the same binaries
-//                              (the training-only outputs are runtime branches: attention log-sum-exp, q / k 1/rms, MLP pre-activation) --
-//                              writing every block's activations into the block's own buffers: the velocity is bit-identical to the no-grad
-//                              forward's, so the replay log-prob equals the rollout's and ratio == 1 before any update;
+//   mi355_flux_forward_train : mi355_flux_forward on flux_engine.hip's forward_core with the plan's training stash (see there);
 //   mi355_flux_backward      : d loss / d weights from d loss / d v (the scheduler step's adjoint is mi355_sde_step_bwd, one op for all families).
 //
 // Gradient scope: weights and biases of every linear layer INSIDE the transformer blocks --
@@ -26,17 +23,6 @@
 // rows first in the joint sequence, and an MLP on both streams.  Weight gradients: dW = dY^T . X as split-K GEMMs on transposed operands, bias
 // gradients as column sums taken by the dY transpose (the machinery of engine_train.inc).
 
-struct FTrainDbl {
-    bf16_t *x_in, *xn, *x_mid, *xn_mlp, *pre, *o_img;
-    bf16_t *c_in, *cn, *c_mid, *cn_mlp, *cpre, *o_ctx;
-    bf16_t *q, *k, *vT;
-    float *lse, *rstd_img, *rstd_ctx;
-};
-struct FTrainSgl {
-    bf16_t *y_in, *yn, *pre, *o;
-    bf16_t *q, *k, *vT;
-    float *lse, *rstd;
-};
 struct FDblWT { bf16_t *qkv, *o, *cqkv, *co, *ff1, *ff2, *cff1, *cff2; };   // transposed weights (dgrad operands)
 struct FSglWT { bf16_t *cat, *out; };                                       // [D][3D + F] = [W_q; W_k; W_v; W_mlp]^T and [D + F][D] = W_out^T
 
@@ -226,127 +212,7 @@ static int flux_train_of(mi355_flux_plan* p, mi355_flux_train** out) {
     return 0;
 }
 
-// ---- training-mode forward: forward_core with per-block buffers ---------------------------------------------------
-// q|k projection -> RMSNorm + RoPE + scatter (with the 1/rms side output); V^T projection with the scatter fused -- `qkv` of forward_core
-static int qkv_train(mi355_flux_plan* p, hipStream_t st, const bf16_t* xin, int M, int rps, int s_off, const bf16_t* w_qk, const float* b_qk,
-                     const bf16_t* w_v, const float* b_v, const float* nq, const float* nk, bf16_t* q, bf16_t* k, bf16_t* vT, float* rstd,
-                     bf16_t* qkb = nullptr) {
-    mi355_flux* e = p->e;
-    const int D = e->D;
-    if (!qkb) qkb = p->qkbuf;
-    GemmParams g = make_gemm(xin, D, w_qk, D, M, 2 * D, D, EPI_BIAS, b_qk, qkb, 2 * D);
-    HIPCHK(launch_gemm(g, st));
-    RopeNormParams r;
-    memset(&r, 0, sizeof(r));
-    r.src = qkb; r.src_ld = 2 * D; r.q_col = 0; r.k_col = D; r.nw_q = nq; r.nw_k = nk; r.cs = p->cs;
-    r.q_out = q; r.k_out = k; r.M = M; r.H = e->H; r.rows_per_sample = rps; r.s_off = s_off; r.S_pad = p->S_pad;
-    r.eps = e->cfg.eps; r.q_scale = 0.08838834764831845f * 1.4426950408889634f;
-    r.rstd_out = rstd;
-    HIPCHK(launch_rope_norm(r, st));
-    GemmParams gv = make_gemm(w_v, D, xin, D, D, M, D, EPI_VT, b_v, nullptr, 0);
-    gv.q = vT; gv.H = e->H; gv.S_pad = p->S_pad; gv.s_off = s_off; gv.rows_per_sample = rps; gv.hd_shift = 7;
-    HIPCHK(launch_gemm(gv, st));
-    return 0;
-}
-
-static int attention_train(mi355_flux_plan* p, hipStream_t st, const bf16_t* q, const bf16_t* k, const bf16_t* vT, bf16_t* o_first, long ld_first,
-                           int n_first, bf16_t* o_rest, long ld_rest, float bound, float* lse) {
-    Attn128Params a;
-    memset(&a, 0, sizeof(a));
-    a.q = q; a.k = k; a.vT = vT; a.o_first = o_first; a.ld_first = ld_first; a.n_first = n_first;
-    a.o_rest = o_rest; a.ld_rest = ld_rest; a.B = p->B; a.H = p->e->H; a.S = p->S; a.S_pad = p->S_pad; a.q_prescaled = 1;
-    a.score_bound = bound; a.lse = lse;
-    HIPCHK(launch_attention128(a, st));
-    return 0;
-}
-
-static int flux_forward_train(mi355_flux_plan* p, mi355_flux_train* t, hipStream_t st, const void* latents, int lat_dt, const bf16_t* mod, bf16_t* v_out) {
-    mi355_flux* e = p->e;
-    const int D = e->D, F = e->F, C = e->cfg.in_channels;
-    const int Ni = p->Ni, Nt = p->Nt, S = p->S, Mi = p->Mi, Mc = p->Mc, M = p->M;
-    const size_t xi_b = (size_t)Mi * D * 2, xc_b = (size_t)Mc * D * 2, y_b = (size_t)M * D * 2;
-    const bf16_t* lat = (const bf16_t*)latents;
-    if (lat_dt != DT_BF16) {
-        HIPCHK(launch_convert(latents, lat_dt, p->lat16, DT_BF16, (long)p->B * p->n_lat, st));
-        lat = p->lat16;
-    }
-    GemmParams gx = make_gemm(lat, C, e->w_x, C, Mi, D, C, EPI_BIAS, e->b_x, p->x, D);
-    HIPCHK(launch_gemm(gx, st));
-    HIPCHK(copy_d2d(p->c, p->c0, xc_b, st));
-    // the text chain of the double blocks on the plan's side stream, exactly as the no-grad forward_core runs it (key 14's size rule; own q|k
-    // staging / MLP-hidden buffers; join before the joint attention, fork after it): same kernels on the same values either way
-    const bool two = flux_two_stream_wanted(p) && e->L > 0;
-    hipStream_t ts = st;
-    bf16_t *qkb_c = p->qkbuf, *big_c = p->big;
-    if (two) {
-        CHK(flux_two_stream_init(p));
-        ts = p->side; qkb_c = p->qkbuf_c; big_c = p->big_c;
-        HIPCHK(ev_record(p->ev_fork[e->L], st));
-        HIPCHK(ev_wait(ts, p->ev_fork[e->L]));
-    }
-    for (int i = 0; i < e->L; ++i) {
-        const DoubleW& b = e->dbl[i];
-        FTrainDbl& k = t->dbl[i];
-        const int mi = b.mod_img, mc = b.mod_ctx;
-        HIPCHK(copy_d2d(k.x_in, p->x, xi_b, st));
-        HIPCHK(copy_d2d(k.c_in, p->c, xc_b, ts));
-        CHK(ln_mod(p, ts, p->c, k.cn, mod, Mc, Nt, mc, mc + D));
-        CHK(qkv_train(p, ts, k.cn, Mc, Nt, 0, b.w_cqk, b.b_cqk, b.w_cv, b.b_cv, b.ncq, b.nck, k.q, k.k, k.vT, k.rstd_ctx, qkb_c));
-        CHK(ln_mod(p, st, p->x, k.xn, mod, Mi, Ni, mi, mi + D));
-        CHK(qkv_train(p, st, k.xn, Mi, Ni, Nt, b.w_qk, b.b_qk, b.w_v, b.b_v, b.nq, b.nk, k.q, k.k, k.vT, k.rstd_img));
-        if (two) {
-            HIPCHK(ev_record(p->ev_join[i], ts));
-            HIPCHK(ev_wait(st, p->ev_join[i]));
-        }
-        CHK(attention_train(p, st, k.q, k.k, k.vT, k.o_ctx, D, Nt, k.o_img, D, b.bound, k.lse));
-        if (two) {
-            HIPCHK(ev_record(p->ev_fork[i], st));
-            HIPCHK(ev_wait(ts, p->ev_fork[i]));
-        }
-        CHK(gate_res(p, st, k.o_img, D, D, b.w_o, b.b_o, p->x, Mi, Ni, mod, mi + 2 * D));
-        CHK(gate_res(p, ts, k.o_ctx, D, D, b.w_co, b.b_co, p->c, Mc, Nt, mod, mc + 2 * D));
-        HIPCHK(copy_d2d(k.x_mid, p->x, xi_b, st));
-        CHK(ln_mod(p, st, p->x, k.xn_mlp, mod, Mi, Ni, mi + 3 * D, mi + 4 * D));
-        GemmParams f1 = make_gemm(k.xn_mlp, D, b.w_ff1, D, Mi, F, D, EPI_BIAS_GELU, b.b_ff1, p->big, F);
-        f1.stash = k.pre; f1.ld_stash = F;
-        HIPCHK(launch_gemm(f1, st));
-        CHK(gate_res(p, st, p->big, F, F, b.w_ff2, b.b_ff2, p->x, Mi, Ni, mod, mi + 5 * D));
-        HIPCHK(copy_d2d(k.c_mid, p->c, xc_b, ts));
-        CHK(ln_mod(p, ts, p->c, k.cn_mlp, mod, Mc, Nt, mc + 3 * D, mc + 4 * D));
-        GemmParams c1 = make_gemm(k.cn_mlp, D, b.w_cff1, D, Mc, F, D, EPI_BIAS_GELU, b.b_cff1, big_c, F);
-        c1.stash = k.cpre; c1.ld_stash = F;
-        HIPCHK(launch_gemm(c1, ts));
-        CHK(gate_res(p, ts, big_c, F, F, b.w_cff2, b.b_cff2, p->c, Mc, Nt, mod, mc + 5 * D));
-    }
-    if (two) {          // the text stream is complete before it is concatenated with the image stream
-        HIPCHK(ev_record(p->ev_join[e->L], ts));
-        HIPCHK(ev_wait(st, p->ev_join[e->L]));
-    }
-    const size_t rowb = (size_t)D * 2;
-    HIPCHK(hipMemcpy2DAsync(p->y, (size_t)S * rowb, p->c, (size_t)Nt * rowb, (size_t)Nt * rowb, p->B, hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipMemcpy2DAsync(p->y + (size_t)Nt * D, (size_t)S * rowb, p->x, (size_t)Ni * rowb, (size_t)Ni * rowb, p->B, hipMemcpyDeviceToDevice, st));
-    for (int i = 0; i < e->LS; ++i) {
-        const SingleW& b = e->sgl[i];
-        FTrainSgl& k = t->sgl[i];
-        const int m0 = b.mod;
-        HIPCHK(copy_d2d(k.y_in, p->y, y_b, st));
-        CHK(ln_mod(p, st, p->y, k.yn, mod, M, S, m0, m0 + D));
-        CHK(qkv_train(p, st, k.yn, M, S, 0, b.w_qk, b.b_qk, b.w_v, b.b_v, b.nq, b.nk, k.q, k.k, k.vT, k.rstd));
-        GemmParams gm = make_gemm(k.yn, D, b.w_mlp, D, M, F, D, EPI_BIAS_GELU, b.b_mlp, p->big + D, D + F);
-        gm.stash = k.pre; gm.ld_stash = F;
-        HIPCHK(launch_gemm(gm, st));
-        CHK(attention_train(p, st, k.q, k.k, k.vT, p->big, D + F, S, p->big, D + F, b.bound, k.lse));
-        HIPCHK(hipMemcpy2DAsync(k.o, rowb, p->big, (size_t)(D + F) * 2, rowb, (size_t)M, hipMemcpyDeviceToDevice, st));    // the attention half of the concat buffer
-        CHK(gate_res(p, st, p->big, D + F, D + F, b.w_out, b.b_out, p->y, M, S, mod, m0 + 2 * D));
-    }
-    HIPCHK(hipMemcpy2DAsync(p->x, (size_t)Ni * rowb, p->y + (size_t)Nt * D, (size_t)S * rowb, (size_t)Ni * rowb, p->B, hipMemcpyDeviceToDevice, st));
-    HIPCHK(copy_d2d(t->x_final, p->x, xi_b, st));
-    CHK(ln_mod(p, st, p->x, p->xn, mod, Mi, Ni, e->mod_out + D, e->mod_out));
-    GemmParams go = make_gemm(p->xn, D, e->w_proj, D, Mi, C, D, EPI_BIAS, e->b_proj, v_out, C);
-    HIPCHK(launch_gemm(go, st));
-    return 0;
-}
-
+// ---- training-mode forward: forward_core (flux_engine.hip) on the per-block stash ------------------------------------------------------
 // transformer only, training mode: arguments as mi355_flux_forward; the activations the backward needs stay in the plan's training stash
 // (ONE stash per plan, overwritten by every call)
 extern "C" int mi355_flux_forward_train(mi355_flux_plan* p, void* stream, const void* latents, int lat_dtype, const float* t_model,
@@ -363,7 +229,7 @@ extern "C" int mi355_flux_forward_train(mi355_flux_plan* p, void* stream, const 
     if (guidance_model) HIPCHK(copy_d2d(p->g_dev, guidance_model, (size_t)p->B * 4, st));
     CHK(prepare_prompt(p, st, prompt_embeds, pooled));
     CHK(prepare_conditioning(p, st, 1));
-    CHK(flux_forward_train(p, t, st, latents, lat_dtype, p->mod_all, (bf16_t*)v_out));
+    CHK(forward_core(p, st, latents, lat_dtype, p->mod_all, (bf16_t*)v_out, t->dbl.data(), t->sgl.data(), t->x_final));
     // this step's modulation rows: the plan's own copy may be overwritten by a no-grad forward (the KL reference pass) before the backward runs
     HIPCHK(copy_d2d(t->mod, p->mod_all, (size_t)p->B * p->e->mod_cols * 2, st));
     t->have_forward = true;
