@@ -434,8 +434,8 @@ __global__ __launch_bounds__(NWAVES * 64, 1) void attn128_bwd_dq_kernel(AttnBwdP
 }
 
 // =============================================================================================== round 6: software-pipelined passes
-// The two passes with their main loops as ONE generated asm statement each (attn_bwd128_asm.inc <- gen_attn_bwd128.py; the schedule of
-// gen_attn_bwd64.py at head_dim 128): B(h - 1) || V(h) || A(h + 1) interleaved MFMA by MFMA -- with one wave per SIMD nothing else puts the
+// The two passes with their main loops as ONE generated asm statement each (attn_bwd128_asm.inc <- gen_attn_bwd.py 128; the schedule of
+// its variant 64 at head_dim 128): B(h - 1) || V(h) || A(h + 1) interleaved MFMA by MFMA -- with one wave per SIMD nothing else puts the
 // exp / mask / pack arithmetic under matrix work.  Same arithmetic and masks in the same order per output element as the kernels above
 // (kept: mi355_tune_set(44, 0), and the A/B of tests/test_gpu_flux_backward.py): bit-identical.
 #include "attn_bwd128_asm.inc"

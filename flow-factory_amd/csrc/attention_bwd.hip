@@ -426,7 +426,7 @@ __global__ __launch_bounds__(NWAVES * 64, 2) void attn_bwd_dq_tr_kernel(AttnBwdP
 }
 
 // =============================================================================================== round 6: software-pipelined passes
-// The same two passes with their main loops as ONE hand-scheduled asm statement each (attn_bwd64_asm.inc, generated by gen_attn_bwd64.py: its
+// The same two passes with their main loops as ONE hand-scheduled asm statement each (attn_bwd64_asm.inc, generated by gen_attn_bwd.py 64: its
 // docstring has the schedule): the second products of half h - 1, the exp / scale / pack of half h and the S / dP chains of half h + 1 are
 // interleaved MFMA by MFMA, so a single wave keeps the matrix pipe fed.  Same arithmetic in the same order per output element: bit-identical to
 // the kernels above (kept: mi355_tune_set(43, 0), and the A/B of tests/test_gpu_backward.py).
@@ -584,7 +584,7 @@ __global__ __launch_bounds__(NWAVES * 64, 2) void attn_bwd_dq_pipe_kernel(AttnBw
     store_rows(dq, LN2, ob, p.dq + bh * p.S_pad * 64, qblk * QB + wave * 32, p.S, lane_e);
 }
 
-// ---- two 32-row blocks per wave, one wave per SIMD (attn_bwd64x2_asm.inc <- gen_attn_bwd64x2.py: its docstring has the why)
+// ---- two 32-row blocks per wave, one wave per SIMD (attn_bwd64x2_asm.inc <- gen_attn_bwd.py 64x2: its docstring has the why)
 #include "attn_bwd64x2_asm.inc"
 
 __global__ __launch_bounds__(NWAVES * 64, 1) void attn_bwd_dkv_pipe2_kernel(AttnBwdParams p) {

@@ -24,6 +24,7 @@ Emitted macros: A128_BODY_MULTI (n_tiles >= 3: first tile, `mid` = n_tiles - 3 l
 A128_CLOBBERS, A128_WRITE_Q(c, kk, frag), A128_READ_O(c, db, dst).
 usage: python gen_attn128_w4.py > attn128_w4_asm.inc
 """
+from asmgen import clobbers, emit, interleave, regs
 
 S_BASE, FX, FY = 32, 96, 160
 O_BASE, Q_BASE = 0, 128
@@ -153,14 +154,6 @@ def rotate_after_loads():
             f"s_add_i32 s{S_MV}, s{S_MV}, 0x4000", f"s_and_b32 s{S_MV}, s{S_MV}, 0xffff"]
 
 
-def phase(mf, fill):
-    out = []
-    for i, m in enumerate(mf):
-        out.append(m)
-        out += fill.get(i, [])
-    return out
-
-
 def merge(*dicts):
     out = {}
     for d in dicts:
@@ -261,7 +254,7 @@ def flatten(L, carry):
             out += mf
             continue
         out.append("s_waitcnt lgkmcnt(0)")          # the fragments this phase multiplies were read during the previous one
-        out += phase(mf, fill)
+        out += interleave(mf, fill)
     return out
 
 
@@ -304,14 +297,6 @@ def body_single():
     return prologue() + flatten(only, {}) + epilogue()
 
 
-def emit(name, lines):
-    print(f"#define {name} \\")
-    for ln in lines:
-        print(f'    "{ln}\\n" \\')
-    print('    ""')
-    print()
-
-
 def main():
     check_softmax()
     print("// GENERATED by gen_attn128_w4.py -- do not edit.  Key loop of attn128_w4_kernel (attention128.hip); see the generator's docstring.")
@@ -324,8 +309,7 @@ def main():
         ABL = ab
         emit(f"A128_BODY_MULTI_{name}", body_multi())
     ABL = set()
-    cl = [f'"a{i}"' for i in range(192)] + [f'"v{i}"' for i in range(S_BASE, FY + 64)] + [f'"s{i}"' for i in range(80, 90)] + ['"vcc"', '"scc"', '"memory"']
-    print("#define A128_CLOBBERS " + ", ".join(cl))
+    print("#define A128_CLOBBERS " + clobbers(*regs("a", 0, 192), *regs("v", S_BASE, FY + 64), *regs("s", 80, 90), "vcc", "scc", "memory"))
     print()
     print("#define A128_WQ_(x, r0, r1, r2, r3) asm volatile(\"v_accvgpr_write_b32 a\" #r0 \", %0\\n v_accvgpr_write_b32 a\" #r1 \", %1\\n"
           " v_accvgpr_write_b32 a\" #r2 \", %2\\n v_accvgpr_write_b32 a\" #r3 \", %3\" : : \"v\"(x[0]), \"v\"(x[1]), \"v\"(x[2]), \"v\"(x[3]))")

@@ -28,7 +28,7 @@ B = 2, 1024^2) are whole rounds of 256 x 192 tiles with a quarter less work on e
 
 usage: python gen_gemm_w4.py > gemm_w4_asm.inc      (the Makefile does this; the .inc is committed so that a build needs no Python)
 """
-import sys
+from asmgen import clobbers, emit, interleave, regs
 
 FB = 120                      # first fragment VGPR; fragments occupy v[FB : FB + 128)
 XW = 32768                    # W rows start here inside a stage
@@ -103,15 +103,6 @@ def loads(stage, nxt=False):
 def advance():
     return [f"s_add_u32 s{S_A}, s{S_A}, 128", f"s_addc_u32 s{S_A + 1}, s{S_A + 1}, 0",
             f"s_add_u32 s{S_W}, s{S_W}, 128", f"s_addc_u32 s{S_W + 1}, s{S_W + 1}, 0"]
-
-
-def interleave(mf, fillers):
-    """fillers: dict MFMA index -> list of instructions placed right behind that MFMA."""
-    out = []
-    for i, m in enumerate(mf):
-        out.append(m)
-        out.extend(fillers.get(i, []))
-    return out
 
 
 # Schedules: where the fillers sit (index = MFMA of the half they follow).
@@ -221,14 +212,6 @@ def main_loop(abl={}):
     return L
 
 
-def emit(name, lines):
-    print(f"#define {name} \\")
-    for ln in lines:
-        print(f'    "{ln}\\n" \\')
-    print('    ""')
-    print()
-
-
 W4 = Tile("w4", 8, 8, 8, 8, 65536, 32, SCHED["s0"]["read"], SCHED["s0"]["m0"], SCHED["s0"]["ld"], 33)
 # 48 MFMAs per half: 16 reads behind MFMAs 0, 2, ..., 30; the 14 (M0 set-up, LDS-DMA) pairs behind 3j + 1 / 3j + 2 (last: 41); base advance from 40
 W6 = Tile("w6", 4, 12, 8, 6, 57344, 16, [2 * j for j in range(16)], [3 * j + 1 for j in range(14)], [3 * j + 2 for j in range(14)], 40)
@@ -247,8 +230,7 @@ def main():
     emit("W4_LOOP_ASM_S3", main_loop({"sched": "s3"}))
     T = W6
     emit("W6_LOOP_ASM", main_loop())
-    cl = [f'"a{i}"' for i in range(256)] + [f'"v{i}"' for i in range(FB, FB + 128)] + [f'"s{i}"' for i in range(80, 92)] + ['"scc"', '"memory"']
-    print("#define W4_CLOBBERS " + ", ".join(cl))
+    print("#define W4_CLOBBERS " + clobbers(*regs("a", 0, 256), *regs("v", FB, FB + 128), *regs("s", 80, 92), "scc", "memory"))
     print()
     # accumulator read-out: W4_READ_CHUNK_q_c(a2) fills f32x4 a2[2][4] with the 32 x 64 chunk (row quarter q, column half c) of the wave tile
     print("#define W4_READ_ACC_(d, r0, r1, r2, r3) { float t0_, t1_, t2_, t3_; asm volatile(\"v_accvgpr_read_b32 %0, a\" #r0 \"\\n v_accvgpr_read_b32 %1, a\" #r1 \"\\n"

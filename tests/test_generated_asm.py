@@ -1,5 +1,5 @@
 """The hand-scheduled main loops are GENERATED text (csrc/gen_gemm_w4.py -> gemm_w4_asm.inc, csrc/gen_attn128_w4.py -> attn128_w4_asm.inc,
-csrc/gen_attn_bwd64.py -> attn_bwd64_asm.inc, csrc/gen_attn_bwd128.py -> attn_bwd128_asm.inc;
+csrc/gen_attn_bwd.py 64 | 64x2 | 128 -> attn_bwd64_asm.inc, attn_bwd64x2_asm.inc, attn_bwd128_asm.inc; csrc/asmgen.py is what they share;
 the Makefile regenerates them when a generator changes).  The committed .inc files must be exactly what the committed generators emit, and
 the generators' own structural checks (register budgets, the in-place P compaction of the attention softmax) must hold."""
 import os
@@ -12,10 +12,11 @@ CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
 
 
 @pytest.mark.parametrize("gen,inc", [("gen_gemm_w4.py", "gemm_w4_asm.inc"), ("gen_attn128_w4.py", "attn128_w4_asm.inc"),
-                                     ("gen_attn_bwd64.py", "attn_bwd64_asm.inc"), ("gen_attn_bwd128.py", "attn_bwd128_asm.inc"),
-                                     ("gen_attn_bwd64x2.py", "attn_bwd64x2_asm.inc")])
+                                     ("gen_attn_bwd.py 64", "attn_bwd64_asm.inc"), ("gen_attn_bwd.py 128", "attn_bwd128_asm.inc"),
+                                     ("gen_attn_bwd.py 64x2", "attn_bwd64x2_asm.inc")])
 def test_committed_inc_is_what_the_generator_emits(gen, inc):
-    out = subprocess.run([sys.executable, os.path.join(CSRC, gen)], capture_output=True, text=True, check=True).stdout
+    script, *args = gen.split()
+    out = subprocess.run([sys.executable, os.path.join(CSRC, script), *args], capture_output=True, text=True, check=True).stdout
     assert out == open(os.path.join(CSRC, inc)).read(), f"{inc} is stale: run `make -C flow-factory_amd/csrc {inc}`"
 
 

@@ -63,7 +63,7 @@ def test_attention_backward_matches_autograd(gpu, B, H, S):
     dq, dk, dv = torch.zeros_like(q), torch.zeros_like(q), torch.zeros_like(q)
     _lib.check(lib.mi355_op_attention_fwd_bwd(_stream(), _ptr(q), _ptr(k), _ptr(vT), _ptr(do), _ptr(o), _ptr(dq), _ptr(dk), _ptr(dv),
                                               B, H, S, S_pad), "op_attention_fwd_bwd")
-    # round 6: the shipped passes are the software-pipelined ones (csrc/gen_attn_bwd64.py; 1 .. 70 tiles here: prologue-only, every ring-slot
+    # round 6: the shipped passes are the software-pipelined ones (csrc/gen_attn_bwd.py 64; 1 .. 70 tiles here: prologue-only, every ring-slot
     # wrap, ragged last tiles).  Same MFMAs in the same order per output element as the round-3 kernels (mi355_tune_set(43, 0)): the same bits,
     # run after run.
     try:
@@ -75,7 +75,7 @@ def test_attention_backward_matches_autograd(gpu, B, H, S):
         lib.mi355_tune_set(43, 1)
     for name, a, b in (("dq", dq, dq0), ("dk", dk, dk0), ("dv", dv, dv0)):
         assert torch.equal(a, b), (name, float((a.float() - b.float()).abs().max()))
-    # the two-row-block form (csrc/gen_attn_bwd64x2.py: 64 keys / queries per wave, one wave per SIMD; mi355_tune_set(43, 6)): the same bits again
+    # the two-row-block form (csrc/gen_attn_bwd.py 64x2: 64 keys / queries per wave, one wave per SIMD; mi355_tune_set(43, 6)): the same bits again
     try:
         _lib.check(lib.mi355_tune_set(43, 6))
         dq2, dk2, dv2 = torch.zeros_like(q), torch.zeros_like(q), torch.zeros_like(q)

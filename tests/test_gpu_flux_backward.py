@@ -63,7 +63,7 @@ def test_attention128_backward_matches_autograd(gpu, B, H, S, static):
     try:
         _lib.check(lib.mi355_op_attention128_fwd_bwd(_stream(), _ptr(q), _ptr(k), _ptr(vT), _ptr(do), _ptr(o), _ptr(dq), _ptr(dk), _ptr(dv),
                                                      B, H, S, S_pad), "op_attention128_fwd_bwd")
-        # round 6: the shipped passes are the software-pipelined ones (csrc/gen_attn_bwd128.py; 1 .. 72 tiles here: prologue-only, every ring-slot
+        # round 6: the shipped passes are the software-pipelined ones (csrc/gen_attn_bwd.py 128; 1 .. 72 tiles here: prologue-only, every ring-slot
         # wrap, ragged tails).  Same MFMAs / masks in the same order per output element as the round-4 kernels (mi355_tune_set(44, 0)): same bits.
         _lib.check(lib.mi355_tune_set(44, 0))
         dq0, dk0, dv0 = torch.zeros_like(q), torch.zeros_like(q), torch.zeros_like(q)
