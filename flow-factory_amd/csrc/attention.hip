@@ -22,20 +22,11 @@
 namespace mi355 {
 namespace {
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
 constexpr int KV = 64;          // keys per tile
 constexpr int QW = 32;          // queries per wave
 constexpr int TILE_BYTES = KV * 64 * 2;          // 8 KiB (K tile, and V^T tile)
 constexpr int STAGE_BYTES = 2 * TILE_BYTES;      // K + V^T
 constexpr float SCALE_LOG2E = 0.125f * 1.4426950408889634f;
-
-// MFMA output row i (0..31) -> key offset inside the 32-key block
-__device__ __forceinline__ int key_perm(int i) {
-    const int a = i >> 3, g = (i >> 2) & 1, b = i & 3;
-    return 16 * (a >> 1) + 8 * g + 4 * (a & 1) + b;
-}
 
 int g_attn_variant = 1;
 
@@ -68,12 +59,7 @@ __global__ __launch_bounds__(NWAVE * 64, 4) void attn_kernel(AttnParams p) {
     // XCD-aware work order: workgroup id w runs on XCD (w % 8); give each XCD a contiguous range of
     // (batch, head, q-block) so that the q-blocks sharing one (b, h)'s K / V^T hit the same private L2.
     const int nqb = (p.S + QB - 1) / QB;
-    const int nwg = nqb * p.H * p.B;
-    int wid = blockIdx.x;
-    {
-        const int q8 = nwg >> 3, r8 = nwg & 7, xcd = wid & 7;
-        wid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (wid >> 3);
-    }
+    const int wid = xcd_remap(blockIdx.x, nqb * p.H * p.B);
     const int qblk = wid % nqb;
     const int bhi = wid / nqb;
     const int h = bhi % p.H, b = bhi / p.H;
@@ -123,7 +109,7 @@ __global__ __launch_bounds__(NWAVE * 64, 4) void attn_kernel(AttnParams p) {
 
     // ---- fragment read offsets
     // K (A operand of S^T): row = 32*kb + pi(lq), chunk = 2*kk + lg
-    const int krow = key_perm(lq);
+    const int krow = row_perm(lq);
     int offK[4];
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) offK[kk] = krow * 128 + (((2 * kk + lg) ^ ((krow >> 1) & 7)) << 4);

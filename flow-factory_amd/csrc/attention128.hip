@@ -12,9 +12,6 @@
 namespace mi355 {
 namespace {
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
 constexpr int HD = 128;
 constexpr int KV = 64;                          // keys per tile
 constexpr int QW = 32;                          // queries per wave
@@ -23,11 +20,6 @@ constexpr int K_BYTES = 2 * SUB_BYTES;          // K tile: d halves
 constexpr int V_BYTES = HD * KV * 2;            // V^T tile: 128 rows (d) x 64 keys
 constexpr int STAGE_BYTES = K_BYTES + V_BYTES;  // 32 KiB
 constexpr float SCALE_LOG2E = 0.08838834764831845f * 1.4426950408889634f;   // 1/sqrt(128) * log2(e)
-
-__device__ __forceinline__ int key_perm(int i) {
-    const int a = i >> 3, g = (i >> 2) & 1, b = i & 3;
-    return 16 * (a >> 1) + 8 * g + 4 * (a & 1) + b;
-}
 
 // STATIC: |score| <= p.score_bound <= 60 proven by the caller (see attention.hip): no running max, no rescale.
 template <int NWAVE, bool STATIC = false>
@@ -40,12 +32,7 @@ __global__ __launch_bounds__(NWAVE * 64, 2) void attn128_kernel(Attn128Params p)
     const int lq = lane & 31, lg = lane >> 5;
     // XCD-aware work order (blockIdx % 8 = XCD): the q-blocks of one (b, h) share an L2
     const int nqb = (p.S + QB - 1) / QB;
-    const int nwg = nqb * p.H * p.B;
-    int wid = blockIdx.x;
-    {
-        const int q8 = nwg >> 3, r8 = nwg & 7, xcd = wid & 7;
-        wid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (wid >> 3);
-    }
+    const int wid = xcd_remap(blockIdx.x, nqb * p.H * p.B);
     const int qblk = wid % nqb;
     const int bhi = wid / nqb;
     const int h = bhi % p.H, b = bhi / p.H;
@@ -104,7 +91,7 @@ __global__ __launch_bounds__(NWAVE * 64, 2) void attn128_kernel(Attn128Params p)
     };
 
     // ---- fragment read offsets
-    const int krow = key_perm(lq);
+    const int krow = row_perm(lq);
     int offK[4];
 #pragma unroll
     for (int k4 = 0; k4 < 4; ++k4) offK[k4] = krow * 128 + (((2 * k4 + lg) ^ ((krow >> 1) & 7)) << 4);
@@ -255,12 +242,7 @@ __global__ __launch_bounds__(256) void attn128_w4_kernel(Attn128Params p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lq = lane & 31, lg = lane >> 5;
     const int nqb = (p.S + QB - 1) / QB;
-    const int nwg = nqb * p.H * p.B;
-    int wid = blockIdx.x;
-    {
-        const int q8 = nwg >> 3, r8 = nwg & 7, xcd = wid & 7;
-        wid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (wid >> 3);
-    }
+    const int wid = xcd_remap(blockIdx.x, nqb * p.H * p.B);
     const int qblk = wid % nqb;
     const int bhi = wid / nqb;
     const int h = bhi % p.H, b = bhi / p.H;
@@ -311,7 +293,7 @@ __global__ __launch_bounds__(256) void attn128_w4_kernel(Attn128Params p) {
 #undef A128_LOADQ
     }
     // ---- fragment read bases (lane part; stage and block offsets are immediates / rotated inside the loop)
-    const int krow = key_perm(lq);
+    const int krow = row_perm(lq);
     unsigned vk0, vk1, vk2, vk3, vc0, vc1, vc2, vc3, vp0 = 0, vp1 = 0, vp2 = 0, vp3 = 0;
     {
         unsigned t[4], u[4];

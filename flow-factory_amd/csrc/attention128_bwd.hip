@@ -19,96 +19,17 @@
 // Also here: the prep kernel (dO head-major, Delta, -L | -Delta per tile) for token-major o / dO with leading dimensions (the single-stream
 // blocks keep the attention output inside the [M][5D] concat buffer), and the backward of the q | k producer (per-head RMSNorm + RoPE,
 // flux_ops.hip rope_norm_kernel) gathered to token-major [dq_pre | dk_pre | dv] rows.
-#include "kernels.h"
+#include "attn_bwd_common.h"
 
 namespace mi355 {
 namespace {
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
 constexpr int HD = 128;
-constexpr int TB = 64;                     // rows of the streamed dimension per tile
-constexpr int SUB = TB * 64 * 2;           // one [64][64] bf16 sub-tile: 8 KiB
-constexpr int TILE = 2 * SUB;              // one [64][128] operand tile: 16 KiB
-constexpr int NWAVES = 4;
-constexpr float LN2 = 0.6931471805599453f;
-
-__device__ __forceinline__ int row_perm(int i) {     // MFMA output row i (0..31) -> row offset inside the 32-row block (attention.hip key_perm)
-    const int a = i >> 3, g = (i >> 2) & 1, b = i & 3;
-    return 16 * (a >> 1) + 8 * g + 4 * (a & 1) + b;
-}
-__device__ __forceinline__ int swz2(int row) {       // attention_bwd.hip: conflict-free for ds_read_b128 AND for the transposed 4-row reads
-    const int f = (row >> 1) & 7;
-    return f ^ ((f & 1) << 2);
-}
-__device__ __forceinline__ bf16x8 frag4(unsigned a, unsigned b, unsigned c, unsigned d) {
-    typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-    const u32x4 u = {a, b, c, d};
-    return __builtin_bit_cast(bf16x8, u);
-}
-
-// one [64 rows][64 d] sub-tile of a row-major [.][128] operand -> LDS (8 KiB, 128-byte rows, chunks XOR-swizzled by swz2(row))
-__device__ __forceinline__ void stage_sub(const bf16_t* src, char* dst, int wave, int lane) {
-#pragma unroll
-    for (int i = 0; i < 8 / NWAVES; ++i) {
-        const int grp = wave + i * NWAVES;
-        const int row = grp * 8 + (lane >> 3);
-        const int c = (lane & 7) ^ swz2(row);
-        __builtin_amdgcn_global_load_lds((gptr_t)(src + (long)row * HD + c * 8), (lptr_t)(dst + grp * 1024), 16, 0, 0);
-    }
-}
-
-// `ahead` tiles were issued after the one about to be read, PER VM operations each (vmcnt retires in order), then the workgroup barrier
-template <int PER>
-__device__ __forceinline__ void wait_tiles_ahead(int ahead) {
-    static_assert(PER == 8 || PER == 9, "per-tile VM operation count");
-    if (PER == 9) {
-        if (ahead >= 2) asm volatile("s_waitcnt vmcnt(18)" ::: "memory");
-        else if (ahead == 1) asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    } else {
-        if (ahead >= 2) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-        else if (ahead == 1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-}
-
-// accumulators acc[db][r] = X^T[d = 32 db + 8 (r>>2) + 4 lg + (r&3)][column = lane & 31] -> rows dst[(row0 + column)][0..128) bf16, scaled
-// (wave-private 8 KiB of LDS: 32 rows x 256 B, 16-byte chunks XOR-swizzled by row & 7 -- attention128.hip's output staging)
-__device__ __forceinline__ void store_rows128(const f32x16 (&acc)[4], float scale, char* ob, bf16_t* dst, int row0, int row_limit, int lane) {
-    const int lq = lane & 31, lg = lane >> 5;
-#pragma unroll
-    for (int db = 0; db < 4; ++db)
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-            const int d0 = 32 * db + 8 * a + 4 * lg;
-            uint2 w = {pack_bf16(acc[db][4 * a] * scale, acc[db][4 * a + 1] * scale),
-                       pack_bf16(acc[db][4 * a + 2] * scale, acc[db][4 * a + 3] * scale)};
-            const int chunk = (d0 >> 3) ^ (lq & 7);
-            *(uint2*)(ob + lq * 256 + chunk * 16 + (d0 & 7) * 2) = w;
-        }
-    __builtin_amdgcn_wave_barrier();      // wave-private region, in-order LDS
-#pragma unroll
-    for (int it = 0; it < 8; ++it) {
-        const int r = it * 4 + (lane >> 4), c = lane & 15;
-        const uint4 val = *(const uint4*)(ob + r * 256 + ((c ^ (r & 7)) << 4));
-        if (row0 + r < row_limit) *(uint4*)(dst + (long)(row0 + r) * HD + c * 8) = val;
-    }
-    __builtin_amdgcn_wave_barrier();
-}
+constexpr int TILE = tile_bytes<HD>;       // one [64][128] operand tile: two sub-tiles, 16 KiB
 
 // The transposed reads and the MFMAs they feed: one inline-assembly block per (32-row half tile, d half), fragments in FIXED registers
-// (attention_bwd.hip explains why: hipcc guards C-level LDS reads with vmcnt(0) while LDS-DMA is in flight, and a fragment is two 64-bit reads
-// into the halves of one operand tuple).  Accumulators are AGPR operands ("+a").  Per-lane addresses a0..a3 = pieces (db, jj) = (0,0), (0,1),
+// (attn_bwd_common.h explains why).  Accumulators are AGPR operands ("+a").  Per-lane addresses a0..a3 = pieces (db, jj) = (0,0), (0,1),
 // (1,0), (1,1) of the 16-row block; the immediates select (operand tile, d half, 16-row step).
-#define TR_RD(dst, a, off) "ds_read_b64_tr_b16 " dst ", " a " offset:" #off "\n\t"
-#define MFMA32(acc, afrag, b) "v_mfma_f32_32x32x16_bf16 " acc ", " afrag ", " b ", " acc "\n\t"
-#define TR_CLOBBER16 "v224", "v225", "v226", "v227", "v228", "v229", "v230", "v231", "v232", "v233", "v234", "v235", "v236", "v237", "v238", "v239"
-#define TR_CLOBBER32 TR_CLOBBER16, "v240", "v241", "v242", "v243", "v244", "v245", "v246", "v247", "v248", "v249", "v250", "v251", "v252", "v253", "v254", "v255"
 
 // dV^T[2 blocks] += dO^T . P, dK^T[2 blocks] += Q^T . dZ over the half tile's 32 queries (two k-steps of 16): OO0 / OQ0 = byte offsets of the
 // dO / Q sub-tile (k-step 0), OO1 / OQ1 = the same + 2048 (16 rows)
@@ -156,80 +77,52 @@ __device__ __forceinline__ void store_rows128(const f32x16 (&acc)[4], float scal
 #define MFMA_DRAIN() asm volatile("s_nop 15\n\ts_nop 3" ::: "memory")
 
 // ---- pass 1: dK, dV.  LDS stage: Q [2 subs][64 q][64 d] | dO [2 subs][64 q][64 d] | -L[64] | -Delta[64]; ring of 4 (130 KiB)
-constexpr int ST1 = 2 * TILE + 512;
-constexpr int NST1 = 4;
+constexpr int ST1 = slot_bytes<HD, true>;
+constexpr int NST1 = NSTAGE;
 __global__ __launch_bounds__(NWAVES * 64, 1) void attn128_bwd_dkv_kernel(AttnBwdParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lk = lane & 31, lg = lane >> 5;
     constexpr int KB = 32 * NWAVES;
-    const int Sk = p.S_kv > 0 ? p.S_kv : p.S;                       // keys: the queries' own sequence, or another one (cross-attention)
-    const long Skp = p.S_kv > 0 ? p.S_kv_pad : p.S_pad;
+    const int Sk = key_count(p);
+    const long Skp = key_rows_pad(p);
     const int nkb = (Sk + KB - 1) / KB;
-    const int nwg = nkb * p.H * p.B;
-    int wid = blockIdx.x;
-    {   // XCD-aware work order: the key blocks of one (b, h) share an L2
-        const int q8 = nwg >> 3, r8 = nwg & 7, xcd = wid & 7;
-        wid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (wid >> 3);
-    }
+    const int wid = xcd_remap(blockIdx.x, nkb * p.H * p.B);
     const int kblk = wid % nkb;
     const long bh = wid / nkb;
     const bf16_t* Qg = p.q + bh * p.S_pad * HD;
     const bf16_t* Og = p.doh + bh * p.S_pad * HD;
-    // -L | -Delta of a 64-query tile: 128 contiguous floats in p.nld ([b h][tile][2][64]); wave w moves floats 32 w .. 32 w + 31 with the
-    // first 8 lanes of one 16-byte LDS-DMA instruction (every wave: 9 VM operations per tile)
-    const float* NLg = p.nld + bh * p.S_pad * 2 + wave * 32 + (lane & 7) * 4;
+    const float* NLg = p.nld + bh * p.S_pad * 2 + wave * 32 + (lane & 7) * 4;      // this lane's 16 bytes of tile 0's -L | -Delta
     const int key = kblk * KB + wave * 32 + lk;
     const int key_ld = key < Sk ? key : Sk - 1;
-    // ragged text (Qwen-Image): keys >= kv_len[b] are masked in the forward; their P is zero here, so their dK / dV rows come out as zeros
-    int Skv = Sk;
-    if (p.kv_len) Skv = min(Skv, max(1, __builtin_amdgcn_readfirstlane(p.kv_len[bh / p.H])));
-    const bool key_ok = key < Skv;
+    const int Skv = valid_keys(p.kv_len, bh / p.H, Sk);
+    const bool key_ok = key < Skv;      // ragged text: keys >= kv_len[b] are masked in the forward; their P is zero here, so their dK / dV rows are zeros
     bf16x8 kf[8], vf[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         kf[j] = *(const bf16x8*)(p.k + (bh * Skp + key_ld) * HD + j * 16 + lg * 8);
         vf[j] = *(const bf16x8*)(p.v + (bh * Skp + key_ld) * HD + j * 16 + lg * 8);
     }
-    auto stage = [&](int t, int buf) {
-        char* base = smem + buf * ST1;
-        const bf16_t* qs = Qg + (long)t * TB * HD;
-        const bf16_t* os = Og + (long)t * TB * HD;
-        stage_sub(qs, base, wave, lane);
-        stage_sub(qs + 64, base + SUB, wave, lane);
-        stage_sub(os, base + TILE, wave, lane);
-        stage_sub(os + 64, base + TILE + SUB, wave, lane);
-        if (lane < 8) __builtin_amdgcn_global_load_lds((gptr_t)(NLg + (long)t * 2 * TB), (lptr_t)(base + 2 * TILE + wave * 128), 16, 0, 0);
-    };
-    // row-major sub-tiles as A operand: row = 32*qb + perm(lk), logical chunk = 2*kk + lg
+    auto stage = [&](int t) { stage_slot<HD, true>(smem, t & (NST1 - 1), Qg, Og, NLg + (long)t * 2 * TB, t, wave, lane); };      // 9 VM operations per wave
     const int prow = row_perm(lk);
-    int offR[4];
+    int offR[4], trb[2][2];
 #pragma unroll
-    for (int kk = 0; kk < 4; ++kk) offR[kk] = prow * 128 + (((2 * kk + lg) ^ swz2(prow)) << 4);
-    // transposed reads: this lane supplies the 8-byte piece (row 8 lg + 4 jj + (i >> 2), columns 32 db + 16 g1 + 4 (i & 3) ..) of the block
-    int trb[2][2];
-    {
-        const int i = lane & 15, g1 = (lane >> 4) & 1;
+    for (int kk = 0; kk < 4; ++kk) offR[kk] = frag_offset(prow, lg, kk);
 #pragma unroll
-        for (int db = 0; db < 2; ++db)
+    for (int db = 0; db < 2; ++db)
 #pragma unroll
-            for (int jj = 0; jj < 2; ++jj) {
-                const int ql = 8 * lg + 4 * jj + (i >> 2);
-                const int ch = 4 * db + 2 * g1 + ((i & 3) >> 1);
-                trb[db][jj] = ql * 128 + ((ch ^ swz2(ql)) << 4) + (i & 1) * 8;
-            }
-    }
+        for (int jj = 0; jj < 2; ++jj) trb[db][jj] = tr_piece_offset(lane, lg, db, jj);
     f32x16 dk[4], dv[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) { dk[j] = (f32x16){0}; dv[j] = (f32x16){0}; }
     const int nt = (p.S + TB - 1) / TB;
-    stage(0, 0);
-    if (nt > 1) stage(1, 1);
-    if (nt > 2) stage(2, 2);
+    stage(0);
+    if (nt > 1) stage(1);
+    if (nt > 2) stage(2);
     for (int t = 0; t < nt; ++t) {
         wait_tiles_ahead<9>(nt - 1 - t);
-        if (t + 3 < nt) stage(t + 3, (t + 3) & (NST1 - 1));      // its buffer held tile t - 1: every wave is past it (the barrier above)
+        if (t + 3 < nt) stage(t + 3);      // its slot held tile t - 1: every wave is past it (the barrier above)
         const char* sb = smem + (t & (NST1 - 1)) * ST1;
         const unsigned stg = (unsigned)(size_t)(__attribute__((address_space(3))) char*)(smem + (t & (NST1 - 1)) * ST1);
         const unsigned sLa = stg + 2 * TILE + 32 * lg;
@@ -302,16 +195,15 @@ __global__ __launch_bounds__(NWAVES * 64, 1) void attn128_bwd_dkv_kernel(AttnBwd
             }
         }
     }
-    __syncthreads();     // every wave is done with the ring: reuse it for the output transposes (8 KiB per wave)
-    char* ob = smem + wave * 8192;
+    const OutStage o = epilogue_begin<HD, false>(smem, wave, lane);
     const int row0 = kblk * KB + wave * 32;
-    store_rows128(dk, LN2, ob, p.dk + bh * Skp * HD, row0, Sk, lane);
-    store_rows128(dv, 1.0f, ob, p.dv + bh * Skp * HD, row0, Sk, lane);
+    store_rows<HD>(dk, LN2, o, p.dk + bh * Skp * HD, row0, Sk);
+    store_rows<HD>(dv, 1.0f, o, p.dv + bh * Skp * HD, row0, Sk);
 }
 
 // ---- pass 2: dQ.  LDS stage: K [2 subs][64 keys][64 d] | V [2 subs][64 keys][64 d]; ring of 4 (128 KiB)
-constexpr int ST2 = 2 * TILE;
-constexpr int NST2 = 4;
+constexpr int ST2 = slot_bytes<HD, false>;
+constexpr int NST2 = NSTAGE;
 __global__ __launch_bounds__(NWAVES * 64, 1) void attn128_bwd_dq_kernel(AttnBwdParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -319,15 +211,10 @@ __global__ __launch_bounds__(NWAVES * 64, 1) void attn128_bwd_dq_kernel(AttnBwdP
     const int lq = lane & 31, lg = lane >> 5;
     constexpr int QB = 32 * NWAVES;
     const int nqb = (p.S + QB - 1) / QB;
-    const int nwg = nqb * p.H * p.B;
-    int wid = blockIdx.x;
-    {
-        const int q8 = nwg >> 3, r8 = nwg & 7, xcd = wid & 7;
-        wid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (wid >> 3);
-    }
+    const int wid = xcd_remap(blockIdx.x, nqb * p.H * p.B);
     const int qblk = wid % nqb;
     const long bh = wid / nqb;
-    const long Skp = p.S_kv > 0 ? p.S_kv_pad : p.S_pad;               // (cross-attention: the keys are another sequence)
+    const long Skp = key_rows_pad(p);
     const bf16_t* Kg = p.k + bh * Skp * HD;
     const bf16_t* Vg = p.v + bh * Skp * HD;
     const int q_row = qblk * QB + wave * 32 + lq;
@@ -345,43 +232,26 @@ __global__ __launch_bounds__(NWAVES * 64, 1) void attn128_bwd_dq_kernel(AttnBwdP
 #pragma unroll
         for (int r = 0; r < 16; ++r) { nL[r] = l; nD[r] = d; }
     }
-    auto stage = [&](int t, int buf) {
-        char* base = smem + buf * ST2;
-        const bf16_t* ks = Kg + (long)t * TB * HD;
-        const bf16_t* vs = Vg + (long)t * TB * HD;
-        stage_sub(ks, base, wave, lane);
-        stage_sub(ks + 64, base + SUB, wave, lane);
-        stage_sub(vs, base + TILE, wave, lane);
-        stage_sub(vs + 64, base + TILE + SUB, wave, lane);
-    };
+    auto stage = [&](int t) { stage_slot<HD, false>(smem, t % NST2, Kg, Vg, nullptr, t, wave, lane); };      // 8 VM operations per wave
     const int prow = row_perm(lq);
-    int offR[4];
+    int offR[4], trb[2][2];
 #pragma unroll
-    for (int kk = 0; kk < 4; ++kk) offR[kk] = prow * 128 + (((2 * kk + lg) ^ swz2(prow)) << 4);
-    int trb[2][2];
-    {
-        const int i = lane & 15, g1 = (lane >> 4) & 1;
+    for (int kk = 0; kk < 4; ++kk) offR[kk] = frag_offset(prow, lg, kk);
 #pragma unroll
-        for (int db = 0; db < 2; ++db)
+    for (int db = 0; db < 2; ++db)
 #pragma unroll
-            for (int jj = 0; jj < 2; ++jj) {
-                const int kl = 8 * lg + 4 * jj + (i >> 2);
-                const int ch = 4 * db + 2 * g1 + ((i & 3) >> 1);
-                trb[db][jj] = kl * 128 + ((ch ^ swz2(kl)) << 4) + (i & 1) * 8;
-            }
-    }
+        for (int jj = 0; jj < 2; ++jj) trb[db][jj] = tr_piece_offset(lane, lg, db, jj);
     f32x16 dq[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) dq[j] = (f32x16){0};
-    int Skv = p.S_kv > 0 ? p.S_kv : p.S;      // ragged text: this sample's keys end at kv_len[b]
-    if (p.kv_len) Skv = min(Skv, max(1, __builtin_amdgcn_readfirstlane(p.kv_len[bh / p.H])));
+    const int Skv = valid_keys(p.kv_len, bh / p.H, key_count(p));
     const int nt = (Skv + TB - 1) / TB;
-    stage(0, 0);
-    if (nt > 1) stage(1, 1);
-    if (nt > 2) stage(2, 2);
+    stage(0);
+    if (nt > 1) stage(1);
+    if (nt > 2) stage(2);
     for (int t = 0; t < nt; ++t) {
         wait_tiles_ahead<8>(nt - 1 - t);
-        if (t + 3 < nt) stage(t + 3, (t + 3) % NST2);
+        if (t + 3 < nt) stage(t + 3);
         const char* sb = smem + (t % NST2) * ST2;
         const unsigned stg = (unsigned)(size_t)(__attribute__((address_space(3))) char*)(smem + (t % NST2) * ST2);
         const int k_lim = Skv - t * TB;
@@ -428,9 +298,8 @@ __global__ __launch_bounds__(NWAVES * 64, 1) void attn128_bwd_dq_kernel(AttnBwdP
             }
         }
     }
-    __syncthreads();
-    char* ob = smem + wave * 8192;
-    store_rows128(dq, LN2, ob, p.dq + bh * p.S_pad * HD, qblk * QB + wave * 32, p.S, lane);
+    const OutStage o = epilogue_begin<HD, false>(smem, wave, lane);
+    store_rows<HD>(dq, LN2, o, p.dq + bh * p.S_pad * HD, qblk * QB + wave * 32, p.S);
 }
 
 // =============================================================================================== round 6: software-pipelined passes
@@ -446,61 +315,35 @@ __global__ __launch_bounds__(NWAVES * 64, 1) void attn128_bwd_dkv_pipe_kernel(At
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lk = lane & 31, lg = lane >> 5;
     constexpr int KB = 32 * NWAVES;
-    const int Sk = p.S_kv > 0 ? p.S_kv : p.S;
-    const long Skp = p.S_kv > 0 ? p.S_kv_pad : p.S_pad;
+    const int Sk = key_count(p);
+    const long Skp = key_rows_pad(p);
     const int nkb = (Sk + KB - 1) / KB;
-    const int nwg = nkb * p.H * p.B;
-    int wid = blockIdx.x;
-    {
-        const int q8 = nwg >> 3, r8 = nwg & 7, xcd = wid & 7;
-        wid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (wid >> 3);
-    }
+    const int wid = xcd_remap(blockIdx.x, nkb * p.H * p.B);
     const int kblk = wid % nkb;
     const long bh = wid / nkb;
-    if ((unsigned)(size_t)(__attribute__((address_space(3))) char*)smem != 0u) __builtin_trap();      // the asm addresses the ring from LDS byte 0
+    require_lds_base0(smem);
     const bf16_t* Qg = p.q + bh * p.S_pad * HD;
     const bf16_t* Og = p.doh + bh * p.S_pad * HD;
     const float* NLt = p.nld + bh * p.S_pad * 2;
     const int key = kblk * KB + wave * 32 + lk;
     const int key_ld = key < Sk ? key : Sk - 1;
-    int Skv = Sk;
-    if (p.kv_len) Skv = min(Skv, max(1, __builtin_amdgcn_readfirstlane(p.kv_len[bh / p.H])));
+    const int Skv = valid_keys(p.kv_len, bh / p.H, Sk);
     const int nt = (p.S + TB - 1) / TB;
-    const int srow = wave * 8 + (lane >> 3);
-    const unsigned g0 = (unsigned)(srow * 256 + (((lane & 7) ^ swz2(srow)) << 4));
-    const unsigned g2 = (unsigned)(wave * 128 + (lane & 7) * 16);
-    const unsigned grow = (unsigned)(key_ld * 256 + lg * 16);
-    auto stage = [&](int t, int buf) {                   // (tiles 0..2; the loop stages the rest)
+    const unsigned g0 = dma_src_offset<HD>(wave, lane), g2 = dma_nld_offset(wave, lane), grow = own_row_offset<HD>(key_ld, lg);
+    auto stage = [&](int t) {                            // (tiles 0..2; the loop stages the rest)
         const int tt = t < nt ? t : nt - 1;
-        char* base = smem + buf * ST1;
-        const bf16_t* qs = Qg + (long)tt * TB * HD;
-        const bf16_t* os = Og + (long)tt * TB * HD;
-        stage_sub(qs, base, wave, lane);
-        stage_sub(qs + 64, base + SUB, wave, lane);
-        stage_sub(os, base + TILE, wave, lane);
-        stage_sub(os + 64, base + TILE + SUB, wave, lane);
-        if (lane < 8) __builtin_amdgcn_global_load_lds((gptr_t)(NLt + (long)tt * 2 * TB + wave * 32 + (lane & 7) * 4), (lptr_t)(base + 2 * TILE + wave * 128), 16, 0, 0);
+        stage_slot<HD, true>(smem, t, Qg, Og, NLt + (long)tt * 2 * TB + wave * 32 + (lane & 7) * 4, tt, wave, lane);
     };
     const int prow = row_perm(lk);
-    unsigned la = (unsigned)(2 * TILE + 32 * lg), r0, a0, a1;
-    {
-        r0 = (unsigned)(prow * 128 + ((lg ^ swz2(prow)) << 4));                  // fragment kk = 0 (offR[0]); kk = 1..3: r0 ^ 32 kk, formed by the asm
-        const int i = lane & 15, g1 = (lane >> 4) & 1;
-        unsigned a[2];
+    unsigned la = nld_read_offset<HD>(lg), r0 = (unsigned)frag_offset(prow, lg, 0), a[2];
 #pragma unroll
-        for (int jj = 0; jj < 2; ++jj) {                                         // pieces (db = 0, jj) (trb[0][jj]); db = 1: ^ 64
-            const int ql = 8 * lg + 4 * jj + (i >> 2);
-            const int ch = 2 * g1 + ((i & 3) >> 1);
-            a[jj] = (unsigned)(ql * 128 + ((ch ^ swz2(ql)) << 4) + (i & 1) * 8);
-        }
-        a0 = a[0]; a1 = a[1];
-    }
+    for (int jj = 0; jj < 2; ++jj) a[jj] = (unsigned)tr_piece_offset(lane, lg, 0, jj);
+    unsigned a0 = a[0], a1 = a[1];
     // valid queries of the current tile minus this half-wave's row offset; a lane whose key is masked (beyond the sample's keys) never has any
     int vrem = key < Skv ? p.S - 8 * lg : -(1 << 30);
-    stage(0, 0); stage(1, 1); stage(2, 2);
-    const int lt = nt - 1 < 3 ? nt - 1 : 3;
-    const unsigned long long b0 = (unsigned long long)(Qg + (long)lt * TB * HD), b1 = (unsigned long long)(Og + (long)lt * TB * HD);
-    const unsigned long long b2 = (unsigned long long)(NLt + (long)lt * 2 * TB);
+    stage(0); stage(1); stage(2);
+    const int lt = first_loop_tile(nt);
+    const unsigned long long b0 = tile_addr<HD>(Qg, lt), b1 = tile_addr<HD>(Og, lt), b2 = nld_addr(NLt, lt);
     const unsigned long long p0 = (unsigned long long)(p.k + bh * Skp * HD), p1 = (unsigned long long)(p.v + bh * Skp * HD);
     asm volatile(ABWD128_DKV_ASM
                  : [la] "+v"(la), [r0] "+v"(r0), [a0] "+v"(a0), [a1] "+v"(a1), [vrem] "+v"(vrem)
@@ -516,13 +359,10 @@ __global__ __launch_bounds__(NWAVES * 64, 1) void attn128_bwd_dkv_pipe_kernel(At
 #pragma unroll
         for (int j = 0; j < 4; ++j) { dk[j] = (f32x16){0}; dv[j] = (f32x16){0}; }
     }
-    __syncthreads();     // every wave is done with the ring (the asm ends with vmcnt(0)): reuse it for the output transposes (8 KiB per wave)
-    int lane_e = lane;   // (an opaque copy: the epilogue's lane arithmetic must not be formed in front of the loop -- see attention_bwd.hip)
-    asm volatile("" : "+v"(lane_e));
-    char* ob = smem + wave * 8192;
+    const OutStage o = epilogue_begin<HD, true>(smem, wave, lane);
     const int row0 = kblk * KB + wave * 32;
-    store_rows128(dk, LN2, ob, p.dk + bh * Skp * HD, row0, Sk, lane_e);
-    store_rows128(dv, 1.0f, ob, p.dv + bh * Skp * HD, row0, Sk, lane_e);
+    store_rows<HD>(dk, LN2, o, p.dk + bh * Skp * HD, row0, Sk);
+    store_rows<HD>(dv, 1.0f, o, p.dv + bh * Skp * HD, row0, Sk);
 }
 
 __global__ __launch_bounds__(NWAVES * 64, 1) void attn128_bwd_dq_pipe_kernel(AttnBwdParams p) {
@@ -532,55 +372,29 @@ __global__ __launch_bounds__(NWAVES * 64, 1) void attn128_bwd_dq_pipe_kernel(Att
     const int lq = lane & 31, lg = lane >> 5;
     constexpr int QB = 32 * NWAVES;
     const int nqb = (p.S + QB - 1) / QB;
-    const int nwg = nqb * p.H * p.B;
-    int wid = blockIdx.x;
-    {
-        const int q8 = nwg >> 3, r8 = nwg & 7, xcd = wid & 7;
-        wid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (wid >> 3);
-    }
+    const int wid = xcd_remap(blockIdx.x, nqb * p.H * p.B);
     const int qblk = wid % nqb;
     const long bh = wid / nqb;
-    if ((unsigned)(size_t)(__attribute__((address_space(3))) char*)smem != 0u) __builtin_trap();
-    const long Skp = p.S_kv > 0 ? p.S_kv_pad : p.S_pad;
+    require_lds_base0(smem);
+    const long Skp = key_rows_pad(p);
     const bf16_t* Kg = p.k + bh * Skp * HD;
     const bf16_t* Vg = p.v + bh * Skp * HD;
     const int q_row = qblk * QB + wave * 32 + lq;
     const int q_ld = q_row < p.S ? q_row : p.S - 1;
-    int Skv = p.S_kv > 0 ? p.S_kv : p.S;      // ragged text: this sample's keys end at kv_len[b]
-    if (p.kv_len) Skv = min(Skv, max(1, __builtin_amdgcn_readfirstlane(p.kv_len[bh / p.H])));
+    const int Skv = valid_keys(p.kv_len, bh / p.H, key_count(p));
     const int nt = (Skv + TB - 1) / TB;
-    const int srow = wave * 8 + (lane >> 3);
-    const unsigned g0 = (unsigned)(srow * 256 + (((lane & 7) ^ swz2(srow)) << 4));
-    const unsigned grow = (unsigned)(q_ld * 256 + lg * 16);
+    const unsigned g0 = dma_src_offset<HD>(wave, lane), grow = own_row_offset<HD>(q_ld, lg);
     const float nl = -p.lse[bh * p.S_pad + q_ld], nd = -p.delta[bh * p.S_pad + q_ld];
-    auto stage = [&](int t, int buf) {
-        const int tt = t < nt ? t : nt - 1;
-        char* base = smem + buf * ST2;
-        const bf16_t* ks = Kg + (long)tt * TB * HD;
-        const bf16_t* vs = Vg + (long)tt * TB * HD;
-        stage_sub(ks, base, wave, lane);
-        stage_sub(ks + 64, base + SUB, wave, lane);
-        stage_sub(vs, base + TILE, wave, lane);
-        stage_sub(vs + 64, base + TILE + SUB, wave, lane);
-    };
+    auto stage = [&](int t) { stage_slot<HD, false>(smem, t, Kg, Vg, nullptr, t < nt ? t : nt - 1, wave, lane); };
     const int prow = row_perm(lq);
-    unsigned r0, a0, a1;
-    {
-        r0 = (unsigned)(prow * 128 + ((lg ^ swz2(prow)) << 4));
-        const int i = lane & 15, g1 = (lane >> 4) & 1;
-        unsigned a[2];
+    unsigned r0 = (unsigned)frag_offset(prow, lg, 0), a[2];
 #pragma unroll
-        for (int jj = 0; jj < 2; ++jj) {
-            const int kl = 8 * lg + 4 * jj + (i >> 2);
-            const int ch = 2 * g1 + ((i & 3) >> 1);
-            a[jj] = (unsigned)(kl * 128 + ((ch ^ swz2(kl)) << 4) + (i & 1) * 8);
-        }
-        a0 = a[0]; a1 = a[1];
-    }
+    for (int jj = 0; jj < 2; ++jj) a[jj] = (unsigned)tr_piece_offset(lane, lg, 0, jj);
+    unsigned a0 = a[0], a1 = a[1];
     int vrem = Skv - 8 * lg;                  // valid keys of the current tile minus this half-wave's row offset
-    stage(0, 0); stage(1, 1); stage(2, 2);
-    const int lt = nt - 1 < 3 ? nt - 1 : 3;
-    const unsigned long long b0 = (unsigned long long)(Kg + (long)lt * TB * HD), b1 = (unsigned long long)(Vg + (long)lt * TB * HD);
+    stage(0); stage(1); stage(2);
+    const int lt = first_loop_tile(nt);
+    const unsigned long long b0 = tile_addr<HD>(Kg, lt), b1 = tile_addr<HD>(Vg, lt);
     const unsigned long long p0 = (unsigned long long)(p.q + bh * p.S_pad * HD), p1 = (unsigned long long)(p.doh + bh * p.S_pad * HD);
     asm volatile(ABWD128_DQ_ASM
                  : [r0] "+v"(r0), [a0] "+v"(a0), [a1] "+v"(a1), [vrem] "+v"(vrem)
@@ -589,30 +403,8 @@ __global__ __launch_bounds__(NWAVES * 64, 1) void attn128_bwd_dq_pipe_kernel(Att
                  : ABWD128_DQ_CLOBBERS);
     f32x16 dq[4];
     ABWD128_READ_ACC_0(dq[0]) ABWD128_READ_ACC_16(dq[1]) ABWD128_READ_ACC_32(dq[2]) ABWD128_READ_ACC_48(dq[3])
-    __syncthreads();
-    int lane_e = lane;
-    asm volatile("" : "+v"(lane_e));
-    char* ob = smem + wave * 8192;
-    store_rows128(dq, LN2, ob, p.dq + bh * p.S_pad * HD, qblk * QB + wave * 32, p.S, lane_e);
-}
-
-__device__ __forceinline__ void unpack8(const uint4 u, float (&v)[8]) {
-    v[0] = bf_lo(u.x); v[1] = bf_hi(u.x); v[2] = bf_lo(u.y); v[3] = bf_hi(u.y);
-    v[4] = bf_lo(u.z); v[5] = bf_hi(u.z); v[6] = bf_lo(u.w); v[7] = bf_hi(u.w);
-}
-__device__ __forceinline__ uint4 pack8(const float (&v)[8]) {
-    return make_uint4(pack_bf16(v[0], v[1]), pack_bf16(v[2], v[3]), pack_bf16(v[4], v[5]), pack_bf16(v[6], v[7]));
-}
-__device__ __forceinline__ float row16_sum_dpp(float v) {      // sum over the 16 lanes of a DPP row, in every lane
-    auto dpp = [](float x, auto ctrl) {
-        return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), decltype(ctrl)::value, 0xf, 0xf, false));
-    };
-    using std::integral_constant;
-    v += dpp(v, integral_constant<int, 0xB1>{});      // quad_perm [1,0,3,2]
-    v += dpp(v, integral_constant<int, 0x4E>{});      // quad_perm [2,3,0,1]
-    v += dpp(v, integral_constant<int, 0x141>{});     // row_half_mirror
-    v += dpp(v, integral_constant<int, 0x140>{});     // row_mirror
-    return v;
+    const OutStage o = epilogue_begin<HD, true>(smem, wave, lane);
+    store_rows<HD>(dq, LN2, o, p.dq + bh * p.S_pad * HD, qblk * QB + wave * 32, p.S);
 }
 
 // ---- prep: token-major o / dO (split like the forward's output: the first n_first positions of a sample in one buffer, the rest in another,

@@ -16,56 +16,13 @@
 // Round 3: the transposed A operands of the second products (dO^T, Q^T, K^T) are read out of the ROW-MAJOR tiles with
 // `ds_read_b64_tr_b16` -- no transposed copies in HBM or LDS (see below).  v in [S_pad][64] comes from the forward's V^T by one HBM-bound
 // transpose (backward.hip); -L | -Delta per 64-query tile from the prep kernel.
-#include "kernels.h"
-#include <type_traits>
+#include "attn_bwd_common.h"
 
 namespace mi355 {
 namespace {
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-constexpr int TB = 64;                     // rows of the streamed dimension per tile
-constexpr int TILE = TB * 64 * 2;          // 8 KiB
-// NWAVES waves x 32 lanes-of-interest keys (pass 1) / queries (pass 2) per workgroup.  4 waves, two (three) workgroups per CU: 8-wave
-// workgroups (one per CU, half the L2 -> LDS operand traffic: every workgroup streams ALL tiles of its (b, h)) measured 4-8 % SLOWER
-// (profiles/r03u_attn_bwd_waves_ab.txt) -- independent barriers per CU overlap better than one.
-constexpr int NWAVES = 4;
-constexpr float LN2 = 0.6931471805599453f;
-
-__device__ __forceinline__ int row_perm(int i) {     // MFMA output row i (0..31) -> row offset inside the 32-row block (attention.hip key_perm)
-    const int a = i >> 3, g = (i >> 2) & 1, b = i & 3;
-    return 16 * (a >> 1) + 8 * g + 4 * (a & 1) + b;
-}
-
-// accumulators acc[db][r] = X^T[d = 32 db + 8 (r>>2) + 4 lg + (r&3)][column = lane & 31] -> rows dst[(row0 + column)][0..64) bf16, scaled
-__device__ __forceinline__ void store_rows(const f32x16 (&acc)[2], float scale, char* ob, bf16_t* dst, int row0, int row_limit, int lane) {
-    const int lq = lane & 31, lg = lane >> 5;
-#pragma unroll
-    for (int db = 0; db < 2; ++db)
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-            const int d0 = 32 * db + 8 * a + 4 * lg;
-            uint2 w = {pack_bf16(acc[db][4 * a] * scale, acc[db][4 * a + 1] * scale),
-                       pack_bf16(acc[db][4 * a + 2] * scale, acc[db][4 * a + 3] * scale)};
-            const int chunk = (d0 >> 3) ^ (lq & 7);
-            *(uint2*)(ob + lq * 128 + chunk * 16 + (d0 & 7) * 2) = w;
-        }
-    __builtin_amdgcn_wave_barrier();      // wave-private region, in-order LDS
-#pragma unroll
-    for (int it = 0; it < 4; ++it) {
-        const int r = it * 8 + (lane >> 3), c = lane & 7;
-        const uint4 val = *(const uint4*)(ob + r * 128 + ((c ^ (r & 7)) << 4));
-        if (row0 + r < row_limit) *(uint4*)(dst + (long)(row0 + r) * 64 + c * 8) = val;
-    }
-    __builtin_amdgcn_wave_barrier();
-}
-
-__device__ __forceinline__ bf16x8 frag4(unsigned a, unsigned b, unsigned c, unsigned d) {
-    typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-    const u32x4 u = {a, b, c, d};
-    return __builtin_bit_cast(bf16x8, u);
-}
+constexpr int HD = 64;
+constexpr int TILE = tile_bytes<HD>;       // 8 KiB
 
 // =============================================================================================== the two passes
 // The second product of each pass contracts over the STREAMED dimension
@@ -76,57 +33,12 @@ __device__ __forceinline__ bf16x8 frag4(unsigned a, unsigned b, unsigned c, unsi
 // tiles ahead and counted waits instead of `vmcnt(0)` per tile, and no q^T / k^T / dO^T transpose launches.  Measured inside the
 // optimize() step (profiles/r03v_attn_bwd_tr_ab.txt, joint + dual average): dK/dV pass 558 -> 492 us, dQ pass 383 -> 380 us (that pass was
 // VALU-bound: see its C-operand splats below).
-// Swizzle: physical 16-byte chunk = logical ^ swz2(row), swz2 = f ^ ((f & 1) << 2) with f = (row >> 1) & 7: still a permutation of the 8
-// even (odd) rows a ds_read_b128 lane group touches (conflict-free as before), and rows r, r + 2 of a transposed read's 4-row block now
-// sit in different 64-byte halves of their 128-byte rows (4 rows x 64 bytes = 64 distinct banks).
-typedef short v4s __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) v4s* lds_v4s_t;
-
-__device__ __forceinline__ int swz2(int row) {
-    const int f = (row >> 1) & 7;
-    return f ^ ((f & 1) << 2);
-}
-
-template <int NWAVE>
-__device__ __forceinline__ void stage_tile2(const bf16_t* src, long row_stride, char* dst, int wave, int lane) {
-#pragma unroll
-    for (int i = 0; i < 8 / NWAVE; ++i) {
-        const int grp = wave + i * NWAVE;
-        const int row = grp * 8 + (lane >> 3);
-        const int c = (lane & 7) ^ swz2(row);
-        __builtin_amdgcn_global_load_lds((gptr_t)(src + (long)row * row_stride + c * 8), (lptr_t)(dst + grp * 1024), 16, 0, 0);
-    }
-}
-
-// The transposed reads and the MFMAs they feed are one inline-assembly block per 32-row half tile, with the fragments in FIXED registers:
-//  * hipcc guards every C-level LDS read it knows to be an LDS read (the `ds_read_tr16_b64` builtin, address-space-3 pointers) with
-//    `s_waitcnt vmcnt(0)` while any LDS-DMA is in flight -- it cannot tell the ring stages apart -- which would drain the tiles just put in
-//    flight (the plain fragment reads go through generic pointers and are not guarded);
-//  * a fragment is two 64-bit reads into the halves of one 4-register MFMA operand: as separate asm outputs they would need packing moves.
-// Per-lane addresses a0..a3 = piece (db, jj) = (0,0), (0,1), (1,0), (1,1) of the 16-row block at the tile's row 32 half (+ hs * 2048 bytes).
-// LDS returns in order, so `lgkmcnt(n)` retires all but the last n reads (compiler-issued fragment reads in flight only make it wait longer).
-#define TR_RD(dst, a, off) "ds_read_b64_tr_b16 " dst ", " a " offset:" #off "\n\t"
-#define MFMA32(acc, afrag, b) "v_mfma_f32_32x32x16_bf16 " acc ", " afrag ", " b ", " acc "\n\t"
-
-__device__ __forceinline__ void wait_tiles_ahead(int ahead, int per_tile) {
-    // `ahead` tiles were issued after the one about to be read, `per_tile` VM operations each (vmcnt retires in order)
-    if (per_tile == 5) {
-        if (ahead >= 2) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-        else if (ahead == 1) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    } else {
-        if (ahead >= 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        else if (ahead == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-}
+// The tile layout, the swizzle, the lane addresses and the inline-assembly form of the transposed reads: attn_bwd_common.h.  Below, per-lane
+// addresses a0..a3 = piece (db, jj) = (0,0), (0,1), (1,0), (1,1) of the 16-row block at the tile's row 32 half (+ hs * 2048 bytes).
 
 // ---- pass 1: dK, dV.  LDS stage: Q [64 q][64 d] | dO [64 q][64 d] | -L[64] | -Delta[64]; ring of 4
-constexpr int ST1T = 2 * TILE + 512;
-constexpr int NST1 = 4;
+constexpr int ST1T = slot_bytes<HD, true>;
+constexpr int NST1 = NSTAGE;
 __global__ __launch_bounds__(NWAVES * 64, 2) void attn_bwd_dkv_tr_kernel(AttnBwdParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -134,19 +46,12 @@ __global__ __launch_bounds__(NWAVES * 64, 2) void attn_bwd_dkv_tr_kernel(AttnBwd
     const int lk = lane & 31, lg = lane >> 5;
     constexpr int KB = 32 * NWAVES;
     const int nkb = (p.S + KB - 1) / KB;
-    const int nwg = nkb * p.H * p.B;
-    int wid = blockIdx.x;
-    {
-        const int q8 = nwg >> 3, r8 = nwg & 7, xcd = wid & 7;
-        wid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (wid >> 3);
-    }
+    const int wid = xcd_remap(blockIdx.x, nkb * p.H * p.B);
     const int kblk = wid % nkb;
     const long bh = wid / nkb;
     const bf16_t* Qg = p.q + bh * p.S_pad * 64;
     const bf16_t* Og = p.doh + bh * p.S_pad * 64;
-    // -L | -Delta of a 64-query tile are 128 contiguous floats in p.nld ([b h][tile][2][64]): wave w moves floats 32 w .. 32 w + 31 with
-    // the first 8 lanes of one 16-byte LDS-DMA instruction (every wave: the same VM-operation count per tile, 5)
-    const float* NLg = p.nld + bh * p.S_pad * 2 + wave * 32 + (lane & 7) * 4;
+    const float* NLg = p.nld + bh * p.S_pad * 2 + wave * 32 + (lane & 7) * 4;      // this lane's 16 bytes of tile 0's -L | -Delta
     const int key = kblk * KB + wave * 32 + lk;
     const int key_ld = key < p.S ? key : p.S - 1;
     bf16x8 kf[4], vf[4];
@@ -155,36 +60,21 @@ __global__ __launch_bounds__(NWAVES * 64, 2) void attn_bwd_dkv_tr_kernel(AttnBwd
         kf[kk] = *(const bf16x8*)(p.k + (bh * p.S_pad + key_ld) * 64 + kk * 16 + lg * 8);
         vf[kk] = *(const bf16x8*)(p.v + (bh * p.S_pad + key_ld) * 64 + kk * 16 + lg * 8);
     }
-    auto stage = [&](int t, int buf) {
-        char* base = smem + buf * ST1T;
-        stage_tile2<NWAVES>(Qg + (long)t * TB * 64, 64, base, wave, lane);
-        stage_tile2<NWAVES>(Og + (long)t * TB * 64, 64, base + TILE, wave, lane);
-        if (lane < 8) __builtin_amdgcn_global_load_lds((gptr_t)(NLg + (long)t * 2 * TB), (lptr_t)(base + 2 * TILE + wave * 128), 16, 0, 0);
-    };
-    // row-major tiles as A operand: row = 32*qb + perm(lk), logical chunk = 2*kk + lg
+    auto stage = [&](int t) { stage_slot<HD, true>(smem, t & (NST1 - 1), Qg, Og, NLg + (long)t * 2 * TB, t, wave, lane); };      // 5 VM operations per wave
     const int prow = row_perm(lk);
-    int offR[4];
+    int offR[4], trb[2][2];
 #pragma unroll
-    for (int kk = 0; kk < 4; ++kk) offR[kk] = prow * 128 + (((2 * kk + lg) ^ swz2(prow)) << 4);
-    // transposed reads: this lane supplies the 8-byte piece (row 8 lg + 4 jj + (i >> 2), columns 32 db + 16 g1 + 4 (i & 3) ..) of the block
-    int trb[2][2];
-    {
-        const int i = lane & 15, g1 = (lane >> 4) & 1;
+    for (int kk = 0; kk < 4; ++kk) offR[kk] = frag_offset(prow, lg, kk);
 #pragma unroll
-        for (int db = 0; db < 2; ++db)
+    for (int db = 0; db < 2; ++db)
 #pragma unroll
-            for (int jj = 0; jj < 2; ++jj) {
-                const int ql = 8 * lg + 4 * jj + (i >> 2);
-                const int ch = 4 * db + 2 * g1 + ((i & 3) >> 1);
-                trb[db][jj] = ql * 128 + ((ch ^ swz2(ql)) << 4) + (i & 1) * 8;
-            }
-    }
+        for (int jj = 0; jj < 2; ++jj) trb[db][jj] = tr_piece_offset(lane, lg, db, jj);
     f32x16 dk[2], dv[2];
     dk[0] = (f32x16){0}; dk[1] = (f32x16){0}; dv[0] = (f32x16){0}; dv[1] = (f32x16){0};
     const int nt = (p.S + TB - 1) / TB;
-    stage(0, 0);
-    if (nt > 1) stage(1, 1);
-    if (nt > 2) stage(2, 2);
+    stage(0);
+    if (nt > 1) stage(1);
+    if (nt > 2) stage(2);
     // one half tile (32 queries): reads -> S / dP chains -> P, dZ -> second products.  Round 6: (1) ALL sixteen fragment / C-operand reads of the
     // half are issued by one asm statement and waited for once -- hipcc had paired every ds_read_b128 with an `s_waitcnt lgkmcnt(0)` in front of
     // its MFMA (eight exposed LDS round trips per half); (2) the query-tail mask is compiled into the LAST tile's copy of the body only (MASK) --
@@ -258,30 +148,28 @@ __global__ __launch_bounds__(NWAVES * 64, 2) void attn_bwd_dkv_tr_kernel(AttnBwd
                 MFMA32("%[dv1]", "v[244:247]", "%[pf1]") MFMA32("%[dk1]", "v[252:255]", "%[zf1]")
                 : [dv0] "+v"(dv_[0]), [dv1] "+v"(dv_[1]), [dk0] "+v"(dk_[0]), [dk1] "+v"(dk_[1])
                 : [a0] "v"(a0), [a1] "v"(a1), [a2] "v"(a2), [a3] "v"(a3), [pf0] "v"(pf0), [pf1] "v"(pf1), [zf0] "v"(zf0), [zf1] "v"(zf1)
-                : "memory", "v224", "v225", "v226", "v227", "v228", "v229", "v230", "v231", "v232", "v233", "v234", "v235", "v236", "v237", "v238", "v239",
-                  "v240", "v241", "v242", "v243", "v244", "v245", "v246", "v247", "v248", "v249", "v250", "v251", "v252", "v253", "v254", "v255");
+                : "memory", TR_CLOBBER32);
         }
     };
     using std::integral_constant;
     for (int t = 0; t < nt - 1; ++t) {
-        wait_tiles_ahead(nt - 1 - t, 5);
-        if (t + 3 < nt) stage(t + 3, (t + 3) & (NST1 - 1));      // its buffer held tile t - 1: every wave is past it (the barrier above)
+        wait_tiles_ahead<5>(nt - 1 - t);
+        if (t + 3 < nt) stage(t + 3);      // its slot held tile t - 1: every wave is past it (the barrier above)
         half(t, integral_constant<int, 0>{}, integral_constant<bool, false>{});
         half(t, integral_constant<int, 1>{}, integral_constant<bool, false>{});
     }
-    wait_tiles_ahead(0, 5);                                      // the last tile, behind the loop (no accumulator merge inside it)
+    wait_tiles_ahead<5>(0);                                      // the last tile, behind the loop (no accumulator merge inside it)
     half(nt - 1, integral_constant<int, 0>{}, integral_constant<bool, true>{});
     half(nt - 1, integral_constant<int, 1>{}, integral_constant<bool, true>{});
-    __syncthreads();     // every wave is done with the ring: reuse it for the output transposes (4 KiB per wave)
-    char* ob = smem + wave * 4096;
+    const OutStage o = epilogue_begin<HD, false>(smem, wave, lane);
     const int row0 = kblk * KB + wave * 32;
-    store_rows(dk, LN2, ob, p.dk + bh * p.S_pad * 64, row0, p.S, lane);
-    store_rows(dv, 1.0f, ob, p.dv + bh * p.S_pad * 64, row0, p.S, lane);
+    store_rows<HD>(dk, LN2, o, p.dk + bh * p.S_pad * 64, row0, p.S);
+    store_rows<HD>(dv, 1.0f, o, p.dv + bh * p.S_pad * 64, row0, p.S);
 }
 
 // ---- pass 2: dQ.  LDS stage: K [64 keys][64 d] | V [64 keys][64 d]; ring of 4, two workgroups per CU
-constexpr int ST2T = 2 * TILE;
-constexpr int NST2 = 4;
+constexpr int ST2T = slot_bytes<HD, false>;
+constexpr int NST2 = NSTAGE;
 // Tail hazard of the UN-MASKED dQ passes (the software-pipelined kernels below).  A zero padding key of the last tile has score 0, so its
 // probability is 2^(0 - L) for a query with log-sum-exp L: harmless while it is finite (dZ * k_pad = dZ * 0 = 0), but for a query whose every real
 // score is far below zero it overflows -- L < -128: P = inf, dZ = inf, inf * 0 = NaN in that query's dQ row (measured: tests/
@@ -304,12 +192,7 @@ __global__ __launch_bounds__(NWAVES * 64, 2) void attn_bwd_dq_tr_kernel(AttnBwdP
     const int lq = lane & 31, lg = lane >> 5;
     constexpr int QB = 32 * NWAVES;
     const int nqb = (p.S + QB - 1) / QB;
-    const int nwg = nqb * p.H * p.B;
-    int wid = blockIdx.x;
-    {
-        const int q8 = nwg >> 3, r8 = nwg & 7, xcd = wid & 7;
-        wid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (wid >> 3);
-    }
+    const int wid = xcd_remap(blockIdx.x, nqb * p.H * p.B);
     const int qblk = wid % nqb;
     const long bh = wid / nqb;
     if (p.dq_mode == 2 && !dq_tail_hazard(p, bh, qblk * QB / p.dq_rows)) return;      // only the blocks the un-masked pass leaves out
@@ -332,33 +215,21 @@ __global__ __launch_bounds__(NWAVES * 64, 2) void attn_bwd_dq_tr_kernel(AttnBwdP
 #pragma unroll
         for (int r = 0; r < 16; ++r) { nL[r] = l; nD[r] = d; }
     }
-    auto stage = [&](int t, int buf) {
-        char* base = smem + buf * ST2T;
-        stage_tile2<NWAVES>(Kg + (long)t * TB * 64, 64, base, wave, lane);
-        stage_tile2<NWAVES>(Vg + (long)t * TB * 64, 64, base + TILE, wave, lane);
-    };
+    auto stage = [&](int t) { stage_slot<HD, false>(smem, t & (NST2 - 1), Kg, Vg, nullptr, t, wave, lane); };      // 4 VM operations per wave
     const int prow = row_perm(lq);
-    int offR[4];
+    int offR[4], trb[2][2];
 #pragma unroll
-    for (int kk = 0; kk < 4; ++kk) offR[kk] = prow * 128 + (((2 * kk + lg) ^ swz2(prow)) << 4);
-    int trb[2][2];
-    {
-        const int i = lane & 15, g1 = (lane >> 4) & 1;
+    for (int kk = 0; kk < 4; ++kk) offR[kk] = frag_offset(prow, lg, kk);
 #pragma unroll
-        for (int db = 0; db < 2; ++db)
+    for (int db = 0; db < 2; ++db)
 #pragma unroll
-            for (int jj = 0; jj < 2; ++jj) {
-                const int kl = 8 * lg + 4 * jj + (i >> 2);
-                const int ch = 4 * db + 2 * g1 + ((i & 3) >> 1);
-                trb[db][jj] = kl * 128 + ((ch ^ swz2(kl)) << 4) + (i & 1) * 8;
-            }
-    }
+        for (int jj = 0; jj < 2; ++jj) trb[db][jj] = tr_piece_offset(lane, lg, db, jj);
     f32x16 dq[2];
     dq[0] = (f32x16){0}; dq[1] = (f32x16){0};
     const int nt = (p.S + TB - 1) / TB;
-    stage(0, 0);
-    if (nt > 1) stage(1, 1);
-    if (nt > 2) stage(2, 2);
+    stage(0);
+    if (nt > 1) stage(1);
+    if (nt > 2) stage(2);
     // one half tile (32 keys); round 6: all eight fragment reads up front, one wait; the key-tail mask only in the last tile's copy (see pass 1)
     auto half = [&](int t, auto kb_c, auto mask_c) {
         constexpr int kb = decltype(kb_c)::value;
@@ -407,22 +278,21 @@ __global__ __launch_bounds__(NWAVES * 64, 2) void attn_bwd_dq_tr_kernel(AttnBwdP
                 MFMA32("%[dq0]", "v[232:235]", "%[zf1]") MFMA32("%[dq1]", "v[236:239]", "%[zf1]")
                 : [dq0] "+v"(dq_[0]), [dq1] "+v"(dq_[1])
                 : [a0] "v"(a0), [a1] "v"(a1), [a2] "v"(a2), [a3] "v"(a3), [zf0] "v"(zf0), [zf1] "v"(zf1)
-                : "memory", "v224", "v225", "v226", "v227", "v228", "v229", "v230", "v231", "v232", "v233", "v234", "v235", "v236", "v237", "v238", "v239");
+                : "memory", TR_CLOBBER16);
         }
     };
     using std::integral_constant;
     for (int t = 0; t < nt - 1; ++t) {
-        wait_tiles_ahead(nt - 1 - t, 4);
-        if (t + 3 < nt) stage(t + 3, (t + 3) % NST2);
+        wait_tiles_ahead<4>(nt - 1 - t);
+        if (t + 3 < nt) stage(t + 3);
         half(t, integral_constant<int, 0>{}, integral_constant<bool, false>{});
         half(t, integral_constant<int, 1>{}, integral_constant<bool, false>{});
     }
-    wait_tiles_ahead(0, 4);
+    wait_tiles_ahead<4>(0);
     half(nt - 1, integral_constant<int, 0>{}, integral_constant<bool, true>{});
     half(nt - 1, integral_constant<int, 1>{}, integral_constant<bool, true>{});
-    __syncthreads();
-    char* ob = smem + wave * 4096;
-    store_rows(dq, LN2, ob, p.dq + bh * p.S_pad * 64, qblk * QB + wave * 32, p.S, lane);
+    const OutStage o = epilogue_begin<HD, false>(smem, wave, lane);
+    store_rows<HD>(dq, LN2, o, p.dq + bh * p.S_pad * 64, qblk * QB + wave * 32, p.S);
 }
 
 // =============================================================================================== round 6: software-pipelined passes
@@ -447,54 +317,32 @@ __global__ __launch_bounds__(NWAVES * 64, 2) void attn_bwd_dkv_pipe_kernel(AttnB
     const int lk = lane & 31, lg = lane >> 5;
     constexpr int KB = 32 * NWAVES;
     const int nkb = (p.S + KB - 1) / KB;
-    const int nwg = nkb * p.H * p.B;
-    int wid = blockIdx.x;
-    {
-        const int q8 = nwg >> 3, r8 = nwg & 7, xcd = wid & 7;
-        wid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (wid >> 3);
-    }
+    const int wid = xcd_remap(blockIdx.x, nkb * p.H * p.B);
     const int kblk = wid % nkb;
     const long bh = wid / nkb;
-    if ((unsigned)(size_t)(__attribute__((address_space(3))) char*)smem != 0u) __builtin_trap();      // the asm addresses the ring from LDS byte 0
+    require_lds_base0(smem);
     const bf16_t* Qg = p.q + bh * p.S_pad * 64;
     const bf16_t* Og = p.doh + bh * p.S_pad * 64;
     const float* NLt = p.nld + bh * p.S_pad * 2;
     const int key = kblk * KB + wave * 32 + lk;
     const int key_ld = key < p.S ? key : p.S - 1;
     const int nt = (p.S + TB - 1) / TB;
-    // LDS-DMA: this lane's 16-byte piece of rows 8 w + (l >> 3) (and + 32) of a 64 x 64 tile; 16 bytes of the tile's -L | -Delta floats
-    const int srow = wave * 8 + (lane >> 3);
-    const unsigned g0 = (unsigned)(srow * 128 + (((lane & 7) ^ swz2(srow)) << 4));
-    const unsigned g2 = (unsigned)(wave * 128 + (lane & 7) * 16);
-    const unsigned grow = (unsigned)(key_ld * 128 + lg * 16);
-    auto stage = [&](int t, int buf) {                   // (tiles 0..2; the loop stages the rest)
-        const int tt = t < nt ? t : nt - 1;
-        char* base = smem + buf * ST1T;
-        stage_tile2<NWAVES>(Qg + (long)tt * TB * 64, 64, base, wave, lane);
-        stage_tile2<NWAVES>(Og + (long)tt * TB * 64, 64, base + TILE, wave, lane);
-        if (lane < 8) __builtin_amdgcn_global_load_lds((gptr_t)(NLt + (long)tt * 2 * TB + wave * 32 + (lane & 7) * 4), (lptr_t)(base + 2 * TILE + wave * 128), 16, 0, 0);
-    };
+    const unsigned g0 = dma_src_offset<HD>(wave, lane), g2 = dma_nld_offset(wave, lane), grow = own_row_offset<HD>(key_ld, lg);
     const int prow = row_perm(lk);
-    unsigned la = (unsigned)(2 * TILE + 32 * lg), r0, a0, a1;
-    {
-        r0 = (unsigned)(prow * 128 + ((lg ^ swz2(prow)) << 4));                  // fragment kk = 0 (pass 1's offR[0])
-        const int i = lane & 15, g1 = (lane >> 4) & 1;
-        unsigned a[2];
+    unsigned la = nld_read_offset<HD>(lg), r0 = (unsigned)frag_offset(prow, lg, 0), a[2];
 #pragma unroll
-        for (int jj = 0; jj < 2; ++jj) {                                         // pieces (db = 0, jj) (pass 1's trb[0][jj])
-            const int ql = 8 * lg + 4 * jj + (i >> 2);
-            const int ch = 2 * g1 + ((i & 3) >> 1);
-            a[jj] = (unsigned)(ql * 128 + ((ch ^ swz2(ql)) << 4) + (i & 1) * 8);
-        }
-        a0 = a[0]; a1 = a[1];
-    }
-    stage(0, 0); stage(1, 1); stage(2, 2);
-    const int lt = nt - 1 < 3 ? nt - 1 : 3;
-    const unsigned long long b0 = (unsigned long long)(Qg + (long)lt * TB * 64), b1 = (unsigned long long)(Og + (long)lt * TB * 64);
-    const unsigned long long b2 = (unsigned long long)(NLt + (long)lt * 2 * TB);
+    for (int jj = 0; jj < 2; ++jj) a[jj] = (unsigned)tr_piece_offset(lane, lg, 0, jj);
+    unsigned a0 = a[0], a1 = a[1];
+    auto stage = [&](int t) {
+        const int tt = t < nt ? t : nt - 1;
+        stage_slot<HD, true>(smem, t, Qg, Og, NLt + (long)tt * 2 * TB + wave * 32 + (lane & 7) * 4, tt, wave, lane);
+    };
+    stage(0); stage(1); stage(2);
+    const int lt = first_loop_tile(nt);
+    const unsigned long long b0 = tile_addr<HD>(Qg, lt), b1 = tile_addr<HD>(Og, lt), b2 = nld_addr(NLt, lt);
     const unsigned long long p0 = (unsigned long long)(p.k + bh * p.S_pad * 64), p1 = (unsigned long long)(p.v + bh * p.S_pad * 64);
 #define DKV_OPERANDS                                                                                                                          \
-                 : [la] "+v"(la), [r0] "+v"(r0), [a0] "+v"(a0), [a1] "+v"(a1)       /* (r1..r3, a2, a3 are r0 ^ 32 kk, a0 / a1 ^ 64: formed at their use) */ \
+                 : [la] "+v"(la), [r0] "+v"(r0), [a0] "+v"(a0), [a1] "+v"(a1)                                                                    \
                  : [g0] "v"(g0), [g2] "v"(g2), [grow] "v"(grow), [b0] "s"(b0), [b1] "s"(b1), [b2] "s"(b2), [p0] "s"(p0), [p1] "s"(p1), [nt] "s"(nt), \
                    [wv] "s"(wave)                                                                                                                \
                  : ABWD64_DKV_CLOBBERS
@@ -506,15 +354,10 @@ __global__ __launch_bounds__(NWAVES * 64, 2) void attn_bwd_dkv_pipe_kernel(AttnB
 #undef DKV_OPERANDS
     f32x16 dk[2], dv[2];
     ABWD64_READ_ACC_0(dv[0]) ABWD64_READ_ACC_16(dk[0]) ABWD64_READ_ACC_32(dv[1]) ABWD64_READ_ACC_48(dk[1])
-    __syncthreads();     // every wave is done with the ring (and its LDS-DMA writes: the asm ends with vmcnt(0)): reuse it for the output transposes
-    // the epilogue's lane arithmetic hangs off an OPAQUE copy of the lane id: hipcc would otherwise form those addresses in front of the loop and
-    // keep them alive across it, where sixteen VGPRs are all there is (one more register and the kernel drops to one wave per SIMD)
-    int lane_e = lane;
-    asm volatile("" : "+v"(lane_e));
-    char* ob = smem + wave * 4096;
+    const OutStage o = epilogue_begin<HD, true>(smem, wave, lane);
     const int row0 = kblk * KB + wave * 32;
-    store_rows(dk, LN2, ob, p.dk + bh * p.S_pad * 64, row0, p.S, lane_e);
-    store_rows(dv, 1.0f, ob, p.dv + bh * p.S_pad * 64, row0, p.S, lane_e);
+    store_rows<HD>(dk, LN2, o, p.dk + bh * p.S_pad * 64, row0, p.S);
+    store_rows<HD>(dv, 1.0f, o, p.dv + bh * p.S_pad * 64, row0, p.S);
 }
 
 __global__ __launch_bounds__(NWAVES * 64, 2) void attn_bwd_dq_pipe_kernel(AttnBwdParams p) {
@@ -524,51 +367,31 @@ __global__ __launch_bounds__(NWAVES * 64, 2) void attn_bwd_dq_pipe_kernel(AttnBw
     const int lq = lane & 31, lg = lane >> 5;
     constexpr int QB = 32 * NWAVES;
     const int nqb = (p.S + QB - 1) / QB;
-    const int nwg = nqb * p.H * p.B;
-    int wid = blockIdx.x;
-    {
-        const int q8 = nwg >> 3, r8 = nwg & 7, xcd = wid & 7;
-        wid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (wid >> 3);
-    }
+    const int wid = xcd_remap(blockIdx.x, nqb * p.H * p.B);
     const int qblk = wid % nqb;
     const long bh = wid / nqb;
-    if ((unsigned)(size_t)(__attribute__((address_space(3))) char*)smem != 0u) __builtin_trap();
+    require_lds_base0(smem);
     if (p.dq_mode == 1 && dq_tail_hazard(p, bh, qblk)) return;      // no tail masks here: the masked kernel takes this block
     const bf16_t* Kg = p.k + bh * p.S_pad * 64;
     const bf16_t* Vg = p.v + bh * p.S_pad * 64;
     const int q_row = qblk * QB + wave * 32 + lq;
     const int q_ld = q_row < p.S ? q_row : p.S - 1;
     const int nt = (p.S + TB - 1) / TB;
-    const int srow = wave * 8 + (lane >> 3);
-    const unsigned g0 = (unsigned)(srow * 128 + (((lane & 7) ^ swz2(srow)) << 4));
-    const unsigned grow = (unsigned)(q_ld * 128 + lg * 16);
+    const unsigned g0 = dma_src_offset<HD>(wave, lane), grow = own_row_offset<HD>(q_ld, lg);
     const float nl = -p.lse[bh * p.S_pad + q_ld], nd = -p.delta[bh * p.S_pad + q_ld];
-    auto stage = [&](int t, int buf) {
-        const int tt = t < nt ? t : nt - 1;
-        char* base = smem + buf * ST2T;
-        stage_tile2<NWAVES>(Kg + (long)tt * TB * 64, 64, base, wave, lane);
-        stage_tile2<NWAVES>(Vg + (long)tt * TB * 64, 64, base + TILE, wave, lane);
-    };
     const int prow = row_perm(lq);
-    unsigned r0, r1, r2, r3, a0, a1, a2, a3;
-    {
-        unsigned r[4], a[4];
+    unsigned r[4], a[4];
 #pragma unroll
-        for (int kk = 0; kk < 4; ++kk) r[kk] = (unsigned)(prow * 128 + (((2 * kk + lg) ^ swz2(prow)) << 4));
-        const int i = lane & 15, g1 = (lane >> 4) & 1;
+    for (int kk = 0; kk < 4; ++kk) r[kk] = (unsigned)frag_offset(prow, lg, kk);
 #pragma unroll
-        for (int db = 0; db < 2; ++db)
+    for (int db = 0; db < 2; ++db)
 #pragma unroll
-            for (int jj = 0; jj < 2; ++jj) {
-                const int kl = 8 * lg + 4 * jj + (i >> 2);
-                const int ch = 4 * db + 2 * g1 + ((i & 3) >> 1);
-                a[db * 2 + jj] = (unsigned)(kl * 128 + ((ch ^ swz2(kl)) << 4) + (i & 1) * 8);
-            }
-        r0 = r[0]; r1 = r[1]; r2 = r[2]; r3 = r[3]; a0 = a[0]; a1 = a[1]; a2 = a[2]; a3 = a[3];
-    }
-    stage(0, 0); stage(1, 1); stage(2, 2);
-    const int lt = nt - 1 < 3 ? nt - 1 : 3;
-    const unsigned long long b0 = (unsigned long long)(Kg + (long)lt * TB * 64), b1 = (unsigned long long)(Vg + (long)lt * TB * 64);
+        for (int jj = 0; jj < 2; ++jj) a[db * 2 + jj] = (unsigned)tr_piece_offset(lane, lg, db, jj);
+    unsigned r0 = r[0], r1 = r[1], r2 = r[2], r3 = r[3], a0 = a[0], a1 = a[1], a2 = a[2], a3 = a[3];
+    auto stage = [&](int t) { stage_slot<HD, false>(smem, t, Kg, Vg, nullptr, t < nt ? t : nt - 1, wave, lane); };
+    stage(0); stage(1); stage(2);
+    const int lt = first_loop_tile(nt);
+    const unsigned long long b0 = tile_addr<HD>(Kg, lt), b1 = tile_addr<HD>(Vg, lt);
     const unsigned long long p0 = (unsigned long long)(p.q + bh * p.S_pad * 64), p1 = (unsigned long long)(p.doh + bh * p.S_pad * 64);
     asm volatile(ABWD64_DQ_ASM
                  : [r0] "+v"(r0), [r1] "+v"(r1), [r2] "+v"(r2), [r3] "+v"(r3), [a0] "+v"(a0), [a1] "+v"(a1), [a2] "+v"(a2), [a3] "+v"(a3)
@@ -577,11 +400,8 @@ __global__ __launch_bounds__(NWAVES * 64, 2) void attn_bwd_dq_pipe_kernel(AttnBw
                  : ABWD64_DQ_CLOBBERS);
     f32x16 dq[2];
     ABWD64_READ_ACC_0(dq[0]) ABWD64_READ_ACC_16(dq[1])
-    __syncthreads();
-    int lane_e = lane;
-    asm volatile("" : "+v"(lane_e));
-    char* ob = smem + wave * 4096;
-    store_rows(dq, LN2, ob, p.dq + bh * p.S_pad * 64, qblk * QB + wave * 32, p.S, lane_e);
+    const OutStage o = epilogue_begin<HD, true>(smem, wave, lane);
+    store_rows<HD>(dq, LN2, o, p.dq + bh * p.S_pad * 64, qblk * QB + wave * 32, p.S);
 }
 
 // ---- two 32-row blocks per wave, one wave per SIMD (attn_bwd64x2_asm.inc <- gen_attn_bwd.py 64x2: its docstring has the why)
@@ -594,50 +414,30 @@ __global__ __launch_bounds__(NWAVES * 64, 1) void attn_bwd_dkv_pipe2_kernel(Attn
     const int lk = lane & 31, lg = lane >> 5;
     constexpr int KB = 64 * NWAVES;
     const int nkb = (p.S + KB - 1) / KB;
-    const int nwg = nkb * p.H * p.B;
-    int wid = blockIdx.x;
-    {
-        const int q8 = nwg >> 3, r8 = nwg & 7, xcd = wid & 7;
-        wid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (wid >> 3);
-    }
+    const int wid = xcd_remap(blockIdx.x, nkb * p.H * p.B);
     const int kblk = wid % nkb;
     const long bh = wid / nkb;
-    if ((unsigned)(size_t)(__attribute__((address_space(3))) char*)smem != 0u) __builtin_trap();
+    require_lds_base0(smem);
     const bf16_t* Qg = p.q + bh * p.S_pad * 64;
     const bf16_t* Og = p.doh + bh * p.S_pad * 64;
     const float* NLt = p.nld + bh * p.S_pad * 2;
     const int key0 = kblk * KB + wave * 64 + lk, key1 = key0 + 32;
     const int kl0 = key0 < p.S ? key0 : p.S - 1, kl1 = key1 < p.S ? key1 : p.S - 1;
     const int nt = (p.S + TB - 1) / TB;
-    const int srow = wave * 8 + (lane >> 3);
-    const unsigned g0 = (unsigned)(srow * 128 + (((lane & 7) ^ swz2(srow)) << 4));
-    const unsigned g2 = (unsigned)(wave * 128 + (lane & 7) * 16);
-    const unsigned grow0 = (unsigned)(kl0 * 128 + lg * 16), grow1 = (unsigned)(kl1 * 128 + lg * 16);
-    auto stage = [&](int t, int buf) {
-        const int tt = t < nt ? t : nt - 1;
-        char* base = smem + buf * ST1T;
-        stage_tile2<NWAVES>(Qg + (long)tt * TB * 64, 64, base, wave, lane);
-        stage_tile2<NWAVES>(Og + (long)tt * TB * 64, 64, base + TILE, wave, lane);
-        if (lane < 8) __builtin_amdgcn_global_load_lds((gptr_t)(NLt + (long)tt * 2 * TB + wave * 32 + (lane & 7) * 4), (lptr_t)(base + 2 * TILE + wave * 128), 16, 0, 0);
-    };
+    const unsigned g0 = dma_src_offset<HD>(wave, lane), g2 = dma_nld_offset(wave, lane);
+    const unsigned grow0 = own_row_offset<HD>(kl0, lg), grow1 = own_row_offset<HD>(kl1, lg);
     const int prow = row_perm(lk);
-    unsigned la = (unsigned)(2 * TILE + 32 * lg), r0, a0, a1;
-    {
-        r0 = (unsigned)(prow * 128 + ((lg ^ swz2(prow)) << 4));
-        const int i = lane & 15, g1 = (lane >> 4) & 1;
-        unsigned a[2];
+    unsigned la = nld_read_offset<HD>(lg), r0 = (unsigned)frag_offset(prow, lg, 0), a[2];
 #pragma unroll
-        for (int jj = 0; jj < 2; ++jj) {
-            const int ql = 8 * lg + 4 * jj + (i >> 2);
-            const int ch = 2 * g1 + ((i & 3) >> 1);
-            a[jj] = (unsigned)(ql * 128 + ((ch ^ swz2(ql)) << 4) + (i & 1) * 8);
-        }
-        a0 = a[0]; a1 = a[1];
-    }
-    stage(0, 0); stage(1, 1); stage(2, 2);
-    const int lt = nt - 1 < 3 ? nt - 1 : 3;
-    const unsigned long long b0 = (unsigned long long)(Qg + (long)lt * TB * 64), b1 = (unsigned long long)(Og + (long)lt * TB * 64);
-    const unsigned long long b2 = (unsigned long long)(NLt + (long)lt * 2 * TB);
+    for (int jj = 0; jj < 2; ++jj) a[jj] = (unsigned)tr_piece_offset(lane, lg, 0, jj);
+    unsigned a0 = a[0], a1 = a[1];
+    auto stage = [&](int t) {
+        const int tt = t < nt ? t : nt - 1;
+        stage_slot<HD, true>(smem, t, Qg, Og, NLt + (long)tt * 2 * TB + wave * 32 + (lane & 7) * 4, tt, wave, lane);
+    };
+    stage(0); stage(1); stage(2);
+    const int lt = first_loop_tile(nt);
+    const unsigned long long b0 = tile_addr<HD>(Qg, lt), b1 = tile_addr<HD>(Og, lt), b2 = nld_addr(NLt, lt);
     const unsigned long long p0 = (unsigned long long)(p.k + bh * p.S_pad * 64), p1 = (unsigned long long)(p.v + bh * p.S_pad * 64);
     asm volatile(ABWD64X2_DKV2_ASM
                  : [la] "+v"(la), [r0] "+v"(r0), [a0] "+v"(a0), [a1] "+v"(a1)
@@ -647,15 +447,12 @@ __global__ __launch_bounds__(NWAVES * 64, 1) void attn_bwd_dkv_pipe2_kernel(Attn
     f32x16 dk0[2], dv0[2], dk1[2], dv1[2];
     ABWD64X2_READ_ACC_0(dv0[0]) ABWD64X2_READ_ACC_16(dv0[1]) ABWD64X2_READ_ACC_32(dk0[0]) ABWD64X2_READ_ACC_48(dk0[1])
     ABWD64X2_READ_ACC_64(dv1[0]) ABWD64X2_READ_ACC_80(dv1[1]) ABWD64X2_READ_ACC_96(dk1[0]) ABWD64X2_READ_ACC_112(dk1[1])
-    __syncthreads();
-    int lane_e = lane;
-    asm volatile("" : "+v"(lane_e));
-    char* ob = smem + wave * 4096;
+    const OutStage o = epilogue_begin<HD, true>(smem, wave, lane);
     const int row0 = kblk * KB + wave * 64;
-    store_rows(dk0, LN2, ob, p.dk + bh * p.S_pad * 64, row0, p.S, lane_e);
-    store_rows(dv0, 1.0f, ob, p.dv + bh * p.S_pad * 64, row0, p.S, lane_e);
-    store_rows(dk1, LN2, ob, p.dk + bh * p.S_pad * 64, row0 + 32, p.S, lane_e);
-    store_rows(dv1, 1.0f, ob, p.dv + bh * p.S_pad * 64, row0 + 32, p.S, lane_e);
+    store_rows<HD>(dk0, LN2, o, p.dk + bh * p.S_pad * 64, row0, p.S);
+    store_rows<HD>(dv0, 1.0f, o, p.dv + bh * p.S_pad * 64, row0, p.S);
+    store_rows<HD>(dk1, LN2, o, p.dk + bh * p.S_pad * 64, row0 + 32, p.S);
+    store_rows<HD>(dv1, 1.0f, o, p.dv + bh * p.S_pad * 64, row0 + 32, p.S);
 }
 
 __global__ __launch_bounds__(NWAVES * 64, 1) void attn_bwd_dq_pipe2_kernel(AttnBwdParams p) {
@@ -665,51 +462,31 @@ __global__ __launch_bounds__(NWAVES * 64, 1) void attn_bwd_dq_pipe2_kernel(AttnB
     const int lq = lane & 31, lg = lane >> 5;
     constexpr int QB = 64 * NWAVES;
     const int nqb = (p.S + QB - 1) / QB;
-    const int nwg = nqb * p.H * p.B;
-    int wid = blockIdx.x;
-    {
-        const int q8 = nwg >> 3, r8 = nwg & 7, xcd = wid & 7;
-        wid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (wid >> 3);
-    }
+    const int wid = xcd_remap(blockIdx.x, nqb * p.H * p.B);
     const int qblk = wid % nqb;
     const long bh = wid / nqb;
-    if ((unsigned)(size_t)(__attribute__((address_space(3))) char*)smem != 0u) __builtin_trap();
+    require_lds_base0(smem);
     if (p.dq_mode == 1 && dq_tail_hazard(p, bh, qblk)) return;      // no tail masks here: the masked kernel takes this block
     const bf16_t* Kg = p.k + bh * p.S_pad * 64;
     const bf16_t* Vg = p.v + bh * p.S_pad * 64;
     const int q0 = qblk * QB + wave * 64 + lq, q1 = q0 + 32;
     const int ql0 = q0 < p.S ? q0 : p.S - 1, ql1 = q1 < p.S ? q1 : p.S - 1;
     const int nt = (p.S + TB - 1) / TB;
-    const int srow = wave * 8 + (lane >> 3);
-    const unsigned g0 = (unsigned)(srow * 128 + (((lane & 7) ^ swz2(srow)) << 4));
-    const unsigned grow0 = (unsigned)(ql0 * 128 + lg * 16), grow1 = (unsigned)(ql1 * 128 + lg * 16);
+    const unsigned g0 = dma_src_offset<HD>(wave, lane);
+    const unsigned grow0 = own_row_offset<HD>(ql0, lg), grow1 = own_row_offset<HD>(ql1, lg);
     const float nl0 = -p.lse[bh * p.S_pad + ql0], nd0 = -p.delta[bh * p.S_pad + ql0];
     const float nl1 = -p.lse[bh * p.S_pad + ql1], nd1 = -p.delta[bh * p.S_pad + ql1];
-    auto stage = [&](int t, int buf) {
-        const int tt = t < nt ? t : nt - 1;
-        char* base = smem + buf * ST2T;
-        stage_tile2<NWAVES>(Kg + (long)tt * TB * 64, 64, base, wave, lane);
-        stage_tile2<NWAVES>(Vg + (long)tt * TB * 64, 64, base + TILE, wave, lane);
-    };
     const int prow = row_perm(lq);
-    unsigned r0, a0, a1, a2, a3;
-    {
-        r0 = (unsigned)(prow * 128 + ((lg ^ swz2(prow)) << 4));
-        const int i = lane & 15, g1 = (lane >> 4) & 1;
-        unsigned a[4];
+    unsigned r0 = (unsigned)frag_offset(prow, lg, 0), a[4];
 #pragma unroll
-        for (int db = 0; db < 2; ++db)
+    for (int db = 0; db < 2; ++db)
 #pragma unroll
-            for (int jj = 0; jj < 2; ++jj) {
-                const int kl = 8 * lg + 4 * jj + (i >> 2);
-                const int ch = 4 * db + 2 * g1 + ((i & 3) >> 1);
-                a[db * 2 + jj] = (unsigned)(kl * 128 + ((ch ^ swz2(kl)) << 4) + (i & 1) * 8);
-            }
-        a0 = a[0]; a1 = a[1]; a2 = a[2]; a3 = a[3];
-    }
-    stage(0, 0); stage(1, 1); stage(2, 2);
-    const int lt = nt - 1 < 3 ? nt - 1 : 3;
-    const unsigned long long b0 = (unsigned long long)(Kg + (long)lt * TB * 64), b1 = (unsigned long long)(Vg + (long)lt * TB * 64);
+        for (int jj = 0; jj < 2; ++jj) a[db * 2 + jj] = (unsigned)tr_piece_offset(lane, lg, db, jj);
+    unsigned a0 = a[0], a1 = a[1], a2 = a[2], a3 = a[3];
+    auto stage = [&](int t) { stage_slot<HD, false>(smem, t, Kg, Vg, nullptr, t < nt ? t : nt - 1, wave, lane); };
+    stage(0); stage(1); stage(2);
+    const int lt = first_loop_tile(nt);
+    const unsigned long long b0 = tile_addr<HD>(Kg, lt), b1 = tile_addr<HD>(Vg, lt);
     const unsigned long long p0 = (unsigned long long)(p.q + bh * p.S_pad * 64), p1 = (unsigned long long)(p.doh + bh * p.S_pad * 64);
     asm volatile(ABWD64X2_DQ2_ASM
                  : [r0] "+v"(r0), [a0] "+v"(a0), [a1] "+v"(a1), [a2] "+v"(a2), [a3] "+v"(a3)
@@ -718,12 +495,9 @@ __global__ __launch_bounds__(NWAVES * 64, 1) void attn_bwd_dq_pipe2_kernel(AttnB
                  : ABWD64X2_DQ2_CLOBBERS);
     f32x16 dqa[2], dqb[2];
     ABWD64X2_READ_ACC_0(dqa[0]) ABWD64X2_READ_ACC_16(dqa[1]) ABWD64X2_READ_ACC_32(dqb[0]) ABWD64X2_READ_ACC_48(dqb[1])
-    __syncthreads();
-    int lane_e = lane;
-    asm volatile("" : "+v"(lane_e));
-    char* ob = smem + wave * 4096;
-    store_rows(dqa, LN2, ob, p.dq + bh * p.S_pad * 64, qblk * QB + wave * 64, p.S, lane_e);
-    store_rows(dqb, LN2, ob, p.dq + bh * p.S_pad * 64, qblk * QB + wave * 64 + 32, p.S, lane_e);
+    const OutStage o = epilogue_begin<HD, true>(smem, wave, lane);
+    store_rows<HD>(dqa, LN2, o, p.dq + bh * p.S_pad * 64, qblk * QB + wave * 64, p.S);
+    store_rows<HD>(dqb, LN2, o, p.dq + bh * p.S_pad * 64, qblk * QB + wave * 64 + 32, p.S);
 }
 
 }  // namespace

@@ -9,14 +9,6 @@
 namespace mi355 {
 namespace {
 
-__device__ __forceinline__ void unpack8(const uint4 u, float (&v)[8]) {
-    v[0] = bf_lo(u.x); v[1] = bf_hi(u.x); v[2] = bf_lo(u.y); v[3] = bf_hi(u.y);
-    v[4] = bf_lo(u.z); v[5] = bf_hi(u.z); v[6] = bf_lo(u.w); v[7] = bf_hi(u.w);
-}
-__device__ __forceinline__ uint4 pack8(const float (&v)[8]) {
-    return make_uint4(pack_bf16(v[0], v[1]), pack_bf16(v[2], v[3]), pack_bf16(v[4], v[5]), pack_bf16(v[6], v[7]));
-}
-
 // ------------------------------------------------------------------ LayerNorm + AdaLN-modulate backward
 // forward (ln_mod_kernel):  xn = LN(x) * (1 + scale[b]) + shift[b]   [, xn2 = LN(x) * (1 + scale2[b]) + shift2[b]]
 // backward w.r.t. x:        g  = dxn * (1 + scale) [+ dxn2 * (1 + scale2)]

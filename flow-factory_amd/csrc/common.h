@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 namespace mi355 {
 
@@ -52,6 +53,45 @@ __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
+}
+__device__ __forceinline__ float row16_sum_dpp(float v) {      // sum over the 16 lanes of a DPP row, in every lane
+    auto dpp = [](float x, auto ctrl) {
+        return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), decltype(ctrl)::value, 0xf, 0xf, false));
+    };
+    using std::integral_constant;
+    v += dpp(v, integral_constant<int, 0xB1>{});      // quad_perm [1,0,3,2]
+    v += dpp(v, integral_constant<int, 0x4E>{});      // quad_perm [2,3,0,1]
+    v += dpp(v, integral_constant<int, 0x141>{});     // row_half_mirror
+    v += dpp(v, integral_constant<int, 0x140>{});     // row_mirror
+    return v;
+}
+
+// 8 bf16 (one 16-byte access) <-> 8 floats
+__device__ __forceinline__ void unpack8(const uint4 u, float (&v)[8]) {
+    v[0] = bf_lo(u.x); v[1] = bf_hi(u.x); v[2] = bf_lo(u.y); v[3] = bf_hi(u.y);
+    v[4] = bf_lo(u.z); v[5] = bf_hi(u.z); v[6] = bf_lo(u.w); v[7] = bf_hi(u.w);
+}
+__device__ __forceinline__ uint4 pack8(const float (&v)[8]) {
+    return make_uint4(pack_bf16(v[0], v[1]), pack_bf16(v[2], v[3]), pack_bf16(v[4], v[5]), pack_bf16(v[6], v[7]));
+}
+
+// source / destination of an LDS-DMA load (__builtin_amdgcn_global_load_lds)
+typedef const __attribute__((address_space(1))) void* gptr_t;
+typedef __attribute__((address_space(3))) void* lptr_t;
+
+// XCD-aware work order: the hardware deals workgroup ids round-robin over the 8 XCDs (id % 8), each with a private L2.  Workgroup `wid` of
+// `nwg` takes the work item at its XCD's contiguous share of [0, nwg) + its turn on that XCD, so neighbouring items (the blocks of one
+// (batch, head), the tiles of one operand panel) hit the same L2.
+__device__ __forceinline__ int xcd_remap(int wid, int nwg) {
+    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = wid & 7;
+    return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (wid >> 3);
+}
+
+// The 32x32x16 MFMA's output row i (0..31) -> row offset inside the 32-row block its A operand is fed in: with this order the 16 accumulator
+// registers of a block, packed to bf16 in register order, ARE the B fragments of a second product (8 consecutive rows per lane)
+__device__ __forceinline__ int row_perm(int i) {
+    const int a = i >> 3, g = (i >> 2) & 1, b = i & 3;
+    return 16 * (a >> 1) + 8 * g + 4 * (a & 1) + b;
 }
 
 // storage-dtype load/store of a latent element (fp32 / bf16 / fp16)

@@ -60,21 +60,6 @@ __device__ __forceinline__ float wave_sum_dpp(float v) {
 // B*H addresses queue: measured 3-10 x the kernel's time): a wave walks NR_RPW consecutive rows of one sample with its running maxima in
 // registers and writes ONE partial row [H]; max_finalize_kernel reduces the partial rows.
 constexpr int NR_RPW = 8;
-__device__ __forceinline__ void unpack8(const uint4 u, float (&v)[8]) {
-    v[0] = bf_lo(u.x); v[1] = bf_hi(u.x); v[2] = bf_lo(u.y); v[3] = bf_hi(u.y);
-    v[4] = bf_lo(u.z); v[5] = bf_hi(u.z); v[6] = bf_lo(u.w); v[7] = bf_hi(u.w);
-}
-__device__ __forceinline__ float row16_sum_dpp(float v) {      // sum over the 16 lanes of a DPP row, in every lane
-    auto dpp = [](float x, auto ctrl) {
-        return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), decltype(ctrl)::value, 0xf, 0xf, false));
-    };
-    using std::integral_constant;
-    v += dpp(v, integral_constant<int, 0xB1>{});      // quad_perm [1,0,3,2]
-    v += dpp(v, integral_constant<int, 0x4E>{});      // quad_perm [2,3,0,1]
-    v += dpp(v, integral_constant<int, 0x141>{});     // row_half_mirror
-    v += dpp(v, integral_constant<int, 0x140>{});     // row_mirror
-    return v;
-}
 // FLUX.1 / Qwen-Image q | k producer: per-head RMSNorm + RoPE + head-major scatter.  One wave per token row, 4 heads per pass, a head per
 // 16-lane DPP row, 16 bytes per lane and access (the narrow form above -- one wave per (token, head), 4-byte accesses, two ds_bpermute
 // reductions -- ran at ~1.5 TB/s: 2.6-2.8 % of the FLUX.1 / Qwen-Image rollouts).  Same arithmetic per element; the per-head sums of

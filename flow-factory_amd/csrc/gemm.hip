@@ -79,8 +79,6 @@ struct Cfg {
     static_assert(BM % (8 * NW) == 0 && BN % (8 * NW) == 0, "glds group split");
 };
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 
 __device__ __forceinline__ void glds16(const void* src, char* lds_wave_base) {
     // 64 lanes x 16 B -> LDS [base + lane*16]; base must be wave-uniform
@@ -414,11 +412,7 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel(GemmParams p) {
     const int ntm = (p.M + BM - 1) / BM, ntn = (p.N + BN - 1) / BN;
     const int nsplit = (EPI == EPI_F32 && p.k_split > 1) ? p.k_split : 1;
     const int nblk = ntm * ntn * nsplit;
-    int bid = blockIdx.x;
-    {
-        const int q8 = nblk >> 3, r8 = nblk & 7, xcd = bid & 7;
-        bid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-    }
+    int bid = xcd_remap(blockIdx.x, nblk);
     const int split = bid / (ntm * ntn);          // (splits of one tile run on different XCDs: they share no operand bytes)
     bid -= split * (ntm * ntn);
     int tm, tn;
@@ -624,11 +618,7 @@ __global__ __launch_bounds__(256, 2) void gemm_mid_kernel(GemmParams p) {
 
     const int ntm = (p.M + BM - 1) / BM, ntn = (p.N + BN - 1) / BN;
     const int nblk = ntm * ntn;
-    int bid = blockIdx.x;
-    {   // consecutive tile ids -> one XCD (blockIdx % 8 is the XCD), as gemm_kernel
-        const int q8 = nblk >> 3, r8 = nblk & 7, xcd = bid & 7;
-        bid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-    }
+    int bid = xcd_remap(blockIdx.x, nblk);      // consecutive tile ids -> one XCD (blockIdx % 8 is the XCD), as gemm_kernel
     int tm, tn;
     tile_coords(bid, ntm, ntn, p.raster_gm, tm, tn);
     const int m0 = tm * BM, n0 = tn * BN;

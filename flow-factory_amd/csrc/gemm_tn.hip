@@ -26,8 +26,6 @@
 namespace mi355 {
 namespace {
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 
 constexpr int TM = 64;                       // m rows per tile
 constexpr int OP_BYTES = TM * 256;           // one operand tile: 64 rows x 128 columns bf16
@@ -128,11 +126,7 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(GemmTnParams p) {
     const int ntn = p.N / 128, ntk = p.K / 128;
     const int nsplit = p.k_split > 1 ? p.k_split : 1;
     const int nblk = ntn * ntk * nsplit;
-    int bid = blockIdx.x;
-    {
-        const int q8 = nblk >> 3, r8 = nblk & 7, xcd = bid & 7;
-        bid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-    }
+    int bid = xcd_remap(blockIdx.x, nblk);
     const int split = bid / (ntn * ntk);
     bid -= split * (ntn * ntk);
     const int tn = bid / ntk, tk = bid - tn * ntk;
@@ -261,11 +255,7 @@ __global__ __launch_bounds__(512) void gemm_tn256_kernel(GemmTnParams p) {
     const int ntn = p.N / 256, ntk = p.K / 256;
     const int nsplit = p.k_split > 1 ? p.k_split : 1;
     const int nblk = ntn * ntk * nsplit;
-    int bid = blockIdx.x;
-    {
-        const int q8 = nblk >> 3, r8 = nblk & 7, xcd = bid & 7;
-        bid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-    }
+    int bid = xcd_remap(blockIdx.x, nblk);
     const int split = bid / (ntn * ntk);
     bid -= split * (ntn * ntk);
     const int tn = bid / ntk, tk = bid - tn * ntk;
