@@ -1,6 +1,7 @@
 // mi355_flow -- host scaffolding shared by the engine translation units (engine.hip, flux_engine.hip, qwen_engine.hip, wan_engine.hip and the
 // two VAE engines): error propagation into mi355_last_error(), the zero-initialised GEMM descriptor, the weight arenas + name table of a
-// transformer engine (ParamTable), the two-phase workspace allocator (Carver) and the hipGraph of a captured rollout loop (RolloutGraph).
+// transformer engine (ParamTable), the weights of a double-stream block (DoubleW: FLUX.1 and Qwen-Image), the two-phase workspace allocator
+// (Carver) and the hipGraph of a captured rollout loop (RolloutGraph).
 #pragma once
 #include <string.h>
 
@@ -120,6 +121,15 @@ struct ParamTable {
             if (!kv.second.bound) return errorf("parameter '%s' has not been bound", kv.first.c_str());
         return 0;
     }
+};
+
+// weights of one double-stream block (FLUX.1 double blocks, Qwen-Image blocks): image stream, then the text stream's (c...) counterparts
+struct DoubleW {
+    bf16_t *w_qk, *w_v, *w_o, *w_cqk, *w_cv, *w_co, *w_ff1, *w_ff2, *w_cff1, *w_cff2;
+    float *b_qk, *b_v, *b_o, *b_cqk, *b_cv, *b_co, *b_ff1, *b_ff2, *b_cff1, *b_cff2;
+    float *nq, *nk, *ncq, *nck;
+    int mod_img, mod_ctx;     // first of the six modulation columns of each stream
+    float bound = 0.f;        // proven |score| bound of the block's attention (update_score_bounds)
 };
 
 // ---- device workspaces ------------------------------------------------------------------------------------------------------------------

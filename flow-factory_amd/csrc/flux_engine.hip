@@ -26,13 +26,6 @@ using namespace mi355;
 
 namespace {
 
-struct DoubleW {
-    bf16_t *w_qk, *w_v, *w_o, *w_cqk, *w_cv, *w_co, *w_ff1, *w_ff2, *w_cff1, *w_cff2;
-    float *b_qk, *b_v, *b_o, *b_cqk, *b_cv, *b_co, *b_ff1, *b_ff2, *b_cff1, *b_cff2;
-    float *nq, *nk, *ncq, *nck;
-    int mod_img, mod_ctx;
-    float bound = 0.f;     // proven |score| bound of the block's attention (update_score_bounds)
-};
 struct SingleW {
     bf16_t *w_qk, *w_v, *w_mlp, *w_out;
     float *b_qk, *b_v, *b_mlp, *b_out;
@@ -40,13 +33,8 @@ struct SingleW {
     int mod;
     float bound = 0.f;
 };
-// training-mode stash of one block (flux_train.inc owns the arrays; forward_core fills them): what the backward needs of the forward
-struct FTrainDbl {
-    bf16_t *x_in, *xn, *x_mid, *xn_mlp, *pre, *o_img;
-    bf16_t *c_in, *cn, *c_mid, *cn_mlp, *cpre, *o_ctx;
-    bf16_t *q, *k, *vT;
-    float *lse, *rstd_img, *rstd_ctx;
-};
+// training-mode stash of one single-stream block (flux_train.inc owns the arrays; forward_core fills them): what the backward needs of the
+// forward (a double-stream block's: DoubleStash, train_common.h)
 struct FTrainSgl {
     bf16_t *y_in, *yn, *pre, *o;
     bf16_t *q, *k, *vT;
@@ -54,9 +42,6 @@ struct FTrainSgl {
 };
 
 }  // namespace
-
-struct FluxTrainState;
-struct mi355_flux_train;
 
 struct mi355_flux : ParamTable {
     mi355_flux_cfg cfg;
@@ -68,15 +53,9 @@ struct mi355_flux : ParamTable {
     std::vector<SingleW> sgl;
     bool bounds_dirty = true;
     int bounds_ver = 0;          // bumped whenever the per-block score bounds are recomputed (they are baked into a captured graph)
-    FluxTrainState* train = nullptr;   // training-mode state (flux_train.inc), created on first use
+    EngineTrain* train = nullptr;      // training-mode state (flux_train.inc: FluxTrainState), created on first use
     void layout();
 };
-
-struct mi355_flux_plan;
-// training-mode state (flux_train.inc, included at the end of this file)
-static void flux_train_release(mi355_flux_plan* p);
-static void flux_train_release_engine(mi355_flux* e);
-static void flux_train_mark_dirty(mi355_flux* e);
 
 void mi355_flux::layout() {
     used16 = used32 = 0;
@@ -166,7 +145,7 @@ extern "C" int mi355_flux_create(const mi355_flux_cfg* cfg, mi355_flux** out) {
 
 extern "C" int mi355_flux_destroy(mi355_flux* e) {
     if (!e) return 0;
-    flux_train_release_engine(e);
+    delete e->train;
     e->release();
     delete e;
     return 0;
@@ -178,7 +157,7 @@ extern "C" int mi355_flux_bind_weight(mi355_flux* e, const char* name, const voi
     if (!e || !name || !src) return errorf("mi355_flux_bind_weight: null argument");
     CHK(e->bind("mi355_flux_bind_weight", name, src, dtype, ndim, shape, (hipStream_t)stream));
     if (strstr(name, ".norm_")) e->bounds_dirty = true;
-    flux_train_mark_dirty(e);          // the transposed copies the backward's dgrad GEMMs read are stale
+    engine_train_mark_dirty(e->train); // the transposed copies the backward's dgrad GEMMs read are stale
     return 0;
 }
 extern "C" int mi355_flux_weights_ready(mi355_flux* e) { return e ? e->ready() : errorf("null engine"); }
@@ -205,7 +184,7 @@ struct mi355_flux_plan {
     bf16_t *qkbuf_c = nullptr, *big_c = nullptr;
     std::vector<hipEvent_t> ev_join, ev_fork;   // per double block: text q|k|v ready (side -> main), attention done (main -> side); [L] = start / end
     RolloutGraph graph;                 // hipGraph of the N-step loop (mi355_tune_set key 16), captured on the second call of a configuration
-    mi355_flux_train* train = nullptr;  // training workspace (flux_train.inc), created by the first training-mode forward
+    PlanTrain* train = nullptr;         // training workspace (flux_train.inc: mi355_flux_train), created by the first training-mode forward
 };
 
 extern "C" int mi355_flux_plan_create(mi355_flux* e, int batch, int latent_h, int latent_w, int n_text, int max_steps,
@@ -268,7 +247,7 @@ extern "C" int mi355_flux_plan_create(mi355_flux* e, int batch, int latent_h, in
 
 extern "C" int mi355_flux_plan_destroy(mi355_flux_plan* p) {
     if (!p) return 0;
-    flux_train_release(p);
+    delete p->train;
     p->graph.release();
     for (hipEvent_t ev : p->ev_join) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : p->ev_fork) (void)hipEventDestroy(ev);
@@ -437,7 +416,7 @@ int flux_two_stream_init(mi355_flux_plan* p) {
 // log-sum-exp / 1/rms side outputs switched on, the MLP pre-activations stashed by the GEMM epilogue): the same kernel binaries on the same
 // values -- the velocity is bit-identical, so the replay log-prob equals the rollout's.
 int forward_core(mi355_flux_plan* p, hipStream_t st, const void* latents, int lat_dt, const bf16_t* mod, bf16_t* v_out,
-                 const FTrainDbl* dbl = nullptr, const FTrainSgl* sgl = nullptr, bf16_t* x_final = nullptr) {
+                 const DoubleStash* dbl = nullptr, const FTrainSgl* sgl = nullptr, bf16_t* x_final = nullptr) {
     mi355_flux* e = p->e;
     const int D = e->D, F = e->F, C = e->cfg.in_channels;
     const int Ni = p->Ni, Nt = p->Nt, S = p->S;
@@ -463,7 +442,7 @@ int forward_core(mi355_flux_plan* p, hipStream_t st, const void* latents, int la
     }
     for (int i = 0; i < e->L; ++i) {
         const DoubleW& b = e->dbl[i];
-        const FTrainDbl* tb = dbl ? dbl + i : nullptr;
+        const DoubleStash* tb = dbl ? dbl + i : nullptr;
         const int mi = b.mod_img, mc = b.mod_ctx;     // chunks: shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp
         bf16_t *xn = tb ? tb->xn : p->xn, *cn = tb ? tb->cn : p->cn;
         bf16_t *q = tb ? tb->q : p->q, *k = tb ? tb->k : p->k, *vT = tb ? tb->vT : p->vT;

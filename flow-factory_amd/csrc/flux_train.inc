@@ -19,54 +19,31 @@
 //   d[q|k|v]_pre  = (RMSNorm . RoPE)'(dq~, dk) | dv            rope_rms_bwd128 -> token-major, written BESIDE dpre in one [M][3D + F] buffer
 //   dyn   = [dq_pre | dk_pre | dv | dpre] . [W_q; W_k; W_v; W_mlp]     ONE dgrad GEMM with K = 3D + F = 7D
 //   dy    = dy' + LNmod'(y)(dyn)                               ln_mod_bwd (accumulating in place)
-// Double-stream blocks: the SD3.5 joint block's backward (engine_train.inc) with this file's head_dim-128 attention / RoPE pieces, context
-// rows first in the joint sequence, and an MLP on both streams.  Weight gradients: dW = dY^T . X as split-K GEMMs on transposed operands, bias
-// gradients as column sums taken by the dY transpose (the machinery of engine_train.inc).
+// Double-stream blocks: train_common.h's t_double_block_back (the one Qwen-Image runs) with context rows first in the joint sequence.  The
+// training state's life cycle, the set_grad family, the scratch carving and the per-layer backward helpers are train_common.h's too; this file
+// keeps FLUX.1's own program: the name scope, the single-stream block, the head and tail of the backward.  Weight gradients: dW = dY^T . X as
+// split-K GEMMs on transposed operands, bias gradients as column sums taken by the dY transpose.
 
-struct FDblWT { bf16_t *qkv, *o, *cqkv, *co, *ff1, *ff2, *cff1, *cff2; };   // transposed weights (dgrad operands)
-struct FSglWT { bf16_t *cat, *out; };                                       // [D][3D + F] = [W_q; W_k; W_v; W_mlp]^T and [D + F][D] = W_out^T
+namespace {
 
-struct FluxTrainState {      // per engine
-    char* arenaT = nullptr; size_t bytes = 0;
-    std::vector<FDblWT> dwt;
+struct FSglWT { bf16_t *cat, *out; };       // [D][3D + F] = [W_q; W_k; W_v; W_mlp]^T and [D + F][D] = W_out^T
+
+struct FluxTrainState : EngineTrain {      // per engine
+    std::vector<DoubleWT> dwt;
     std::vector<FSglWT> swt;
-    bf16_t* projT = nullptr;
-    bool dirty = true;
-    GradRegistry grads;
 };
-struct mi355_flux_train {    // per plan
-    mi355_flux_plan* p;
-    char* ws = nullptr; size_t ws_bytes = 0;
-    std::vector<FTrainDbl> dbl;
+struct mi355_flux_train : PlanTrain {      // per plan
+    std::vector<DoubleStash> dbl;
     std::vector<FTrainSgl> sgl;
     bf16_t *x_final, *mod;
-    bool have_forward = false;
-    // backward: residual-stream gradients + the shared scratch (train_common.h)
-    bf16_t *dyj, *dx, *dc, *dvb;
-    TrainScratch sc;
+    bf16_t *dyj, *dx, *dc, *dvb;            // backward: residual-stream gradients
     int M_pad, Mi_pad, Mc_pad;
 };
 
-static FluxTrainState* flux_train_state(mi355_flux* e) {      // created on first use
-    if (!e->train) e->train = new FluxTrainState();
-    return e->train;
-}
-static void flux_train_mark_dirty(mi355_flux* e) {
-    if (e->train) e->train->dirty = true;
-}
-static void flux_train_release(mi355_flux_plan* p) {
-    if (!p->train) return;
-    t_wgrad_streams_destroy(p->train->sc);
-    if (p->train->ws) (void)hipFree(p->train->ws);
-    delete p->train;
-    p->train = nullptr;
-}
-static void flux_train_release_engine(mi355_flux* e) {
-    if (!e->train) return;
-    if (e->train->arenaT) (void)hipFree(e->train->arenaT);
-    delete e->train;
-    e->train = nullptr;
-}
+}  // namespace
+
+static FluxTrainState* flux_train_state(mi355_flux* e) { return engine_train_state<FluxTrainState>(e->train); }
+static const DoubleBackSched kFluxDouble{false, ".ff", ".ff_context", false};
 
 static bool flux_trainable_name(const std::string& n) {
     static const char* dbl_ok[] = {".attn.to_q.", ".attn.to_k.", ".attn.to_v.", ".attn.to_out.0.", ".attn.add_q_proj.", ".attn.add_k_proj.",
@@ -87,39 +64,17 @@ static bool flux_trainable_name(const std::string& n) {
 
 // fp32 gradient buffer (same shape as the parameter, caller-owned, OVERWRITTEN by every backward); NULL un-registers
 extern "C" int mi355_flux_set_grad(mi355_flux* e, const char* name, float* grad) {
-    if (!e || !name) return errorf("mi355_flux_set_grad: null argument");
-    if (e->slots.find(name) == e->slots.end()) return errorf("mi355_flux_set_grad: unknown parameter '%s'", name);
-    if (grad && !flux_trainable_name(name))
-        return errorf("mi355_flux_set_grad: '%s' lies outside the native backward's scope (the linear layers inside the transformer blocks)", name);
-    flux_train_state(e)->grads.set(name, grad);
-    return 0;
+    return t_set_grad<FluxTrainState>(e, "mi355_flux", flux_trainable_name, name, grad);
 }
 // the same with the buffer's dtype: MI355_F32, or MI355_BF16 for the weights / biases of the linear layers inside the transformer blocks (the
 // kernels that finish those gradients round their fp32 sums to bf16 on the way out: the values of `fp32 buffer -> bf16`, minus the round trip)
 extern "C" int mi355_flux_set_grad_typed(mi355_flux* e, const char* name, void* grad, int dtype) {
-    if (dtype == DT_F32 || !grad) return mi355_flux_set_grad(e, name, (float*)grad);
-    if (dtype != DT_BF16) return errorf("mi355_flux_set_grad_typed: gradient buffers are fp32 or bf16 (dtype %d)", dtype);
-    if (!e || !name) return errorf("mi355_flux_set_grad_typed: null argument");
-    if (!flux_trainable_name(name)) return errorf("mi355_flux_set_grad_typed: bf16 gradient buffers are limited to the linear layers inside the transformer blocks ('%s')", name);
-    const int rc = mi355_flux_set_grad(e, name, (float*)grad);
-    if (rc == 0) grad_buf_mark(grad, DT_BF16);
-    return rc;
+    return t_set_grad_typed<FluxTrainState>(e, "mi355_flux", flux_trainable_name, name, grad, dtype);
 }
-extern "C" int mi355_flux_clear_grads(mi355_flux* e) {
-    if (!e) return errorf("null engine");
-    flux_train_state(e)->grads.clear();
-    return 0;
-}
+extern "C" int mi355_flux_clear_grads(mi355_flux* e) { return t_clear_grads<FluxTrainState>(e); }
 // 0 = the native backward produces a gradient for `name`, 1 = it does not
-extern "C" int mi355_flux_grad_supported(mi355_flux* e, const char* name) {
-    if (!e || !name || !e->slots.count(name)) return 1;
-    return flux_trainable_name(name) ? 0 : 1;
-}
-extern "C" int64_t mi355_flux_plan_training_bytes(mi355_flux_plan* p) {
-    return p && p->train ? (int64_t)p->train->ws_bytes : 0;
-}
-
-static float* fgrad_of(mi355_flux* e, const std::string& name) { return flux_train_state(e)->grads.find(name); }
+extern "C" int mi355_flux_grad_supported(mi355_flux* e, const char* name) { return t_grad_supported(e, flux_trainable_name, name); }
+extern "C" int64_t mi355_flux_plan_training_bytes(mi355_flux_plan* p) { return p && p->train ? (int64_t)p->train->ws_bytes : 0; }
 
 // ---- transposed weights -------------------------------------------------------------------------------------------
 static int flux_ensure_transposed(mi355_flux* e, hipStream_t st) {
@@ -128,30 +83,15 @@ static int flux_ensure_transposed(mi355_flux* e, hipStream_t st) {
     if (!s->arenaT) {
         Carver c;
         s->dwt.resize(L); s->swt.resize(LS);
-        for (FDblWT& w : s->dwt) {
-            c.take(w.qkv, (int64_t)D * 3 * D); c.take(w.o, (int64_t)D * D); c.take(w.cqkv, (int64_t)D * 3 * D); c.take(w.co, (int64_t)D * D);
-            c.take(w.ff1, (int64_t)D * F); c.take(w.ff2, (int64_t)F * D); c.take(w.cff1, (int64_t)D * F); c.take(w.cff2, (int64_t)F * D);
-        }
+        for (DoubleWT& w : s->dwt) t_double_wt_take(c, w, D, F);
         for (FSglWT& w : s->swt) { c.take(w.cat, (int64_t)D * (3 * D + F)); c.take(w.out, (int64_t)(D + F) * D); }
         c.take(s->projT, (int64_t)D * C);
         CHK(c.alloc(&s->arenaT, &s->bytes, false, "flux training", " for the transposed weights"));
         s->dirty = true;
     }
     if (!s->dirty) return 0;
-    // W [rows][cols] -> out[c][col0 + r] with row stride ld_out
-    auto tr = [&](const bf16_t* w, int rows, int cols, bf16_t* out, long ld_out, int col0) {
-        return launch_transpose(w, cols, 0, out + col0, ld_out, 0, rows, cols, rows, 1, st);
-    };
-    for (int i = 0; i < L; ++i) {
-        const DoubleW& b = e->dbl[i];
-        FDblWT& w = s->dwt[i];
-        HIPCHK(tr(b.w_qk, 2 * D, D, w.qkv, 3 * D, 0)); HIPCHK(tr(b.w_v, D, D, w.qkv, 3 * D, 2 * D));
-        HIPCHK(tr(b.w_o, D, D, w.o, D, 0));
-        HIPCHK(tr(b.w_cqk, 2 * D, D, w.cqkv, 3 * D, 0)); HIPCHK(tr(b.w_cv, D, D, w.cqkv, 3 * D, 2 * D));
-        HIPCHK(tr(b.w_co, D, D, w.co, D, 0));
-        HIPCHK(tr(b.w_ff1, F, D, w.ff1, F, 0)); HIPCHK(tr(b.w_ff2, D, F, w.ff2, D, 0));
-        HIPCHK(tr(b.w_cff1, F, D, w.cff1, F, 0)); HIPCHK(tr(b.w_cff2, D, F, w.cff2, D, 0));
-    }
+    auto tr = [&](const bf16_t* w, int rows, int cols, bf16_t* out, long ld_out, int col0) { return t_transpose_weight(w, rows, cols, out, ld_out, col0, st); };
+    for (int i = 0; i < L; ++i) CHK(t_double_wt_fill(e->dbl[i], s->dwt[i], D, F, st));
     for (int i = 0; i < LS; ++i) {
         const SingleW& b = e->sgl[i];
         FSglWT& w = s->swt[i];
@@ -166,29 +106,22 @@ static int flux_ensure_transposed(mi355_flux* e, hipStream_t st) {
 
 // ---- training workspace ----------------------------------------------------------------------------------------------
 static int flux_train_of(mi355_flux_plan* p, mi355_flux_train** out) {
-    if (p->train) { *out = p->train; return 0; }
+    if (p->train) { *out = static_cast<mi355_flux_train*>(p->train); return 0; }
     mi355_flux* e = p->e;
     const int D = e->D, F = e->F, L = e->L, LS = e->LS, H = e->H, C = e->cfg.in_channels;
     const int Mi = p->Mi, Mc = p->Mc, M = p->M;
     const int64_t qk_el = (int64_t)p->B * H * p->S_pad * 128;
+    const int64_t bhs = (int64_t)p->B * H * p->S_pad;
     mi355_flux_train* t = new mi355_flux_train();
-    t->p = p;
     t->M_pad = (M + 63) / 64 * 64; t->Mi_pad = (Mi + 63) / 64 * 64; t->Mc_pad = (Mc + 63) / 64 * 64;
     TrainScratch& sc = t->sc;
     Carver c;
     t->dbl.resize(L); t->sgl.resize(LS);
-    for (FTrainDbl& k : t->dbl) {
-        c.take(k.x_in, (int64_t)Mi * D); c.take(k.xn, (int64_t)Mi * D); c.take(k.x_mid, (int64_t)Mi * D); c.take(k.xn_mlp, (int64_t)Mi * D);
-        c.take(k.pre, (int64_t)Mi * F); c.take(k.o_img, (int64_t)Mi * D);
-        c.take(k.c_in, (int64_t)Mc * D); c.take(k.cn, (int64_t)Mc * D); c.take(k.c_mid, (int64_t)Mc * D); c.take(k.cn_mlp, (int64_t)Mc * D);
-        c.take(k.cpre, (int64_t)Mc * F); c.take(k.o_ctx, (int64_t)Mc * D);
-        c.take(k.q, qk_el); c.take(k.k, qk_el); c.take(k.vT, qk_el);
-        c.take(k.lse, (int64_t)p->B * H * p->S_pad); c.take(k.rstd_img, (int64_t)Mi * 2 * H); c.take(k.rstd_ctx, (int64_t)Mc * 2 * H);
-    }
+    for (DoubleStash& k : t->dbl) t_double_stash_take(c, k, Mi, Mc, D, F, H, qk_el, bhs);
     for (FTrainSgl& k : t->sgl) {
         c.take(k.y_in, (int64_t)M * D); c.take(k.yn, (int64_t)M * D); c.take(k.pre, (int64_t)M * F); c.take(k.o, (int64_t)M * D);
         c.take(k.q, qk_el); c.take(k.k, qk_el); c.take(k.vT, qk_el);
-        c.take(k.lse, (int64_t)p->B * H * p->S_pad); c.take(k.rstd, (int64_t)M * 2 * H);
+        c.take(k.lse, bhs); c.take(k.rstd, (int64_t)M * 2 * H);
     }
     c.take(t->x_final, (int64_t)Mi * D); c.take(t->mod, (int64_t)p->B * e->mod_cols);
     c.take(t->dyj, (int64_t)M * D); c.take(t->dx, (int64_t)Mi * D); c.take(t->dc, (int64_t)Mc * D);
@@ -196,17 +129,8 @@ static int flux_train_of(mi355_flux_plan* p, mi355_flux_train** out) {
     c.take(sc.g3, (int64_t)M * D); c.take(sc.g3c, (int64_t)Mc * D);
     c.take(sc.wide, (int64_t)M * (3 * D + F)); c.take(sc.widec, (int64_t)Mc * (3 * D + F)); c.take(sc.hid, (int64_t)M * F);
     c.take(t->dvb, (int64_t)Mi * C);
-    c.take(sc.doh, qk_el); c.take(sc.v, qk_el); c.take(sc.dq, qk_el); c.take(sc.dk, qk_el); c.take(sc.dvh, qk_el);
-    c.take(sc.delta, (int64_t)p->B * H * p->S_pad); c.take(sc.nld, (int64_t)p->B * H * p->S_pad * 2);
-    const int n_slots = get_wgrad_side() ? WG_SLOTS : 1;
-    for (int i = 0; i < n_slots; ++i) { c.take(sc.slot[i].aT, (int64_t)F * t->M_pad); c.take(sc.slot[i].xT, (int64_t)(D + F) * t->M_pad); }
-    sc.part_floats = (size_t)16 * D * D > (size_t)2 * F * D ? (size_t)16 * D * D : (size_t)2 * F * D;
-    const int nrt = t->M_pad / 64 > 64 ? t->M_pad / 64 : 64;
-    c.take(sc.part, (int64_t)sc.part_floats); c.take(sc.csum, (int64_t)nrt * F); c.take(sc.zero_bias, 3 * D + F);
-    c.take(sc.hid_c, (int64_t)Mc * F); c.take(sc.csum_c, (int64_t)(t->Mc_pad / 64 > 64 ? t->Mc_pad / 64 : 64) * F);
-    if (c.alloc(&t->ws, &t->ws_bytes, true, "flux training", " of activation stash + backward scratch") != 0) { delete t; return 1; }
-    sc.aT_rows = F; sc.xT_rows = D + F;
-    if (t_wgrad_streams_init(sc, n_slots > 1) != 0) { t_wgrad_streams_destroy(sc); (void)hipFree(t->ws); delete t; return 1; }   // (mi355_last_error: the failing HIP call)
+    // operand slots: the widest dY group is [M][F], the widest layer input the single blocks' [o | gelu(pre)]
+    CHK(t_train_alloc(c, t, "flux training", ScratchSizes{D, F, qk_el, qk_el, bhs, F, D + F, t->M_pad, 3 * D + F, Mc}));
     p->train = t;
     *out = t;
     return 0;
@@ -242,7 +166,7 @@ extern "C" int mi355_flux_forward_train(mi355_flux_plan* p, void* stream, const 
 extern "C" int mi355_flux_backward(mi355_flux_plan* p, void* stream, const float* dv) {
     if (!p || !dv) return errorf("mi355_flux_backward: null argument");
     if (!p->train || !p->train->have_forward) return errorf("mi355_flux_backward: no training-mode forward has run on this plan");
-    mi355_flux_train* t = p->train;
+    mi355_flux_train* t = static_cast<mi355_flux_train*>(p->train);
     mi355_flux* e = p->e;
     hipStream_t st = (hipStream_t)stream;
     CHK(flux_ensure_transposed(e, st));
@@ -254,20 +178,14 @@ extern "C" int mi355_flux_backward(mi355_flux_plan* p, void* stream, const float
     const size_t rowb = (size_t)D * 2;
     TrainScratch& sc = t->sc;
     const AttnGeom ag{p->B, e->H, D, S, p->S_pad, p->cs, nullptr};
-    auto GD = [&](int i, const char* leaf) { return fgrad_of(e, "transformer_blocks." + std::to_string(i) + leaf); };
-    auto GS = [&](int i, const char* leaf) { return fgrad_of(e, "single_transformer_blocks." + std::to_string(i) + leaf); };
-    auto ln_back_on = [&](hipStream_t s_, const bf16_t* x, const bf16_t* dy, bf16_t* dres, int Mr, int rps, int shift_off, int scale_off,
-                          int accumulate) -> hipError_t {
-        LnModBwdParams l{x, dy, nullptr, dres, mod, mld, scale_off, 0, Mr, D, rps, e->cfg.eps, accumulate, nullptr, shift_off, 0};
-        return launch_ln_mod_bwd(l, s_);
-    };
-    auto ln_back = [&](const bf16_t* x, const bf16_t* dy, bf16_t* dres, int Mr, int rps, int shift_off, int scale_off, int accumulate) -> hipError_t {
-        return ln_back_on(st, x, dy, dres, Mr, rps, shift_off, scale_off, accumulate);
-    };
+    const ModRows mr{mod, mld, e->cfg.eps};
+    const TrainChain joint{st, M, t->M_pad, S, sc.g1, sc.g2, sc.g3, sc.wide, sc.hid, false};
+    const TrainChain im{st, Mi, t->Mi_pad, Ni, sc.g1, sc.g2, sc.g3, sc.wide, sc.hid, false};
+    auto GS = [&](int i, const char* leaf) { return ts->grads.find("single_transformer_blocks." + std::to_string(i) + leaf); };
     // ---- proj_out and norm_out (AdaLayerNormContinuous: scale first)
     HIPCHK(launch_convert(dv, DT_F32, t->dvb, DT_BF16, (long)Mi * C, st));
     CHK(t_dgrad(sc, st, t->dvb, C, C, ts->projT, Mi, D, sc.g3, D, nullptr, 0));
-    HIPCHK(ln_back(t->x_final, sc.g3, t->dx, Mi, Ni, e->mod_out + D, e->mod_out, 0));
+    CHK(t_ln_back(im, mr, D, t->x_final, sc.g3, t->dx, e->mod_out + D, e->mod_out, 0));
     // ---- joint stream gradient: the text rows of the last single block's output have no consumer
     HIPCHK(hipMemsetAsync(t->dyj, 0, (size_t)M * rowb, st));
     HIPCHK(hipMemcpy2DAsync(t->dyj + (size_t)Nt * D, (size_t)S * rowb, t->dx, (size_t)Ni * rowb, (size_t)Ni * rowb, p->B, hipMemcpyDeviceToDevice, st));
@@ -297,148 +215,28 @@ extern "C" int mi355_flux_backward(mi355_flux_plan* p, void* stream, const float
             CHK(t_wgrad_group(sc, st, sc.wide, ldw, sg, 4, &xy, 1, M, t->M_pad));
         }
         CHK(t_dgrad(sc, st, sc.wide, ldw, 3 * D + F, w.cat, M, D, sc.g3, D, nullptr, 0));
-        HIPCHK(ln_back(k.y_in, sc.g3, t->dyj, M, S, m0, m0 + D, 1));
+        CHK(t_ln_back(joint, mr, D, k.y_in, sc.g3, t->dyj, m0, m0 + D, 1));
     }
     // ---- split the joint gradient: context rows first
     HIPCHK(hipMemcpy2DAsync(t->dc, (size_t)Nt * rowb, t->dyj, (size_t)S * rowb, (size_t)Nt * rowb, p->B, hipMemcpyDeviceToDevice, st));
     HIPCHK(hipMemcpy2DAsync(t->dx, (size_t)Ni * rowb, t->dyj + (size_t)Nt * D, (size_t)S * rowb, (size_t)Ni * rowb, p->B, hipMemcpyDeviceToDevice, st));
     // The text chain of the double blocks on the plan's side stream (key 28; the stream and events of the forward's text chain, key 14's size
-    // rule; only with the weight-gradient stream, whose events order the shared operand slots): join before the joint attention backward, fork
-    // after it.  Per-chain scratch: g?c, widec, hid_c, csum_c.  Same kernels and operands: bit-identical to the in-line order.
+    // rule; only with the weight-gradient stream, whose events order the shared operand slots).  Per-chain scratch: g?c, widec, hid_c, csum_c.
     const bool two = get_train_text_side() != 0 && flux_two_stream_wanted(p) && sc.wside != nullptr && e->L > 0;
     if (two) CHK(flux_two_stream_init(p));
-    hipStream_t cs = two ? p->side : st;
-    bf16_t* hid_c = two ? sc.hid_c : sc.hid;
-    if (two) {          // d c / d x (split above), the stash and the transposed weights are complete on `st`
-        HIPCHK(ev_record(p->ev_fork[e->L], st));
-        HIPCHK(ev_wait(cs, p->ev_fork[e->L]));
-    }
-    for (int i = e->L - 1; i >= 0; --i) {
-        const DoubleW& b = e->dbl[i];
-        const FTrainDbl& k = t->dbl[i];
-        const FDblWT& w = ts->dwt[i];
-        const int mi = b.mod_img, mc = b.mod_ctx;
-        bf16_t* dpre = sc.wide + (size_t)Mi * 3 * D;         // [Mi][F] behind the [Mi][3D] q|k|v gradient
-        bf16_t* dpre_c = sc.widec + (size_t)Mc * 3 * D;
-        // ---- MLP, image stream
-        HIPCHK(launch_gate_mul(t->dx, mod + mi + 5 * D, mld, sc.g1, Mi, D, Ni, st));
-        if (GD(i, ".ff.net.2.weight") || GD(i, ".ff.net.2.bias")) {
-            if (GD(i, ".ff.net.2.weight")) HIPCHK(launch_gelu_fwd(k.pre, sc.hid, (long)Mi * F, st));
-            CHK(t_wgrad(sc, st, sc.g1, D, 0, D, sc.hid, F, F, Mi, t->Mi_pad, GD(i, ".ff.net.2.weight"), GD(i, ".ff.net.2.bias")));
-        }
-        CHK(t_dgrad(sc, st, sc.g1, D, D, w.ff2, Mi, F, dpre, F, k.pre, F));
-        if (GD(i, ".ff.net.0.proj.weight") || GD(i, ".ff.net.0.proj.bias"))
-            CHK(t_wgrad(sc, st, dpre, F, 0, F, k.xn_mlp, D, D, Mi, t->Mi_pad, GD(i, ".ff.net.0.proj.weight"), GD(i, ".ff.net.0.proj.bias")));
-        CHK(t_dgrad(sc, st, dpre, F, F, w.ff1, Mi, D, sc.g3, D, nullptr, 0));
-        HIPCHK(ln_back(k.x_mid, sc.g3, t->dx, Mi, Ni, mi + 3 * D, mi + 4 * D, 1));
-        // ---- MLP, context stream
-        HIPCHK(launch_gate_mul(t->dc, mod + mc + 5 * D, mld, sc.g1c, Mc, D, Nt, cs));
-        if (GD(i, ".ff_context.net.2.weight") || GD(i, ".ff_context.net.2.bias")) {
-            if (GD(i, ".ff_context.net.2.weight")) HIPCHK(launch_gelu_fwd(k.cpre, hid_c, (long)Mc * F, cs));
-            CHK(t_wgrad(sc, cs, sc.g1c, D, 0, D, hid_c, F, F, Mc, t->Mc_pad, GD(i, ".ff_context.net.2.weight"), GD(i, ".ff_context.net.2.bias"), two));
-        }
-        CHK(t_dgrad(sc, cs, sc.g1c, D, D, w.cff2, Mc, F, dpre_c, F, k.cpre, F));
-        if (GD(i, ".ff_context.net.0.proj.weight") || GD(i, ".ff_context.net.0.proj.bias"))
-            CHK(t_wgrad(sc, cs, dpre_c, F, 0, F, k.cn_mlp, D, D, Mc, t->Mc_pad, GD(i, ".ff_context.net.0.proj.weight"),
-                       GD(i, ".ff_context.net.0.proj.bias"), two));
-        CHK(t_dgrad(sc, cs, dpre_c, F, F, w.cff1, Mc, D, sc.g3c, D, nullptr, 0));
-        HIPCHK(ln_back_on(cs, k.c_mid, sc.g3c, t->dc, Mc, Nt, mc + 3 * D, mc + 4 * D, 1));
-        // ---- joint attention: out-projections of both streams
-        HIPCHK(launch_gate_mul(t->dx, mod + mi + 2 * D, mld, sc.g1, Mi, D, Ni, st));
-        if (GD(i, ".attn.to_out.0.weight") || GD(i, ".attn.to_out.0.bias"))
-            CHK(t_wgrad(sc, st, sc.g1, D, 0, D, k.o_img, D, D, Mi, t->Mi_pad, GD(i, ".attn.to_out.0.weight"), GD(i, ".attn.to_out.0.bias")));
-        CHK(t_dgrad(sc, st, sc.g1, D, D, w.o, Mi, D, sc.g2, D, nullptr, 0));
-        HIPCHK(launch_gate_mul(t->dc, mod + mc + 2 * D, mld, sc.g1c, Mc, D, Nt, cs));
-        if (GD(i, ".attn.to_add_out.weight") || GD(i, ".attn.to_add_out.bias"))
-            CHK(t_wgrad(sc, cs, sc.g1c, D, 0, D, k.o_ctx, D, D, Mc, t->Mc_pad, GD(i, ".attn.to_add_out.weight"), GD(i, ".attn.to_add_out.bias"), two));
-        CHK(t_dgrad(sc, cs, sc.g1c, D, D, w.co, Mc, D, sc.g2c, D, nullptr, 0));
-        if (two) {      // join: the attention backward reads the text rows' dO (and the previous block's text chain has read dq / dk / dv)
-            HIPCHK(ev_record(p->ev_join[i], cs));
-            HIPCHK(ev_wait(st, p->ev_join[i]));
-        }
-        CHK(t_attention128_backward(sc, ag, st, k.q, k.k, k.vT, k.lse, k.o_ctx, k.o_img, sc.g2c, sc.g2, Nt));
-        if (two) {      // fork: dq / dk / dv are written
-            HIPCHK(ev_record(p->ev_fork[i], st));
-            HIPCHK(ev_wait(cs, p->ev_fork[i]));
-        }
-        CHK(t_rope_back(sc, ag, cs, k.q, k.k, k.rstd_ctx, b.ncq, b.nck, sc.widec, 3 * D, Mc, Nt, 0));
-        CHK(t_rope_back(sc, ag, st, k.q, k.k, k.rstd_img, b.nq, b.nk, sc.wide, 3 * D, Mi, Ni, Nt));
-        {
-            const char* nm[3] = {".attn.to_q", ".attn.to_k", ".attn.to_v"};
-            const char* cn[3] = {".attn.add_q_proj", ".attn.add_k_proj", ".attn.add_v_proj"};
-            WgradSeg si[3], sx[3];
-            for (int j = 0; j < 3; ++j) {
-                si[j] = WgradSeg{j * D, D, GD(i, (std::string(nm[j]) + ".weight").c_str()), GD(i, (std::string(nm[j]) + ".bias").c_str())};
-                sx[j] = WgradSeg{j * D, D, GD(i, (std::string(cn[j]) + ".weight").c_str()), GD(i, (std::string(cn[j]) + ".bias").c_str())};
-            }
-            const WgradX xi{k.xn, D, D}, xc{k.cn, D, D};
-            CHK(t_wgrad_group(sc, st, sc.wide, 3 * D, si, 3, &xi, 1, Mi, t->Mi_pad));
-            CHK(t_wgrad_group(sc, cs, sc.widec, 3 * D, sx, 3, &xc, 1, Mc, t->Mc_pad, two));
-        }
-        CHK(t_dgrad(sc, st, sc.wide, 3 * D, 3 * D, w.qkv, Mi, D, sc.g3, D, nullptr, 0));
-        CHK(t_dgrad(sc, cs, sc.widec, 3 * D, 3 * D, w.cqkv, Mc, D, sc.g3c, D, nullptr, 0));
-        HIPCHK(ln_back(k.x_in, sc.g3, t->dx, Mi, Ni, mi, mi + D, 1));
-        HIPCHK(ln_back_on(cs, k.c_in, sc.g3c, t->dc, Mc, Nt, mc, mc + D, 1));
-    }
-    if (two) {          // the caller's stream goes on only after the text chain
-        HIPCHK(ev_record(p->ev_join[e->L], cs));
-        HIPCHK(ev_wait(st, p->ev_join[e->L]));
-    }
+    const TrainChain tx{two ? p->side : st, Mc, t->Mc_pad, Nt, sc.g1c, sc.g2c, sc.g3c, sc.widec, two ? sc.hid_c : sc.hid, two};
+    CHK(t_double_blocks_back(sc, kFluxDouble, ag, F, mr, e->L, e->dbl.data(), t->dbl.data(), ts->dwt.data(), ts->grads, im, tx, t->dx, t->dc,
+                             p->ev_join.data(), p->ev_fork.data()));
     CHK(t_wgrad_join(sc, st));
     return 0;
 }
 
 // ---- operator-level entry points (unit tests of the new kernels) -----------------------------------------------------------------------
-// attention forward (with log-sum-exp) + backward, head_dim 128: q (already scaled by log2(e)/sqrt(128)), k [B][H][S_pad][128], vT
-// [B][H][128][S_pad]; d_o token-major [B*S][H*128] -> o [B*S][H*128], dq, dk, dv [B][H][S_pad][128].  score_bound as mi355_op_attention128
-// (mi355_tune_set(21, .)).  Scratch is allocated and freed inside (test helper, synchronises).
-extern "C" int mi355_op_attention128_fwd_bwd(void* stream, const void* q, const void* k, const void* vT, const void* d_o, void* o, void* dq, void* dk,
-                                             void* dv, int B, int H, int S, int S_pad) {
-    if (!q || !k || !vT || !d_o || !o || !dq || !dk || !dv) return errorf("mi355_op_attention128_fwd_bwd: null argument");
-    hipStream_t st = (hipStream_t)stream;
-    const size_t el = (size_t)B * H * S_pad * 128, bhs = (size_t)B * H * S_pad;
-    char* ws = nullptr;
-    const size_t bytes = el * 2 * 2 + bhs * 4 * 4;
-    HIPCHK(hipMalloc((void**)&ws, bytes));
-    HIPCHK(hipMemsetAsync(ws, 0, bytes, st));
-    bf16_t* doh = (bf16_t*)ws; bf16_t* v = doh + el;
-    float* lse = (float*)(v + el); float* delta = lse + bhs; float* nld = delta + bhs;
-    const long D = (long)H * 128;
-    Attn128Params a;
-    memset(&a, 0, sizeof(a));
-    a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.vT = (const bf16_t*)vT; a.o_first = (bf16_t*)o; a.ld_first = D; a.n_first = S;
-    a.o_rest = nullptr; a.ld_rest = D; a.B = B; a.H = H; a.S = S; a.S_pad = S_pad; a.q_prescaled = 1;
-    a.score_bound = (float)get_attn128_op_bound(); a.lse = lse;
-    hipError_t err = launch_attention128(a, st);
-    Attn128BwdPrepParams pp;
-    memset(&pp, 0, sizeof(pp));
-    pp.o_first = (const bf16_t*)o; pp.ld_o_first = D; pp.do_first = (const bf16_t*)d_o; pp.ld_do_first = D; pp.n_first = S;
-    pp.lse = lse; pp.doh = doh; pp.delta = delta; pp.nld = nld; pp.B = B; pp.H = H; pp.S = S; pp.S_pad = S_pad;
-    if (err == hipSuccess) err = launch_attn128_bwd_prep(pp, st);
-    const long hs = (long)S_pad * 128;
-    if (err == hipSuccess) err = launch_transpose((const bf16_t*)vT, S_pad, hs, v, 128, hs, 128, S_pad, 128, B * H, st);
-    AttnBwdParams ab{(const bf16_t*)q, (const bf16_t*)k, v, doh, lse, delta, nld, (bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv, B, H, S, S_pad};
-    if (err == hipSuccess) err = launch_attention128_bwd(ab, st);
-    if (err == hipSuccess) err = hipStreamSynchronize(st);
-    (void)hipFree(ws);
-    if (err != hipSuccess) return errorf("mi355_op_attention128_fwd_bwd: %s", hipGetErrorString(err));
-    return 0;
-}
-
-// The same with the fields the helper above pins exposed: cross-attention and ragged keys (as mi355_op_attention128_ex; k, vT, dk, dv are then
-// [B][H][S_kv_pad][128] / [B][H][128][S_kv_pad]), the first / rest split of o and dO with their row strides (Attn128BwdPrepParams; do_rest may be
-// NULL: that part of the output has no consumer), the |score| bound as an argument, and optional copies of the forward's log2-sum-exp and of the
-// backward's delta = rowsum(dO * O), both [B][H][S_pad] fp32 (rows >= S: zero, as the zeroed scratch holds them).
-extern "C" int mi355_op_attention128_fwd_bwd_ex(void* stream, const void* q, const void* k, const void* vT, const void* do_first, const void* do_rest,
-                                                void* o_first, void* o_rest, int64_t ld_first, int64_t ld_rest, int n_first, void* dq, void* dk, void* dv,
-                                                int B, int H, int S, int S_pad, int S_kv, int S_kv_pad, const void* kv_len, int kv_len_n,
-                                                float score_bound, float* lse_out, float* delta_out) {
-    const char* who = "mi355_op_attention128_fwd_bwd_ex";
-    if (!q || !k || !vT || !dq || !dk || !dv) return errorf("%s: null argument", who);
-    if (attn128_ex_check(who, B, H, S, S_pad, n_first, S_kv, S_kv_pad, kv_len, kv_len_n, score_bound)) return 1;
-    if (n_first > 0 && (!o_first || !do_first || ld_first < (int64_t)H * 128)) return errorf("%s: o_first / do_first is NULL or ld_first < H * 128", who);
-    if (n_first < S && (!o_rest || ld_rest < (int64_t)H * 128)) return errorf("%s: o_rest is NULL or ld_rest < H * 128", who);
-    hipStream_t st = (hipStream_t)stream;
+// attention forward (with log-sum-exp) + backward, head_dim 128, for both entry points below (`who`, for the messages).  Scratch is allocated
+// and freed inside (test helper, synchronises).
+static int op_attention128_fwd_bwd(const char* who, hipStream_t st, const void* q, const void* k, const void* vT, const void* do_first, const void* do_rest,
+                                   void* o_first, void* o_rest, int64_t ld_first, int64_t ld_rest, int n_first, void* dq, void* dk, void* dv, int B, int H,
+                                   int S, int S_pad, int S_kv, int S_kv_pad, const void* kv_len, float score_bound, float* lse_out, float* delta_out) {
     const int Skp = S_kv > 0 ? S_kv_pad : S_pad;
     const size_t el = (size_t)B * H * S_pad * 128, elk = (size_t)B * H * Skp * 128, bhs = (size_t)B * H * S_pad;
     char* ws = nullptr;
@@ -470,6 +268,33 @@ extern "C" int mi355_op_attention128_fwd_bwd_ex(void* stream, const void* q, con
     (void)hipFree(ws);
     if (err != hipSuccess) return errorf("%s: %s", who, hipGetErrorString(err));
     return 0;
+}
+
+// q (already scaled by log2(e)/sqrt(128)), k [B][H][S_pad][128], vT [B][H][128][S_pad]; d_o token-major [B*S][H*128] -> o [B*S][H*128],
+// dq, dk, dv [B][H][S_pad][128].  score_bound as mi355_op_attention128 (mi355_tune_set(21, .)).
+extern "C" int mi355_op_attention128_fwd_bwd(void* stream, const void* q, const void* k, const void* vT, const void* d_o, void* o, void* dq, void* dk,
+                                             void* dv, int B, int H, int S, int S_pad) {
+    const char* who = "mi355_op_attention128_fwd_bwd";
+    if (!q || !k || !vT || !d_o || !o || !dq || !dk || !dv) return errorf("%s: null argument", who);
+    return op_attention128_fwd_bwd(who, (hipStream_t)stream, q, k, vT, d_o, nullptr, o, nullptr, (int64_t)H * 128, (int64_t)H * 128, S, dq, dk, dv, B, H, S, S_pad,
+                                   0, 0, nullptr, (float)get_attn128_op_bound(), nullptr, nullptr);
+}
+
+// The same with the fields the entry point above pins exposed: cross-attention and ragged keys (as mi355_op_attention128_ex; k, vT, dk, dv are then
+// [B][H][S_kv_pad][128] / [B][H][128][S_kv_pad]), the first / rest split of o and dO with their row strides (Attn128BwdPrepParams; do_rest may be
+// NULL: that part of the output has no consumer), the |score| bound as an argument, and optional copies of the forward's log2-sum-exp and of the
+// backward's delta = rowsum(dO * O), both [B][H][S_pad] fp32 (rows >= S: zero, as the zeroed scratch holds them).
+extern "C" int mi355_op_attention128_fwd_bwd_ex(void* stream, const void* q, const void* k, const void* vT, const void* do_first, const void* do_rest,
+                                                void* o_first, void* o_rest, int64_t ld_first, int64_t ld_rest, int n_first, void* dq, void* dk, void* dv,
+                                                int B, int H, int S, int S_pad, int S_kv, int S_kv_pad, const void* kv_len, int kv_len_n,
+                                                float score_bound, float* lse_out, float* delta_out) {
+    const char* who = "mi355_op_attention128_fwd_bwd_ex";
+    if (!q || !k || !vT || !dq || !dk || !dv) return errorf("%s: null argument", who);
+    if (attn128_ex_check(who, B, H, S, S_pad, n_first, S_kv, S_kv_pad, kv_len, kv_len_n, score_bound)) return 1;
+    if (n_first > 0 && (!o_first || !do_first || ld_first < (int64_t)H * 128)) return errorf("%s: o_first / do_first is NULL or ld_first < H * 128", who);
+    if (n_first < S && (!o_rest || ld_rest < (int64_t)H * 128)) return errorf("%s: o_rest is NULL or ld_rest < H * 128", who);
+    return op_attention128_fwd_bwd(who, (hipStream_t)stream, q, k, vT, do_first, do_rest, o_first, o_rest, ld_first, ld_rest, n_first, dq, dk, dv, B, H, S, S_pad,
+                                   S_kv, S_kv_pad, kv_len, score_bound, lse_out, delta_out);
 }
 
 // q | k producer forward (mi355_op_rope_norm + the 1/rms side output) and its backward: dq / dk / dv [B][H][S_pad][128] (dq w.r.t. the stored,

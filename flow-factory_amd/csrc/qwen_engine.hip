@@ -26,39 +26,17 @@
 
 using namespace mi355;
 
-namespace {
-
-struct QBlockW {
-    bf16_t *w_qk, *w_v, *w_o, *w_cqk, *w_cv, *w_co, *w_ff1, *w_ff2, *w_cff1, *w_cff2;
-    float *b_qk, *b_v, *b_o, *b_cqk, *b_cv, *b_co, *b_ff1, *b_ff2, *b_cff1, *b_cff2;
-    float *nq, *nk, *ncq, *nck;
-    int mod_img, mod_ctx;
-    float bound = 0.f;
-};
-
-// per-block activation stash of the training-mode forward (qwen_train.inc): what the backward of the block needs
-struct QTrainBlk {
-    bf16_t *x_in, *xn, *x_mid, *xn_mlp, *pre, *o_img;
-    bf16_t *c_in, *cn, *c_mid, *cn_mlp, *cpre, *o_ctx;
-    bf16_t *q, *k, *vT;
-    float *lse, *rstd_img, *rstd_ctx;
-};
-
-}  // namespace
-
-struct QwenTrainState;
-struct mi355_qwen_train;
-
+// (a block's weights: DoubleW, engine_common.h; its training-mode stash: DoubleStash, train_common.h)
 struct mi355_qwen : ParamTable {
     mi355_qwen_cfg cfg;
     int D, F, L, H;
     int mod_cols, mod_out;
     bf16_t *w_x, *w_ctx, *w_t1, *w_t2, *w_mod, *w_proj;
     float *b_x, *b_ctx, *b_t1, *b_t2, *b_mod, *b_proj, *txt_norm;
-    std::vector<QBlockW> blk;
+    std::vector<DoubleW> blk;
     bool bounds_dirty = true;
     int bounds_ver = 0;          // bumped whenever the per-block score bounds are recomputed (they are baked into a captured graph)
-    QwenTrainState* train = nullptr;   // training-mode state (qwen_train.inc), created on first use
+    EngineTrain* train = nullptr;      // training-mode state (qwen_train.inc: QwenTrainState), created on first use
     void layout();
 };
 
@@ -66,7 +44,7 @@ struct mi355_qwen : ParamTable {
 void mi355_qwen::layout() {
     used16 = used32 = 0;
     slots.clear(); names.clear();
-    blk.assign(L, QBlockW());
+    blk.assign(L, DoubleW());
     const int T = cfg.time_proj_dim, J = cfg.joint_attention_dim, C = cfg.in_channels;
     const int64_t DD = (int64_t)D * D;
     w_x = a16((int64_t)D * C); b_x = a32(D); lin("img_in", w_x, b_x, D, C);
@@ -86,7 +64,7 @@ void mi355_qwen::layout() {
     }
     lin("norm_out.linear", w_mod + (int64_t)mod_out * D, b_mod + mod_out, 2 * D, D);
     for (int i = 0; i < L; ++i) {
-        QBlockW& b = blk[i];
+        DoubleW& b = blk[i];
         const std::string pre = "transformer_blocks." + std::to_string(i);
         b.w_qk = a16(2 * DD); b.b_qk = a32(2 * D);
         lin(pre + ".attn.to_q", b.w_qk, b.b_qk, D, D); lin(pre + ".attn.to_k", b.w_qk + DD, b.b_qk + D, D, D);
@@ -107,12 +85,6 @@ void mi355_qwen::layout() {
     }
     w_proj = a16((int64_t)C * D); b_proj = a32(C); lin("proj_out", w_proj, b_proj, C, D);
 }
-
-// training-mode state (qwen_train.inc, included at the end of this file)
-struct mi355_qwen_plan;
-static void qwen_train_release(mi355_qwen_plan* p);
-static void qwen_train_release_engine(mi355_qwen* e);
-static void qwen_train_mark_dirty(mi355_qwen* e);
 
 extern "C" int mi355_qwen_create(const mi355_qwen_cfg* cfg, mi355_qwen** out) {
     if (!cfg || !out) return errorf("mi355_qwen_create: null argument");
@@ -135,7 +107,7 @@ extern "C" int mi355_qwen_create(const mi355_qwen_cfg* cfg, mi355_qwen** out) {
 
 extern "C" int mi355_qwen_destroy(mi355_qwen* e) {
     if (!e) return 0;
-    qwen_train_release_engine(e);
+    delete e->train;
     e->release();
     delete e;
     return 0;
@@ -146,7 +118,7 @@ extern "C" int mi355_qwen_bind_weight(mi355_qwen* e, const char* name, const voi
                                       void* stream) {
     if (!e || !name || !src) return errorf("mi355_qwen_bind_weight: null argument");
     CHK(e->bind("mi355_qwen_bind_weight", name, src, dtype, ndim, shape, (hipStream_t)stream));
-    qwen_train_mark_dirty(e);          // the transposed copies the backward's dgrad GEMMs read are stale
+    engine_train_mark_dirty(e->train); // the transposed copies the backward's dgrad GEMMs read are stale
     if (strstr(name, ".norm_")) e->bounds_dirty = true;
     return 0;
 }
@@ -177,7 +149,7 @@ struct mi355_qwen_plan {
     bf16_t *qkbuf_c = nullptr, *big_c = nullptr;
     std::vector<hipEvent_t> ev_join, ev_fork;   // per block: text q|k|v ready (side -> main), attention done (main -> side); [L] = forward start / end
     RolloutGraph graph;                 // hipGraph of the N-step loop (mi355_tune_set key 17), captured on the second call of a configuration
-    mi355_qwen_train* train = nullptr;  // training workspace (qwen_train.inc), created by the first training-mode forward
+    PlanTrain* train = nullptr;         // training workspace (qwen_train.inc: mi355_qwen_train), created by the first training-mode forward
 };
 
 extern "C" int mi355_qwen_plan_create(mi355_qwen* e, int batch, int n_cfg, int latent_h, int latent_w, int n_text, int max_steps,
@@ -251,7 +223,7 @@ extern "C" int mi355_qwen_plan_create(mi355_qwen* e, int batch, int n_cfg, int l
 
 extern "C" int mi355_qwen_plan_destroy(mi355_qwen_plan* p) {
     if (!p) return 0;
-    qwen_train_release(p);
+    delete p->train;
     p->graph.release();
     for (hipEvent_t ev : p->ev_join) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : p->ev_fork) (void)hipEventDestroy(ev);
@@ -329,7 +301,7 @@ int ln_mod(mi355_qwen_plan* p, hipStream_t st, const bf16_t* x, bf16_t* out, con
 
 // q|k projection (one GEMM) -> per-head RMSNorm + RoPE + scatter; V^T projection with the scatter fused (operands swapped)
 int qkv(mi355_qwen_plan* p, hipStream_t st, const bf16_t* xin, int M, int rps, int s_off, const bf16_t* w_qk, const float* b_qk,
-        const bf16_t* w_v, const float* b_v, const float* nq, const float* nk, bf16_t* qkb, const QTrainBlk* tb = nullptr, float* rstd = nullptr) {
+        const bf16_t* w_v, const float* b_v, const float* nq, const float* nk, bf16_t* qkb, const DoubleStash* tb = nullptr, float* rstd = nullptr) {
     mi355_qwen* e = p->e;
     const int D = e->D;
     GemmParams g = make_gemm(xin, D, w_qk, D, M, 2 * D, D, EPI_BIAS, b_qk, qkb, 2 * D);
@@ -397,7 +369,7 @@ int qwen_two_stream_init(mi355_qwen_plan* p) {
 // Training mode (`tb` = the plan's per-block stash, qwen_train.inc): the SAME launches with the activations the backward needs written to per-block
 // buffers instead of the plan's shared ones (+ the block inputs copied aside, the log-sum-exp / 1/rms side outputs switched on, the MLP
 // pre-activations stashed by the GEMM epilogue): the same kernel binaries on the same values -- the prediction is bit-identical.
-int forward_core(mi355_qwen_plan* p, hipStream_t st, const void* latents, int lat_dt, const bf16_t* mod, const QTrainBlk* tb = nullptr,
+int forward_core(mi355_qwen_plan* p, hipStream_t st, const void* latents, int lat_dt, const bf16_t* mod, const DoubleStash* tb = nullptr,
                  bf16_t* x_final = nullptr) {
     mi355_qwen* e = p->e;
     const int D = e->D, F = e->F, C = e->cfg.in_channels;
@@ -426,8 +398,8 @@ int forward_core(mi355_qwen_plan* p, hipStream_t st, const void* latents, int la
         HIPCHK(ev_wait(ts, p->ev_fork[e->L]));
     }
     for (int i = 0; i < e->L; ++i) {
-        const QBlockW& b = e->blk[i];
-        const QTrainBlk* k = tb ? tb + i : nullptr;
+        const DoubleW& b = e->blk[i];
+        const DoubleStash* k = tb ? tb + i : nullptr;
         const int mi = b.mod_img, mc = b.mod_ctx;     // chunks: shift1, scale1, gate1, shift2, scale2, gate2
         bf16_t* cn = k ? k->cn : p->cn;
         bf16_t* xn = k ? k->xn : p->xn;

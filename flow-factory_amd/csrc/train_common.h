@@ -1,6 +1,9 @@
 // mi355_flow -- training-side helpers shared by the engines' *_train.inc files: the gradient-buffer registry of an engine (all four engines), and,
-// for the native backward passes of the head_dim-128 engines (flux_train.inc, qwen_train.inc, wan_train.inc), the dgrad / wgrad GEMM wrappers, the
-// attention-backward and q | k producer backward sequences, and the scratch they work in.  (The SD3.5 engine's training file, engine_train.inc,
+// for the native backward passes of the head_dim-128 engines (flux_train.inc, qwen_train.inc, wan_train.inc), everything that is not a family's
+// own program: the per-engine / per-plan training state and its life cycle, the set_grad family behind the C ABI, the backward scratch and its
+// carving, the dgrad / wgrad GEMM wrappers, the backward of a linear layer and of a gated MLP, the attention-backward and q | k producer backward
+// sequences, and the backward of a double-stream block (FLUX.1 and Qwen-Image run the same one, told apart by a DoubleBackSched).  A change to the
+// text-chain fork / join or to the weight-gradient slot hand-over is made once, here.  (The SD3.5 engine's training file, engine_train.inc,
 // predates this header and keeps its own dgrad / wgrad helpers: head_dim 64, per-block dual attention, side-stream scratch pairs.)
 #pragma once
 #include "engine_common.h"
@@ -10,6 +13,7 @@ namespace mi355 {
 // Parameter name -> caller-owned gradient buffer (absent = frozen; every backward OVERWRITES the buffers), with the buffers' dtype bookkeeping
 // (grad_buf_mark): fp32 when registered -- the *_set_grad_typed functions re-mark a bf16 buffer afterwards -- and un-marked when it leaves.
 // Which names an engine accepts is the engine's own rule (its trainable-name predicate and refusal messages).
+struct LinGrad { float *w = nullptr, *b = nullptr; };      // the registered gradient buffers of one linear layer (null = frozen)
 struct GradRegistry {
     std::map<std::string, float*> grads;
     void set(const std::string& name, float* grad) {       // null un-registers
@@ -27,6 +31,7 @@ struct GradRegistry {
         auto it = grads.find(name);
         return it == grads.end() ? nullptr : it->second;
     }
+    LinGrad linear(const std::string& layer) const { return LinGrad{find(layer + ".weight"), find(layer + ".bias")}; }
 };
 
 // One in-flight weight-gradient group: its operands in contraction-contiguous form (aT: the dY columns, [rows <= aT_rows][M_pad]; xT: the
@@ -101,6 +106,93 @@ static inline void t_wgrad_streams_destroy(TrainScratch& t) {
 static inline int t_wgrad_join(TrainScratch& t, hipStream_t st) {
     for (int i = 0; i < t.n_slots; ++i)
         if (t.slot[i].busy) { HIPCHK(ev_wait(st, t.slot[i].done)); t.slot[i].busy = false; }
+    return 0;
+}
+
+// ---- training state of an engine and of a plan ------------------------------------------------------------------------------------------
+// Both are created on first use, owned through these bases (the engine / plan structs hold `EngineTrain* train` / `PlanTrain* train` and
+// `delete` them), and a family derives from them to add only its own members: its per-block transposed-weight and stash pointers.
+struct EngineTrain {         // per engine: the transposed weights (dgrad operands; stale after a bind_weight) + the registered gradient buffers
+    char* arenaT = nullptr; size_t bytes = 0;
+    bf16_t* projT = nullptr;
+    bool dirty = true;
+    GradRegistry grads;
+    virtual ~EngineTrain() { if (arenaT) (void)hipFree(arenaT); }
+};
+struct PlanTrain {           // per plan: ONE workspace = activation stash of the last training-mode forward + backward scratch
+    char* ws = nullptr; size_t ws_bytes = 0;
+    bool have_forward = false;
+    TrainScratch sc;
+    virtual ~PlanTrain() {
+        t_wgrad_streams_destroy(sc);
+        if (ws) (void)hipFree(ws);
+    }
+};
+template <class S> static inline S* engine_train_state(EngineTrain*& t) {      // S = the family's EngineTrain
+    if (!t) t = new S();
+    return static_cast<S*>(t);
+}
+static inline void engine_train_mark_dirty(EngineTrain* t) {
+    if (t) t->dirty = true;
+}
+
+// The set_grad family of an engine E (a ParamTable with a `train` pointer) whose training state is S: `fam` = the C-ABI prefix for the messages
+// ("mi355_flux"), `ok` = the family's trainable-name predicate.
+typedef bool (*TrainableName)(const std::string&);
+template <class S, class E> static int t_set_grad(E* e, const char* fam, TrainableName ok, const char* name, float* grad) {
+    if (!e || !name) return errorf("%s_set_grad: null argument", fam);
+    if (e->slots.find(name) == e->slots.end()) return errorf("%s_set_grad: unknown parameter '%s'", fam, name);
+    if (grad && !ok(name))
+        return errorf("%s_set_grad: '%s' lies outside the native backward's scope (the linear layers inside the transformer blocks)", fam, name);
+    engine_train_state<S>(e->train)->grads.set(name, grad);
+    return 0;
+}
+template <class S, class E> static int t_set_grad_typed(E* e, const char* fam, TrainableName ok, const char* name, void* grad, int dtype) {
+    if (dtype == DT_F32 || !grad) return t_set_grad<S>(e, fam, ok, name, (float*)grad);
+    if (dtype != DT_BF16) return errorf("%s_set_grad_typed: gradient buffers are fp32 or bf16 (dtype %d)", fam, dtype);
+    if (!e || !name) return errorf("%s_set_grad_typed: null argument", fam);
+    if (!ok(name)) return errorf("%s_set_grad_typed: bf16 gradient buffers are limited to the linear layers inside the transformer blocks ('%s')", fam, name);
+    const int rc = t_set_grad<S>(e, fam, ok, name, (float*)grad);
+    if (rc == 0) grad_buf_mark(grad, DT_BF16);
+    return rc;
+}
+template <class S, class E> static int t_clear_grads(E* e) {
+    if (!e) return errorf("null engine");
+    engine_train_state<S>(e->train)->grads.clear();
+    return 0;
+}
+static inline int t_grad_supported(const ParamTable* e, TrainableName ok, const char* name) {
+    if (!e || !name || !e->slots.count(name)) return 1;
+    return ok(name) ? 0 : 1;
+}
+
+// The common tail of a plan's training workspace, after the family's own take() calls: the attention-backward scratch, the weight-gradient
+// operand slots, the split-K partials, the column-sum partials and the zero bias; then the allocation and the weight-gradient stream.
+struct ScratchSizes {
+    int D, F;
+    int64_t q_el, kv_el, bhs;     // elements of a head-major q (doh, dq), of a head-major k / v (v, dk, dvh), and B * H * S_pad
+    long aT_rows, xT_rows;        // rows of an operand slot: the widest dY group, the widest layer input
+    int M_pad;                    // columns of an operand slot: the longest token count a weight gradient contracts over (padded to 64)
+    int64_t zero_bias;            // the widest dgrad output
+    int Mc;                       // rows of the text chain when it can run on its own stream (its own gelu / column-sum scratch), else 0
+};
+// A failure deletes `t` (mi355_last_error: the failing call).
+static inline int t_train_alloc(Carver& c, PlanTrain* t, const char* who, const ScratchSizes& z) {
+    TrainScratch& sc = t->sc;
+    const int D = z.D, F = z.F;
+    c.take(sc.doh, z.q_el); c.take(sc.v, z.kv_el); c.take(sc.dq, z.q_el); c.take(sc.dk, z.kv_el); c.take(sc.dvh, z.kv_el);
+    c.take(sc.delta, z.bhs); c.take(sc.nld, z.bhs * 2);
+    const bool side = get_wgrad_side() != 0;
+    for (int i = 0; i < (side ? WG_SLOTS : 1); ++i) { c.take(sc.slot[i].aT, (int64_t)z.aT_rows * z.M_pad); c.take(sc.slot[i].xT, (int64_t)z.xT_rows * z.M_pad); }
+    sc.part_floats = (size_t)16 * D * D > (size_t)2 * F * D ? (size_t)16 * D * D : (size_t)2 * F * D;
+    auto row_tiles = [](int rows_pad) { return (int64_t)(rows_pad / 64 > 64 ? rows_pad / 64 : 64); };
+    c.take(sc.part, (int64_t)sc.part_floats); c.take(sc.csum, row_tiles(z.M_pad) * F); c.take(sc.zero_bias, z.zero_bias);
+    if (z.Mc > 0) { c.take(sc.hid_c, (int64_t)z.Mc * F); c.take(sc.csum_c, row_tiles((z.Mc + 63) / 64 * 64) * F); }
+    sc.aT_rows = z.aT_rows; sc.xT_rows = z.xT_rows;
+    if (c.alloc(&t->ws, &t->ws_bytes, true, who, " of activation stash + backward scratch") != 0 || t_wgrad_streams_init(sc, side) != 0) {
+        delete t;
+        return 1;
+    }
     return 0;
 }
 
@@ -252,6 +344,166 @@ static inline int t_rope_back(const TrainScratch& t, const AttnGeom& a, hipStrea
     r.q_scale = 0.08838834764831845f * 1.4426950408889634f;
     r.out = out; r.ld_out = ld_out; r.M = M; r.H = a.H; r.rows_per_sample = rps; r.s_off = s_off; r.S_pad = a.S_pad;
     HIPCHK(launch_rope_rms_bwd128(r, st));
+    return 0;
+}
+
+// ---- layers of one token stream ----------------------------------------------------------------------------------------------------------
+// One stream of token rows in the backward: where its launches go, its rows, and its own scratch ([M][D] g1 / g2 / g3, [M][3D + F] wide,
+// [M][F] hid).  `side`: the text chain on its own stream (its weight gradients take their column sums in csum_c).
+struct TrainChain {
+    hipStream_t st;
+    int M, M_pad, rps;                        // rows, padded to 64, rows per sample
+    bf16_t *g1, *g2, *g3, *wide, *hid;
+    bool side;
+};
+struct ModRows { const bf16_t* mod; long ld; float eps; };     // the step's modulation rows [B][ld] and the LayerNorm epsilon
+
+// d res (+)= LNmod'(x)(dy): backward of the modulated LayerNorm (shift / scale at columns shift_off / scale_off of the modulation rows)
+static inline int t_ln_back(const TrainChain& c, const ModRows& m, int D, const bf16_t* x, const bf16_t* dy, bf16_t* dres, int shift_off, int scale_off,
+                            int accumulate) {
+    LnModBwdParams l{x, dy, nullptr, dres, m.mod, m.ld, scale_off, 0, c.M, D, c.rps, m.eps, accumulate, nullptr, shift_off, 0};
+    HIPCHK(launch_ln_mod_bwd(l, c.st));
+    return 0;
+}
+
+// Backward of y = X . W^T + b from dY [M][N]: the weight / bias gradient where one is registered, then dX [M][K] = dY . W on the transposed
+// weight WT, with the optional fused gelu'(pre).
+static inline int t_linear_back(TrainScratch& t, const TrainChain& c, const bf16_t* dY, long ldY, int N, const bf16_t* X, long ldX, int K,
+                                const bf16_t* WT, LinGrad g, bf16_t* dX, long ld_dX, const bf16_t* gelu_pre = nullptr, long ld_pre = 0) {
+    CHK(t_wgrad(t, c.st, dY, ldY, 0, N, X, ldX, K, c.M, c.M_pad, g.w, g.b, c.side));
+    return t_dgrad(t, c.st, dY, ldY, N, WT, c.M, K, dX, ld_dX, gelu_pre, ld_pre);
+}
+
+// Backward of the gated MLP x' = x + gate * W2 . gelu(W1 . LNmod(x)) of one stream: dres = d x' on entry, d x on return.  m0 = the first of the
+// block's six modulation columns [shift | scale | gate] x (attention, MLP); stash: x_mid = x, xn = LNmod(x), pre = W1 . xn; w1T / w2T transposed.
+// gelu(pre), the input of W2, is recomputed into c.hid only when W2's weight gradient is wanted.
+static inline int t_mlp_back(TrainScratch& t, const TrainChain& c, const ModRows& m, int m0, int D, int F, bf16_t* dres, const bf16_t* x_mid,
+                             const bf16_t* xn, const bf16_t* pre, const bf16_t* w1T, const bf16_t* w2T, LinGrad g1, LinGrad g2) {
+    bf16_t* dpre = c.wide + (size_t)c.M * 3 * D;          // [M][F] behind the [M][3D] q|k|v gradient
+    HIPCHK(launch_gate_mul(dres, m.mod + m0 + 5 * D, m.ld, c.g1, c.M, D, c.rps, c.st));
+    if (g2.w) HIPCHK(launch_gelu_fwd(pre, c.hid, (long)c.M * F, c.st));
+    CHK(t_linear_back(t, c, c.g1, D, D, c.hid, F, F, w2T, g2, dpre, F, pre, F));
+    CHK(t_linear_back(t, c, dpre, F, F, xn, D, D, w1T, g1, c.g3, D));
+    return t_ln_back(c, m, D, x_mid, c.g3, dres, m0 + 3 * D, m0 + 4 * D, 1);
+}
+
+// ---- double-stream block (FLUX.1 double blocks, Qwen-Image blocks) ---------------------------------------------------------------------------
+// per-block activation stash of the training-mode forward (the family's forward_core fills it): what the backward of the block needs
+struct DoubleStash {
+    bf16_t *x_in, *xn, *x_mid, *xn_mlp, *pre, *o_img;
+    bf16_t *c_in, *cn, *c_mid, *cn_mlp, *cpre, *o_ctx;
+    bf16_t *q, *k, *vT;
+    float *lse, *rstd_img, *rstd_ctx;
+};
+struct DoubleWT { bf16_t *qkv, *o, *cqkv, *co, *ff1, *ff2, *cff1, *cff2; };   // transposed weights (dgrad operands)
+struct DoubleGrads { LinGrad q, k, v, o, cq, ck, cv, co, ff1, ff2, cff1, cff2; };
+
+// What tells the two families apart: the order of the joint sequence and the names of the two MLPs (the attention names are shared).
+struct DoubleBackSched {
+    bool image_first;                 // image rows first in the joint sequence (Qwen-Image) or context rows first (FLUX.1)
+    const char *mlp_img, *mlp_ctx;    // parameter-name leaves of the image / text MLP
+    bool last_text_dead;              // the text output of the LAST block has no consumer (Qwen-Image; FLUX.1's feeds the single-stream blocks)
+};
+
+static inline void t_double_stash_take(Carver& c, DoubleStash& k, int Mi, int Mc, int D, int F, int H, int64_t qk_el, int64_t bhs) {
+    c.take(k.x_in, (int64_t)Mi * D); c.take(k.xn, (int64_t)Mi * D); c.take(k.x_mid, (int64_t)Mi * D); c.take(k.xn_mlp, (int64_t)Mi * D);
+    c.take(k.pre, (int64_t)Mi * F); c.take(k.o_img, (int64_t)Mi * D);
+    c.take(k.c_in, (int64_t)Mc * D); c.take(k.cn, (int64_t)Mc * D); c.take(k.c_mid, (int64_t)Mc * D); c.take(k.cn_mlp, (int64_t)Mc * D);
+    c.take(k.cpre, (int64_t)Mc * F); c.take(k.o_ctx, (int64_t)Mc * D);
+    c.take(k.q, qk_el); c.take(k.k, qk_el); c.take(k.vT, qk_el);
+    c.take(k.lse, bhs); c.take(k.rstd_img, (int64_t)Mi * 2 * H); c.take(k.rstd_ctx, (int64_t)Mc * 2 * H);
+}
+static inline void t_double_wt_take(Carver& c, DoubleWT& w, int D, int F) {
+    c.take(w.qkv, (int64_t)D * 3 * D); c.take(w.o, (int64_t)D * D); c.take(w.cqkv, (int64_t)D * 3 * D); c.take(w.co, (int64_t)D * D);
+    c.take(w.ff1, (int64_t)D * F); c.take(w.ff2, (int64_t)F * D); c.take(w.cff1, (int64_t)D * F); c.take(w.cff2, (int64_t)F * D);
+}
+// W [rows][cols] -> out[c][col0 + r] with row stride ld_out
+static inline hipError_t t_transpose_weight(const bf16_t* w, int rows, int cols, bf16_t* out, long ld_out, int col0, hipStream_t st) {
+    return launch_transpose(w, cols, 0, out + col0, ld_out, 0, rows, cols, rows, 1, st);
+}
+static inline int t_double_wt_fill(const DoubleW& b, DoubleWT& w, int D, int F, hipStream_t st) {
+    HIPCHK(t_transpose_weight(b.w_qk, 2 * D, D, w.qkv, 3 * D, 0, st)); HIPCHK(t_transpose_weight(b.w_v, D, D, w.qkv, 3 * D, 2 * D, st));
+    HIPCHK(t_transpose_weight(b.w_o, D, D, w.o, D, 0, st));
+    HIPCHK(t_transpose_weight(b.w_cqk, 2 * D, D, w.cqkv, 3 * D, 0, st)); HIPCHK(t_transpose_weight(b.w_cv, D, D, w.cqkv, 3 * D, 2 * D, st));
+    HIPCHK(t_transpose_weight(b.w_co, D, D, w.co, D, 0, st));
+    HIPCHK(t_transpose_weight(b.w_ff1, F, D, w.ff1, F, 0, st)); HIPCHK(t_transpose_weight(b.w_ff2, D, F, w.ff2, D, 0, st));
+    HIPCHK(t_transpose_weight(b.w_cff1, F, D, w.cff1, F, 0, st)); HIPCHK(t_transpose_weight(b.w_cff2, D, F, w.cff2, D, 0, st));
+    return 0;
+}
+static inline DoubleGrads t_double_grads(const GradRegistry& r, const DoubleBackSched& d, int i) {
+    const std::string blk = "transformer_blocks." + std::to_string(i);
+    auto L = [&](const std::string& leaf) { return r.linear(blk + leaf); };
+    return DoubleGrads{L(".attn.to_q"), L(".attn.to_k"), L(".attn.to_v"), L(".attn.to_out.0"), L(".attn.add_q_proj"), L(".attn.add_k_proj"),
+                       L(".attn.add_v_proj"), L(".attn.to_add_out"), L(std::string(d.mlp_img) + ".net.0.proj"), L(std::string(d.mlp_img) + ".net.2"),
+                       L(std::string(d.mlp_ctx) + ".net.0.proj"), L(std::string(d.mlp_ctx) + ".net.2")};
+}
+
+// Backward of one double-stream block: dx / dc = the gradient of the block's image / text output on entry, of its inputs on return.  The image
+// chain `im` runs on the backward's stream; the text chain `tx` on the same one, or (tx.side) on the plan's side stream: it joins before the
+// joint attention backward, which reads the text rows' dO (and whose predecessor's text chain has read dq / dk / dv), and forks after it, when
+// dq / dk / dv are written.  Scratch is per chain; the weight-gradient operand slots are shared through their events.  Same kernels and
+// operands either way: bit-identical.
+// `dead_text`: the block's text output has no consumer.  Its text MLP and text out-projection are skipped, the text rows' dO is null, and d c
+// STARTS at this block's attention.  (Frozen by construction: the gradient of an unused output is exactly zero; registered buffers are still
+// overwritten.)
+static inline int t_double_block_back(TrainScratch& t, const DoubleBackSched& d, const AttnGeom& a, int F, const ModRows& m, const DoubleW& b,
+                                      const DoubleStash& k, const DoubleWT& w, const DoubleGrads& g, const TrainChain& im, const TrainChain& tx,
+                                      bf16_t* dx, bf16_t* dc, bool dead_text, hipEvent_t ev_join, hipEvent_t ev_fork) {
+    const int D = a.D, mi = b.mod_img, mc = b.mod_ctx;
+    const bool two = tx.side;
+    // ---- MLP of both streams
+    CHK(t_mlp_back(t, im, m, mi, D, F, dx, k.x_mid, k.xn_mlp, k.pre, w.ff1, w.ff2, g.ff1, g.ff2));
+    if (!dead_text) CHK(t_mlp_back(t, tx, m, mc, D, F, dc, k.c_mid, k.cn_mlp, k.cpre, w.cff1, w.cff2, g.cff1, g.cff2));
+    // ---- joint attention: out-projections of both streams
+    HIPCHK(launch_gate_mul(dx, m.mod + mi + 2 * D, m.ld, im.g1, im.M, D, im.rps, im.st));
+    CHK(t_linear_back(t, im, im.g1, D, D, k.o_img, D, D, w.o, g.o, im.g2, D));
+    if (!dead_text) {
+        HIPCHK(launch_gate_mul(dc, m.mod + mc + 2 * D, m.ld, tx.g1, tx.M, D, tx.rps, tx.st));
+        CHK(t_linear_back(t, tx, tx.g1, D, D, k.o_ctx, D, D, w.co, g.co, tx.g2, D));
+        if (two) { HIPCHK(ev_record(ev_join, tx.st)); HIPCHK(ev_wait(im.st, ev_join)); }
+    } else {
+        const struct { float* p; size_t n; } zero[6] = {{g.co.w, (size_t)D * D}, {g.co.b, (size_t)D}, {g.cff1.w, (size_t)F * D}, {g.cff1.b, (size_t)F},
+                                                        {g.cff2.w, (size_t)D * F}, {g.cff2.b, (size_t)D}};
+        for (const auto& z : zero)
+            if (z.p) HIPCHK(hipMemsetAsync(z.p, 0, z.n * grad_buf_esize(z.p), im.st));
+    }
+    const bf16_t* do_ctx = dead_text ? nullptr : tx.g2;
+    if (d.image_first) CHK(t_attention128_backward(t, a, im.st, k.q, k.k, k.vT, k.lse, k.o_img, k.o_ctx, im.g2, do_ctx, im.rps));
+    else CHK(t_attention128_backward(t, a, im.st, k.q, k.k, k.vT, k.lse, k.o_ctx, k.o_img, do_ctx, im.g2, tx.rps));
+    if (two) { HIPCHK(ev_record(ev_fork, im.st)); HIPCHK(ev_wait(tx.st, ev_fork)); }
+    // ---- q | k | v producers of both streams, in the order of the joint sequence
+    auto rope_img = [&](int s_off) { return t_rope_back(t, a, im.st, k.q, k.k, k.rstd_img, b.nq, b.nk, im.wide, 3 * D, im.M, im.rps, s_off); };
+    auto rope_ctx = [&](int s_off) { return t_rope_back(t, a, tx.st, k.q, k.k, k.rstd_ctx, b.ncq, b.nck, tx.wide, 3 * D, tx.M, tx.rps, s_off); };
+    if (d.image_first) { CHK(rope_img(0)); CHK(rope_ctx(im.rps)); }
+    else { CHK(rope_ctx(0)); CHK(rope_img(tx.rps)); }
+    const WgradSeg si[3] = {{0, D, g.q.w, g.q.b}, {D, D, g.k.w, g.k.b}, {2 * D, D, g.v.w, g.v.b}};
+    const WgradSeg sx[3] = {{0, D, g.cq.w, g.cq.b}, {D, D, g.ck.w, g.ck.b}, {2 * D, D, g.cv.w, g.cv.b}};
+    const WgradX xi{k.xn, D, D}, xc{k.cn, D, D};
+    CHK(t_wgrad_group(t, im.st, im.wide, 3 * D, si, 3, &xi, 1, im.M, im.M_pad));
+    CHK(t_wgrad_group(t, tx.st, tx.wide, 3 * D, sx, 3, &xc, 1, tx.M, tx.M_pad, tx.side));
+    CHK(t_dgrad(t, im.st, im.wide, 3 * D, 3 * D, w.qkv, im.M, D, im.g3, D, nullptr, 0));
+    CHK(t_dgrad(t, tx.st, tx.wide, 3 * D, 3 * D, w.cqkv, tx.M, D, tx.g3, D, nullptr, 0));
+    CHK(t_ln_back(im, m, D, k.x_in, im.g3, dx, mi, mi + D, 1));
+    return t_ln_back(tx, m, D, k.c_in, tx.g3, dc, mc, mc + D, dead_text ? 0 : 1);
+}
+
+// The L double-stream blocks of an engine, last to first.  ev_join / ev_fork: the plan's per-block events of the text chain, [L] = start / end
+// (read only when the text chain has its own stream).
+static inline int t_double_blocks_back(TrainScratch& t, const DoubleBackSched& d, const AttnGeom& a, int F, const ModRows& m, int L, const DoubleW* b,
+                                       const DoubleStash* k, const DoubleWT* w, const GradRegistry& r, const TrainChain& im, const TrainChain& tx,
+                                       bf16_t* dx, bf16_t* dc, const hipEvent_t* ev_join, const hipEvent_t* ev_fork) {
+    const bool two = tx.side;
+    if (two) {          // d x / d c, the stash and the transposed weights are complete on the backward's stream
+        HIPCHK(ev_record(ev_fork[L], im.st));
+        HIPCHK(ev_wait(tx.st, ev_fork[L]));
+    }
+    for (int i = L - 1; i >= 0; --i)
+        CHK(t_double_block_back(t, d, a, F, m, b[i], k[i], w[i], t_double_grads(r, d, i), im, tx, dx, dc, d.last_text_dead && i + 1 == L,
+                                two ? ev_join[i] : nullptr, two ? ev_fork[i] : nullptr));
+    if (two) {          // the backward's stream goes on only after the text chain
+        HIPCHK(ev_record(ev_join[L], tx.st));
+        HIPCHK(ev_wait(im.st, ev_join[L]));
+    }
     return 0;
 }
 

@@ -44,9 +44,6 @@ struct WanBlockW {
 
 }  // namespace
 
-struct WanTrainState;
-struct mi355_wan_train;
-
 struct mi355_wan : ParamTable {
     mi355_wan_cfg cfg;
     int D, F, L, H, KP, NO;
@@ -56,7 +53,7 @@ struct mi355_wan : ParamTable {
     bool derived_dirty = true;   // ln2_mod tables / score bounds need a rebuild after a (re)bind
     int derived_ver = 0;         // bumped by every rebuild (the bounds are baked into a captured graph)
     std::vector<float> bound_self, bound_cross;
-    WanTrainState* train = nullptr;   // training-mode state (wan_train.inc), created on first use
+    EngineTrain* train = nullptr;     // training-mode state (wan_train.inc: WanTrainState), created on first use
     void layout();
 };
 
@@ -100,12 +97,6 @@ void mi355_wan::layout() {
     w_proj = a16((int64_t)NO * D); b_proj = a32(NO); lin("proj_out", w_proj, b_proj, NO, D);
 }
 
-// training-mode state (wan_train.inc, included at the end of this file)
-struct mi355_wan_plan;
-static void wan_train_release(mi355_wan_plan* p);
-static void wan_train_release_engine(mi355_wan* e);
-static void wan_train_mark_dirty(mi355_wan* e);
-
 extern "C" int mi355_wan_create(const mi355_wan_cfg* cfg, mi355_wan** out) {
     if (!cfg || !out) return errorf("mi355_wan_create: null argument");
     if (cfg->head_dim != 128) return errorf("mi355_wan_create: head_dim must be 128 (got %d)", cfg->head_dim);
@@ -128,7 +119,7 @@ extern "C" int mi355_wan_create(const mi355_wan_cfg* cfg, mi355_wan** out) {
 
 extern "C" int mi355_wan_destroy(mi355_wan* e) {
     if (!e) return 0;
-    wan_train_release_engine(e);
+    delete e->train;
     e->release();
     delete e;
     return 0;
@@ -140,7 +131,7 @@ extern "C" int mi355_wan_bind_weight(mi355_wan* e, const char* name, const void*
     if (!e || !name || !src) return errorf("mi355_wan_bind_weight: null argument");
     CHK(e->bind("mi355_wan_bind_weight", name, src, dtype, ndim, shape, (hipStream_t)stream));
     e->derived_dirty = true;
-    wan_train_mark_dirty(e);           // the transposed copies the backward's dgrad GEMMs read are stale
+    engine_train_mark_dirty(e->train); // the transposed copies the backward's dgrad GEMMs read are stale
     return 0;
 }
 extern "C" int mi355_wan_weights_ready(mi355_wan* e) { return e ? e->ready() : errorf("null engine"); }
@@ -163,7 +154,7 @@ struct mi355_wan_plan {
     float* max2_part;          // scratch of the kernel that measures them
     std::vector<float> host_t, host_sc;
     int mod_cols;
-    mi355_wan_train* train = nullptr;   // training workspace (wan_train.inc), created by the first training-mode forward
+    PlanTrain* train = nullptr;         // training workspace (wan_train.inc: mi355_wan_train), created by the first training-mode forward
 };
 
 extern "C" int mi355_wan_plan_create(mi355_wan* e, int batch, int n_cfg, int latent_t, int latent_h, int latent_w, int n_text,
@@ -226,7 +217,7 @@ extern "C" int mi355_wan_plan_create(mi355_wan* e, int batch, int n_cfg, int lat
 
 extern "C" int mi355_wan_plan_destroy(mi355_wan_plan* p) {
     if (!p) return 0;
-    wan_train_release(p);
+    delete p->train;
     if (p->ws) (void)hipFree(p->ws);
     delete p;
     return 0;

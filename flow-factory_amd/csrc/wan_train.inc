@@ -1,6 +1,7 @@
 // mi355_flow -- Wan2.1 / Wan2.2 T2V differentiable transformer forward + native backward for the `optimize()` replay (SURVEY.md 8(f) N1 over N4;
 // reference src/flow_factory/trainers/grpo.py:263, :326-330 over models/wan/wan2_t2v.py:426-543).  Textually included at the end of wan_engine.hip.
-// Written at the end of round 4 on the FLUX.1 / Qwen-Image machinery (train_common.h); its GPU tests (tests/test_gpu_wan_backward.py: operator level,
+// Written at the end of round 4 on the FLUX.1 / Qwen-Image machinery (train_common.h: the training state's life cycle, the set_grad family, the
+// scratch carving, t_linear_back / t_mlp_back and the attention backward; the block loop below is Wan's own program); its GPU tests (tests/test_gpu_wan_backward.py: operator level,
 // three tiny shapes with and without CFG, Wan2.1-1.3B width at 4 608 tokens, an optimizer-step loop) are green on MI355X (profiles/r04u_*, r04v_*).
 // Not yet measured: a full-depth (30-layer) step timing and the emitted schedule's race check (the cross-stream pattern is train_common.h's).
 //
@@ -14,47 +15,24 @@
 // of THIS block: their gradient reaches attn2.to_k / to_v through the k-norm backward, the text embedder behind them is frozen) | self-attention
 // (gated; 3-D RoPE; q / k RMSNorm across ALL heads: norm_rope_full_bwd).  Attention backward = the head_dim-128 passes with a separate key length.
 
+namespace {
+
 struct WBlkWT { bf16_t *qkv, *o, *q2, *o2, *ff1, *ff2; };
 
-struct WanTrainState {       // per engine
-    char* arenaT = nullptr; size_t bytes = 0;
+struct WanTrainState : EngineTrain {       // per engine
     std::vector<WBlkWT> wt;
-    bf16_t* projT = nullptr;
-    bool dirty = true;
-    GradRegistry grads;
 };
-struct mi355_wan_train {     // per plan
-    mi355_wan_plan* p;
-    char* ws = nullptr; size_t ws_bytes = 0;
+struct mi355_wan_train : PlanTrain {       // per plan
     std::vector<WTrainBlk> blk;
     bf16_t *x_final, *mod, *kx, *vTx, *ctx;     // this step's modulation rows, cross-attention k / v and text context (the plan's own copies may be
     float* rstd_kx;                             // overwritten by a no-grad forward -- the KL reference pass -- before the backward runs); [L][Mc]
-    bool have_forward = false;
     bf16_t *dx, *dproj, *widec;
-    TrainScratch sc;
     int M_pad, Mc_pad;
 };
 
-static WanTrainState* wan_train_state(mi355_wan* e) {      // created on first use
-    if (!e->train) e->train = new WanTrainState();
-    return e->train;
-}
-static void wan_train_mark_dirty(mi355_wan* e) {
-    if (e->train) e->train->dirty = true;
-}
-static void wan_train_release(mi355_wan_plan* p) {
-    if (!p->train) return;
-    t_wgrad_streams_destroy(p->train->sc);
-    if (p->train->ws) (void)hipFree(p->train->ws);
-    delete p->train;
-    p->train = nullptr;
-}
-static void wan_train_release_engine(mi355_wan* e) {
-    if (!e->train) return;
-    if (e->train->arenaT) (void)hipFree(e->train->arenaT);
-    delete e->train;
-    e->train = nullptr;
-}
+}  // namespace
+
+static WanTrainState* wan_train_state(mi355_wan* e) { return engine_train_state<WanTrainState>(e->train); }
 
 static bool wan_trainable_name(const std::string& n) {
     static const char* ok[] = {".attn1.to_q.", ".attn1.to_k.", ".attn1.to_v.", ".attn1.to_out.0.", ".attn2.to_q.", ".attn2.to_k.", ".attn2.to_v.",
@@ -66,35 +44,15 @@ static bool wan_trainable_name(const std::string& n) {
 }
 
 extern "C" int mi355_wan_set_grad(mi355_wan* e, const char* name, float* grad) {
-    if (!e || !name) return errorf("mi355_wan_set_grad: null argument");
-    if (e->slots.find(name) == e->slots.end()) return errorf("mi355_wan_set_grad: unknown parameter '%s'", name);
-    if (grad && !wan_trainable_name(name))
-        return errorf("mi355_wan_set_grad: '%s' lies outside the native backward's scope (the linear layers inside the transformer blocks)", name);
-    wan_train_state(e)->grads.set(name, grad);
-    return 0;
+    return t_set_grad<WanTrainState>(e, "mi355_wan", wan_trainable_name, name, grad);
 }
 extern "C" int mi355_wan_set_grad_typed(mi355_wan* e, const char* name, void* grad, int dtype) {
-    if (dtype == DT_F32 || !grad) return mi355_wan_set_grad(e, name, (float*)grad);
-    if (dtype != DT_BF16) return errorf("mi355_wan_set_grad_typed: gradient buffers are fp32 or bf16 (dtype %d)", dtype);
-    const int rc = mi355_wan_set_grad(e, name, (float*)grad);
-    if (rc == 0) grad_buf_mark(grad, DT_BF16);
-    return rc;
+    return t_set_grad_typed<WanTrainState>(e, "mi355_wan", wan_trainable_name, name, grad, dtype);
 }
-extern "C" int mi355_wan_clear_grads(mi355_wan* e) {
-    if (!e) return errorf("null engine");
-    wan_train_state(e)->grads.clear();
-    return 0;
-}
+extern "C" int mi355_wan_clear_grads(mi355_wan* e) { return t_clear_grads<WanTrainState>(e); }
 // 0 = the native backward produces a gradient for `name`, 1 = it does not
-extern "C" int mi355_wan_grad_supported(mi355_wan* e, const char* name) {
-    if (!e || !name || !e->slots.count(name)) return 1;
-    return wan_trainable_name(name) ? 0 : 1;
-}
-extern "C" int64_t mi355_wan_plan_training_bytes(mi355_wan_plan* p) {
-    return p && p->train ? (int64_t)p->train->ws_bytes : 0;
-}
-
-static float* wgrad_of(mi355_wan* e, const std::string& name) { return wan_train_state(e)->grads.find(name); }
+extern "C" int mi355_wan_grad_supported(mi355_wan* e, const char* name) { return t_grad_supported(e, wan_trainable_name, name); }
+extern "C" int64_t mi355_wan_plan_training_bytes(mi355_wan_plan* p) { return p && p->train ? (int64_t)p->train->ws_bytes : 0; }
 
 // ---- transposed weights (dgrad operands) -------------------------------------------------------------------------------------------
 static int wan_ensure_transposed(mi355_wan* e, hipStream_t st) {
@@ -112,9 +70,7 @@ static int wan_ensure_transposed(mi355_wan* e, hipStream_t st) {
         s->dirty = true;
     }
     if (!s->dirty) return 0;
-    auto tr = [&](const bf16_t* w, int rows, int cols, bf16_t* out, long ld_out, int col0) {
-        return launch_transpose(w, cols, 0, out + col0, ld_out, 0, rows, cols, rows, 1, st);
-    };
+    auto tr = [&](const bf16_t* w, int rows, int cols, bf16_t* out, long ld_out, int col0) { return t_transpose_weight(w, rows, cols, out, ld_out, col0, st); };
     for (int i = 0; i < L; ++i) {
         const WanBlockW& b = e->blk[i];
         WBlkWT& w = s->wt[i];
@@ -129,14 +85,13 @@ static int wan_ensure_transposed(mi355_wan* e, hipStream_t st) {
 
 // ---- training workspace ----------------------------------------------------------------------------------------------
 static int wan_train_of(mi355_wan_plan* p, mi355_wan_train** out) {
-    if (p->train) { *out = p->train; return 0; }
+    if (p->train) { *out = static_cast<mi355_wan_train*>(p->train); return 0; }
     mi355_wan* e = p->e;
     const int D = e->D, F = e->F, L = e->L, H = e->H, NO = e->NO;
     const int M = p->M, Mc = p->Mc;
     const int64_t qk_el = (int64_t)p->Bp * H * p->S_pad * 128, kx_el = (int64_t)p->Bp * H * p->Nt_pad * 128;
     const int64_t bhs = (int64_t)p->Bp * H * p->S_pad;
     mi355_wan_train* t = new mi355_wan_train();
-    t->p = p;
     t->M_pad = (M + 63) / 64 * 64; t->Mc_pad = (Mc + 63) / 64 * 64;
     TrainScratch& sc = t->sc;
     Carver c;
@@ -153,26 +108,17 @@ static int wan_train_of(mi355_wan_plan* p, mi355_wan_train** out) {
     c.take(t->dx, (int64_t)M * D); c.take(t->dproj, (int64_t)M * NO); c.take(t->widec, (int64_t)Mc * 2 * D);
     c.take(sc.g1, (int64_t)M * D); c.take(sc.g2, (int64_t)M * D); c.take(sc.g3, (int64_t)M * D);
     c.take(sc.wide, (int64_t)M * (3 * D + F)); c.take(sc.hid, (int64_t)M * F);
-    // (the cross-attention backward puts its transposed V and its dK / dV -- stride Nt_pad * 128 per (batch, head) -- into the same v / dk / dvh
-    // scratch as the self-attention: those three hold the LONGER of the two key counts, a 512-token prompt on a single small frame has
-    // Nt_pad > S_pad (ADVICE r4))
+    // kv_el: the cross-attention backward puts its transposed V and its dK / dV -- stride Nt_pad * 128 per (batch, head) -- into the same v / dk /
+    // dvh scratch as the self-attention: those three hold the LONGER of the two key counts, a 512-token prompt on a single small frame has
+    // Nt_pad > S_pad (ADVICE r4).
+    // Mmax_pad: operand slots and column-sum partials serve the text-side weight gradients too: rows = the LONGER of the two token counts -- a clip
+    // shorter than its prompt overflowed slots sized by the video rows in the first GPU run of this file, profiles/r04t_wan_bwd_diag.txt.
     const int64_t kv_el = qk_el > kx_el ? qk_el : kx_el;
-    c.take(sc.doh, qk_el); c.take(sc.v, kv_el); c.take(sc.dq, qk_el); c.take(sc.dk, kv_el); c.take(sc.dvh, kv_el);
-    c.take(sc.delta, bhs); c.take(sc.nld, bhs * 2);
-    const int n_slots = get_wgrad_side() ? WG_SLOTS : 1;
-    const int rows_T = F > 3 * D ? F : 3 * D;
-    // (operand slots and column-sum partials serve the text-side weight gradients too: rows = the LONGER of the two token counts -- a clip shorter
-    // than its prompt overflowed slots sized by the video rows in the first GPU run of this file, profiles/r04t_wan_bwd_diag.txt)
     const int Mmax_pad = t->M_pad > t->Mc_pad ? t->M_pad : t->Mc_pad;
-    for (int i = 0; i < n_slots; ++i) { c.take(sc.slot[i].aT, (int64_t)rows_T * Mmax_pad); c.take(sc.slot[i].xT, (int64_t)F * Mmax_pad); }
-    sc.part_floats = (size_t)16 * D * D > (size_t)2 * F * D ? (size_t)16 * D * D : (size_t)2 * F * D;
-    const int nrt = Mmax_pad / 64 > 64 ? Mmax_pad / 64 : 64;
-    c.take(sc.part, (int64_t)sc.part_floats); c.take(sc.csum, (int64_t)nrt * F); c.take(sc.zero_bias, F > 3 * D ? F : 3 * D);
-    if (c.alloc(&t->ws, &t->ws_bytes, true, "wan training", " of activation stash + backward scratch") != 0) { delete t; return 1; }
+    const int rows_T = F > 3 * D ? F : 3 * D;
+    CHK(t_train_alloc(c, t, "wan training", ScratchSizes{D, F, qk_el, kv_el, bhs, rows_T, F, Mmax_pad, rows_T, 0}));
     sc.g1c = sc.g2c = sc.g3c = nullptr; sc.widec = t->widec;
-    sc.aT_rows = rows_T; sc.xT_rows = F;
     sc.tn_default = true;          // weight gradients on row-major operands (train_common.h: measured -1.9 % on the config-D step)
-    if (t_wgrad_streams_init(sc, n_slots > 1) != 0) { t_wgrad_streams_destroy(sc); (void)hipFree(t->ws); delete t; return 1; }
     p->train = t;
     *out = t;
     return 0;
@@ -208,7 +154,7 @@ extern "C" int mi355_wan_forward_train(mi355_wan_plan* p, void* stream, const vo
 extern "C" int mi355_wan_backward(mi355_wan_plan* p, void* stream, const float* dv) {
     if (!p || !dv) return errorf("mi355_wan_backward: null argument");
     if (!p->train || !p->train->have_forward) return errorf("mi355_wan_backward: no training-mode forward has run on this plan");
-    mi355_wan_train* t = p->train;
+    mi355_wan_train* t = static_cast<mi355_wan_train*>(p->train);
     mi355_wan* e = p->e;
     hipStream_t st = (hipStream_t)stream;
     CHK(wan_ensure_transposed(e, st));
@@ -220,11 +166,9 @@ extern "C" int mi355_wan_backward(mi355_wan_plan* p, void* stream, const float* 
     TrainScratch& sc = t->sc;
     const AttnGeom ag_self{p->Bp, e->H, D, S, p->S_pad, p->cs, nullptr, 0, 0};
     const AttnGeom ag_cross{p->Bp, e->H, D, S, p->S_pad, nullptr, nullptr, p->Nt, p->Nt_pad};
-    auto G = [&](int i, const char* leaf) { return wgrad_of(e, "blocks." + std::to_string(i) + leaf); };
-    auto ln_back = [&](const bf16_t* x, const bf16_t* dy, bf16_t* dres, const bf16_t* m_, long mld_, int shift_off, int scale_off, int accumulate) -> hipError_t {
-        LnModBwdParams l{x, dy, nullptr, dres, m_, mld_, scale_off, 0, M, D, S, e->cfg.eps, accumulate, nullptr, shift_off, 0};
-        return launch_ln_mod_bwd(l, st);
-    };
+    const ModRows mr{mod, mld, e->cfg.eps};
+    const TrainChain ch{st, M, t->M_pad, S, sc.g1, sc.g2, sc.g3, sc.wide, sc.hid, false};
+    auto G = [&](int i, const char* layer) { return ts->grads.linear("blocks." + std::to_string(i) + layer); };
     auto norm_back = [&](const bf16_t* y, const bf16_t* dy, const float* w_, const float* rstd, bool rope, float scale, bf16_t* out, long ld, int col, int rows,
                          int rps, int S_pad_) -> hipError_t {
         NormRopeFullBwdParams r{y, dy, w_, rstd, rope ? p->cs : nullptr, out, ld, col, rows, e->H, rps, 0, S_pad_, scale};
@@ -234,62 +178,45 @@ extern "C" int mi355_wan_backward(mi355_wan_plan* p, void* stream, const float* 
     HIPCHK(launch_unpatch_bwd(dv, t->dproj, p->Bp, e->cfg.out_channels, p->T * p->hp, p->wp, 2, st));
     CHK(t_dgrad(sc, st, t->dproj, NO, NO, ts->projT, M, D, sc.g3, D, nullptr, 0));
     const int mo = e->L * 6 * D;
-    HIPCHK(ln_back(t->x_final, sc.g3, t->dx, mod, mld, mo, mo + D, 0));
+    CHK(t_ln_back(ch, mr, D, t->x_final, sc.g3, t->dx, mo, mo + D, 0));
     for (int i = e->L - 1; i >= 0; --i) {
         const WanBlockW& b = e->blk[i];
         const WTrainBlk& k = t->blk[i];
         const WBlkWT& w = ts->wt[i];
         const int m0 = i * 6 * D;
-        bf16_t* dpre = sc.wide + (size_t)M * 3 * D;          // [M][F] behind the [M][3D] q|k|v gradient
         // ---- feed-forward (gated residual)
-        HIPCHK(launch_gate_mul(t->dx, mod + m0 + 5 * D, mld, sc.g1, M, D, S, st));
-        if (G(i, ".ffn.net.2.weight") || G(i, ".ffn.net.2.bias")) {
-            if (G(i, ".ffn.net.2.weight")) HIPCHK(launch_gelu_fwd(k.pre, sc.hid, (long)M * F, st));
-            CHK(t_wgrad(sc, st, sc.g1, D, 0, D, sc.hid, F, F, M, t->M_pad, G(i, ".ffn.net.2.weight"), G(i, ".ffn.net.2.bias")));
-        }
-        CHK(t_dgrad(sc, st, sc.g1, D, D, w.ff2, M, F, dpre, F, k.pre, F));
-        if (G(i, ".ffn.net.0.proj.weight") || G(i, ".ffn.net.0.proj.bias"))
-            CHK(t_wgrad(sc, st, dpre, F, 0, F, k.xn3, D, D, M, t->M_pad, G(i, ".ffn.net.0.proj.weight"), G(i, ".ffn.net.0.proj.bias")));
-        CHK(t_dgrad(sc, st, dpre, F, F, w.ff1, M, D, sc.g3, D, nullptr, 0));
-        HIPCHK(ln_back(k.x_mid2, sc.g3, t->dx, mod, mld, m0 + 3 * D, m0 + 4 * D, 1));
+        CHK(t_mlp_back(sc, ch, mr, m0, D, F, t->dx, k.x_mid2, k.xn3, k.pre, w.ff1, w.ff2, G(i, ".ffn.net.0.proj"), G(i, ".ffn.net.2")));
         // ---- cross-attention (x += attn2(norm2(x), text): no gate): d (projection output) = d x
-        if (G(i, ".attn2.to_out.0.weight") || G(i, ".attn2.to_out.0.bias"))
-            CHK(t_wgrad(sc, st, t->dx, D, 0, D, k.o2, D, D, M, t->M_pad, G(i, ".attn2.to_out.0.weight"), G(i, ".attn2.to_out.0.bias")));
-        CHK(t_dgrad(sc, st, t->dx, D, D, w.o2, M, D, sc.g2, D, nullptr, 0));
+        CHK(t_linear_back(sc, ch, t->dx, D, D, k.o2, D, D, w.o2, G(i, ".attn2.to_out.0"), sc.g2, D));
         CHK(t_attention128_backward(sc, ag_cross, st, k.q2, t->kx + i * kx_el, t->vTx + i * kx_el, k.lse2, k.o2, nullptr, sc.g2, nullptr, S));
         // queries: full-row RMSNorm backward (no RoPE) -> d (to_q output) [M][D]
         HIPCHK(norm_back(k.q2, sc.dq, b.nq2, k.rstd_q2, false, kScale, sc.wide, D, 0, M, S, p->S_pad));
-        if (G(i, ".attn2.to_q.weight") || G(i, ".attn2.to_q.bias"))
-            CHK(t_wgrad(sc, st, sc.wide, D, 0, D, k.xn2, D, D, M, t->M_pad, G(i, ".attn2.to_q.weight"), G(i, ".attn2.to_q.bias")));
-        CHK(t_dgrad(sc, st, sc.wide, D, D, w.q2, M, D, sc.g3, D, nullptr, 0));
-        HIPCHK(ln_back(k.x_mid1, sc.g3, t->dx, b.ln2_mod, 0, 0, D, 1));          // norm2: LayerNorm with affine = modulation rows (bias, weight - 1)
+        CHK(t_linear_back(sc, ch, sc.wide, D, D, k.xn2, D, D, w.q2, G(i, ".attn2.to_q"), sc.g3, D));
+        CHK(t_ln_back(ch, ModRows{b.ln2_mod, 0, e->cfg.eps}, D, k.x_mid1, sc.g3, t->dx, 0, D, 1));          // norm2: LayerNorm with affine = modulation rows (bias, weight - 1)
         // keys / values: the text tokens' k (RMSNorm across heads, no RoPE) and v of THIS block -> d (to_k | to_v outputs) [Mc][2D]
-        if (G(i, ".attn2.to_k.weight") || G(i, ".attn2.to_k.bias") || G(i, ".attn2.to_v.weight") || G(i, ".attn2.to_v.bias")) {
+        const LinGrad gk2 = G(i, ".attn2.to_k"), gv2 = G(i, ".attn2.to_v");
+        if (gk2.w || gk2.b || gv2.w || gv2.b) {
             HIPCHK(norm_back(t->kx + i * kx_el, sc.dk, b.nk2, t->rstd_kx + (int64_t)i * Mc, false, 1.0f, t->widec, 2 * D, 0, Mc, p->Nt, p->Nt_pad));
             HIPCHK(norm_back(nullptr, sc.dvh, nullptr, nullptr, false, 1.0f, t->widec, 2 * D, D, Mc, p->Nt, p->Nt_pad));
-            const WgradSeg sg[2] = {{0, D, G(i, ".attn2.to_k.weight"), G(i, ".attn2.to_k.bias")}, {D, D, G(i, ".attn2.to_v.weight"), G(i, ".attn2.to_v.bias")}};
+            const WgradSeg sg[2] = {{0, D, gk2.w, gk2.b}, {D, D, gv2.w, gv2.b}};
             const WgradX xc{t->ctx, D, D};
             CHK(t_wgrad_group(sc, st, t->widec, 2 * D, sg, 2, &xc, 1, Mc, t->Mc_pad));
         }
         // ---- self-attention (gated residual)
         HIPCHK(launch_gate_mul(t->dx, mod + m0 + 2 * D, mld, sc.g1, M, D, S, st));
-        if (G(i, ".attn1.to_out.0.weight") || G(i, ".attn1.to_out.0.bias"))
-            CHK(t_wgrad(sc, st, sc.g1, D, 0, D, k.o1, D, D, M, t->M_pad, G(i, ".attn1.to_out.0.weight"), G(i, ".attn1.to_out.0.bias")));
-        CHK(t_dgrad(sc, st, sc.g1, D, D, w.o, M, D, sc.g2, D, nullptr, 0));
+        CHK(t_linear_back(sc, ch, sc.g1, D, D, k.o1, D, D, w.o, G(i, ".attn1.to_out.0"), sc.g2, D));
         CHK(t_attention128_backward(sc, ag_self, st, k.q, k.k, k.vT, k.lse1, k.o1, nullptr, sc.g2, nullptr, S));
         HIPCHK(norm_back(k.q, sc.dq, b.nq, k.rstd_q, true, kScale, sc.wide, 3 * D, 0, M, S, p->S_pad));
         HIPCHK(norm_back(k.k, sc.dk, b.nk, k.rstd_k, true, 1.0f, sc.wide, 3 * D, D, M, S, p->S_pad));
         HIPCHK(norm_back(nullptr, sc.dvh, nullptr, nullptr, false, 1.0f, sc.wide, 3 * D, 2 * D, M, S, p->S_pad));
         {
-            const char* nm[3] = {".attn1.to_q", ".attn1.to_k", ".attn1.to_v"};
-            WgradSeg sg[3];
-            for (int j = 0; j < 3; ++j)
-                sg[j] = WgradSeg{j * D, D, G(i, (std::string(nm[j]) + ".weight").c_str()), G(i, (std::string(nm[j]) + ".bias").c_str())};
+            const LinGrad gq = G(i, ".attn1.to_q"), gk = G(i, ".attn1.to_k"), gv = G(i, ".attn1.to_v");
+            const WgradSeg sg[3] = {{0, D, gq.w, gq.b}, {D, D, gk.w, gk.b}, {2 * D, D, gv.w, gv.b}};
             const WgradX xi{k.xn1, D, D};
             CHK(t_wgrad_group(sc, st, sc.wide, 3 * D, sg, 3, &xi, 1, M, t->M_pad));
         }
         CHK(t_dgrad(sc, st, sc.wide, 3 * D, 3 * D, w.qkv, M, D, sc.g3, D, nullptr, 0));
-        HIPCHK(ln_back(k.x_in, sc.g3, t->dx, mod, mld, m0, m0 + D, 1));
+        CHK(t_ln_back(ch, mr, D, k.x_in, sc.g3, t->dx, m0, m0 + D, 1));
     }
     CHK(t_wgrad_join(sc, st));
     return 0;
