@@ -166,11 +166,17 @@ extern "C" int mi355_flux_weights_ready(mi355_flux* e) { return e ? e->ready() :
 struct mi355_flux_plan {
     mi355_flux* e;
     int B, h, w, hp, wp, Ni, Nt, S, S_pad, Mi, Mc, M, max_steps;
+    // FLUX.1 Kontext (mi355_flux_plan_create_cond): Nc condition tokens per sample follow the Ni target tokens in the image stream, with rotary
+    // ids (1, row, col) on their own hc x wc grid.  Nx = Ni + Nc rows per sample run through the blocks (Mx = B * Nx, S = Nt + Nx); Ni / Mi /
+    // n_lat stay what the scheduler step sees.  A plain plan has Nc = 0: Nx = Ni, Mx = Mi.
+    int hc = 0, wc = 0, Nc = 0, Nx, Mx;
     int64_t n_lat;      // packed elements per sample = Ni * in_channels
     char* ws = nullptr;
     size_t ws_bytes = 0;
     bf16_t *lat16, *x, *c, *c0, *xn, *cn, *y, *yn, *qkbuf, *q, *k, *vT, *o_img, *o_ctx, *big, *v;
     bf16_t *tproj, *gproj, *h1, *p1, *pemb, *gemb, *semb, *mod_all;
+    bf16_t *cond16, *cemb;      // condition plan: the condition latents as bf16 [B][Nc][C] and embedded [B][Nc][D] (constant over a rollout)
+    char* io_cond;              // ... and staged in their own dtype (the captured rollout reads fixed addresses)
     float2* cs;
     float *t_dev, *g_dev, *scal;
     char *io_init, *io_traj;
@@ -187,26 +193,31 @@ struct mi355_flux_plan {
     PlanTrain* train = nullptr;         // training workspace (flux_train.inc: mi355_flux_train), created by the first training-mode forward
 };
 
-extern "C" int mi355_flux_plan_create(mi355_flux* e, int batch, int latent_h, int latent_w, int n_text, int max_steps,
-                                      mi355_flux_plan** out) {
+// cond_h x cond_w = the unpacked latent grid of the condition image (FLUX.1 Kontext), or 0 x 0 = a plain plan
+extern "C" int mi355_flux_plan_create_cond(mi355_flux* e, int batch, int latent_h, int latent_w, int cond_h, int cond_w, int n_text, int max_steps,
+                                           mi355_flux_plan** out) {
     if (!e || !out) return errorf("mi355_flux_plan_create: null argument");
     if (batch < 1 || n_text < 1 || max_steps < 1 || latent_h < 2 || latent_w < 2 || (latent_h | latent_w) & 1)
         return errorf("mi355_flux_plan_create: bad shape (latent size must be even)");
+    if ((cond_h | cond_w) != 0 && (cond_h < 2 || cond_w < 2 || (cond_h | cond_w) & 1))
+        return errorf("mi355_flux_plan_create_cond: bad condition grid %d x %d (both even and >= 2, or both 0)", cond_h, cond_w);
     mi355_flux_plan* p = new mi355_flux_plan();
     p->e = e; p->B = batch; p->h = latent_h; p->w = latent_w; p->hp = latent_h / 2; p->wp = latent_w / 2;
-    p->Ni = p->hp * p->wp; p->Nt = n_text; p->S = p->Ni + p->Nt; p->S_pad = (p->S + 63) / 64 * 64;
-    p->Mi = batch * p->Ni; p->Mc = batch * p->Nt; p->M = batch * p->S; p->max_steps = max_steps;
+    p->hc = cond_h / 2; p->wc = cond_w / 2; p->Nc = p->hc * p->wc;
+    p->Ni = p->hp * p->wp; p->Nx = p->Ni + p->Nc; p->Nt = n_text; p->S = p->Nx + p->Nt; p->S_pad = (p->S + 63) / 64 * 64;
+    p->Mi = batch * p->Ni; p->Mx = batch * p->Nx; p->Mc = batch * p->Nt; p->M = batch * p->S; p->max_steps = max_steps;
     p->n_lat = (int64_t)p->Ni * e->cfg.in_channels;
     const int D = e->D, F = e->F;
     const int64_t rows_cond = (int64_t)max_steps * batch;
     const int64_t qk_el = (int64_t)batch * e->H * p->S_pad * 128;
     const int64_t nl = (int64_t)batch * p->n_lat;
+    const int64_t ncl = (int64_t)batch * p->Nc * e->cfg.in_channels;
     Carver c;
-    c.take(p->lat16, nl); c.take(p->x, (int64_t)p->Mi * D); c.take(p->c, (int64_t)p->Mc * D); c.take(p->c0, (int64_t)p->Mc * D);
-    c.take(p->xn, (int64_t)p->Mi * D); c.take(p->cn, (int64_t)p->Mc * D);
+    c.take(p->lat16, nl); c.take(p->x, (int64_t)p->Mx * D); c.take(p->c, (int64_t)p->Mc * D); c.take(p->c0, (int64_t)p->Mc * D);
+    c.take(p->xn, (int64_t)p->Mx * D); c.take(p->cn, (int64_t)p->Mc * D);
     c.take(p->y, (int64_t)p->M * D); c.take(p->yn, (int64_t)p->M * D); c.take(p->qkbuf, (int64_t)p->M * 2 * D);
     c.take(p->q, qk_el); c.take(p->k, qk_el); c.take(p->vT, qk_el);
-    c.take(p->o_img, (int64_t)p->Mi * D); c.take(p->o_ctx, (int64_t)p->Mc * D);
+    c.take(p->o_img, (int64_t)p->Mx * D); c.take(p->o_ctx, (int64_t)p->Mc * D);
     c.take(p->big, (int64_t)p->M * (D + F));        // single blocks: [attn | gelu(mlp)]; double blocks: ff hidden (img, then ctx)
     c.take(p->v, nl);
     c.take(p->tproj, rows_cond * e->cfg.time_proj_dim); c.take(p->gproj, (int64_t)batch * e->cfg.time_proj_dim);
@@ -217,16 +228,18 @@ extern "C" int mi355_flux_plan_create(mi355_flux* e, int batch, int latent_h, in
     c.take(p->io_init, nl * 4); c.take(p->io_traj, (int64_t)(max_steps + 1) * nl * 4); c.take(p->io_noise, (int64_t)max_steps * nl);
     c.take(p->io_lp, (int64_t)max_steps * batch);
     c.take(p->io_pe, (int64_t)batch * p->Nt * e->cfg.joint_attention_dim); c.take(p->io_pp, (int64_t)batch * e->cfg.pooled_projection_dim);
+    c.take(p->cond16, ncl); c.take(p->cemb, (int64_t)batch * p->Nc * D); c.take(p->io_cond, ncl * 4);
     // zeroed: the padded key rows / columns of q, k, vT must stay finite
     if (c.alloc(&p->ws, &p->ws_bytes, true, "mi355_flux_plan_create") != 0) { delete p; return 1; }
-    // rotary table of the joint sequence [txt (ids 0) | img (0, row, col)]: FluxPosEmbed evaluates the angles in float64
-    // (get_1d_rotary_pos_embed(freqs_dtype=float64)) and casts cos / sin to fp32
+    // rotary table of the joint sequence [txt (ids 0) | img (0, row, col) on hp x wp | condition (1, row, col) on hc x wc]: FluxPosEmbed
+    // evaluates the angles in float64 (get_1d_rotary_pos_embed(freqs_dtype=float64)) and casts cos / sin to fp32
     {
         std::vector<float> cs((size_t)p->S * 128);
         const int* ax = e->cfg.axes_dims_rope;
         for (int s = 0; s < p->S; ++s) {
             double pos[3] = {0.0, 0.0, 0.0};
-            if (s >= p->Nt) { const int t = s - p->Nt; pos[1] = t / p->wp; pos[2] = t % p->wp; }
+            if (s >= p->Nt + p->Ni) { const int t = s - p->Nt - p->Ni; pos[0] = 1.0; pos[1] = t / p->wc; pos[2] = t % p->wc; }
+            else if (s >= p->Nt) { const int t = s - p->Nt; pos[1] = t / p->wp; pos[2] = t % p->wp; }
             int pair = 0;
             for (int a = 0; a < 3; ++a)
                 for (int j = 0; j < ax[a] / 2; ++j, ++pair) {
@@ -242,6 +255,18 @@ extern "C" int mi355_flux_plan_create(mi355_flux* e, int batch, int latent_h, in
         }
     }
     *out = p;
+    return 0;
+}
+
+extern "C" int mi355_flux_plan_create(mi355_flux* e, int batch, int latent_h, int latent_w, int n_text, int max_steps,
+                                      mi355_flux_plan** out) {
+    return mi355_flux_plan_create_cond(e, batch, latent_h, latent_w, 0, 0, n_text, max_steps, out);
+}
+
+// the plan's rotary table [S][64] (cos, sin) fp32 -> host (tests; synchronises)
+extern "C" int mi355_flux_plan_rope_table(mi355_flux_plan* p, float* out_host) {
+    if (!p || !out_host) return errorf("mi355_flux_plan_rope_table: null argument");
+    HIPCHK(hipMemcpy(out_host, p->cs, (size_t)p->S * 64 * sizeof(float2), hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -391,7 +416,7 @@ int g_flux_two_stream_rows = 16384;
 int g_flux_graph = 1;
 
 bool flux_two_stream_wanted(const mi355_flux_plan* p) {
-    return g_flux_two_stream == 1 || (g_flux_two_stream == 2 && p->Mi <= g_flux_two_stream_rows);
+    return g_flux_two_stream == 1 || (g_flux_two_stream == 2 && p->Mx <= g_flux_two_stream_rows);
 }
 
 int flux_two_stream_init(mi355_flux_plan* p) {
@@ -419,8 +444,8 @@ int forward_core(mi355_flux_plan* p, hipStream_t st, const void* latents, int la
                  const DoubleStash* dbl = nullptr, const FTrainSgl* sgl = nullptr, bf16_t* x_final = nullptr) {
     mi355_flux* e = p->e;
     const int D = e->D, F = e->F, C = e->cfg.in_channels;
-    const int Ni = p->Ni, Nt = p->Nt, S = p->S;
-    const size_t xi_b = (size_t)p->Mi * D * 2, xc_b = (size_t)p->Mc * D * 2, y_b = (size_t)p->M * D * 2;
+    const int Ni = p->Ni, Nx = p->Nx, Nt = p->Nt, S = p->S, Mx = p->Mx;     // Nx / Mx: image-stream rows (target + condition tokens); Ni: target rows
+    const size_t xi_b = (size_t)Mx * D * 2, xc_b = (size_t)p->Mc * D * 2, y_b = (size_t)p->M * D * 2;
     const bool two = flux_two_stream_wanted(p) && e->L > 0;
     hipStream_t ts = st;                               // carries the text chain of the double blocks
     bf16_t *qkb_c = p->qkbuf, *big_c = p->big;
@@ -433,8 +458,11 @@ int forward_core(mi355_flux_plan* p, hipStream_t st, const void* latents, int la
         HIPCHK(launch_convert(latents, lat_dt, p->lat16, DT_BF16, (long)p->B * p->n_lat, st));
         lat = p->lat16;
     }
-    GemmParams gx = make_gemm(lat, C, e->w_x, C, p->Mi, D, C, EPI_BIAS, e->b_x, p->x, D);
+    // condition plan: the target rows are embedded aside (xn is free here) and interleaved per sample with the condition rows, which
+    // prepare_condition embedded once (GEMM rows are independent: the bits of embedding cat([latents, image_latents], dim=1))
+    GemmParams gx = make_gemm(lat, C, e->w_x, C, p->Mi, D, C, EPI_BIAS, e->b_x, p->Nc ? p->xn : p->x, D);
     HIPCHK(launch_gemm(gx, st));
+    if (p->Nc) HIPCHK(launch_concat_rows(p->xn, Ni, p->cemb, p->Nc, p->x, p->B, D, st));
     HIPCHK(copy_d2d(p->c, p->c0, xc_b, st));
     if (two) {          // c, the conditioning (modulation table, prompt) and the previous forward are complete on `st`
         HIPCHK(ev_record(p->ev_fork[e->L], st));
@@ -453,8 +481,8 @@ int forward_core(mi355_flux_plan* p, hipStream_t st, const void* latents, int la
         }
         CHK(ln_mod(p, ts, p->c, cn, mod, p->Mc, Nt, mc, mc + D));
         CHK(qkv(p, ts, cn, p->Mc, Nt, 0, b.w_cqk, b.b_cqk, b.w_cv, b.b_cv, b.ncq, b.nck, qkb_c, q, k, vT, tb ? tb->rstd_ctx : nullptr));
-        CHK(ln_mod(p, st, p->x, xn, mod, p->Mi, Ni, mi, mi + D));
-        CHK(qkv(p, st, xn, p->Mi, Ni, Nt, b.w_qk, b.b_qk, b.w_v, b.b_v, b.nq, b.nk, p->qkbuf, q, k, vT, tb ? tb->rstd_img : nullptr));
+        CHK(ln_mod(p, st, p->x, xn, mod, Mx, Nx, mi, mi + D));
+        CHK(qkv(p, st, xn, Mx, Nx, Nt, b.w_qk, b.b_qk, b.w_v, b.b_v, b.nq, b.nk, p->qkbuf, q, k, vT, tb ? tb->rstd_img : nullptr));
         if (two) {      // join: the attention reads the text rows of q / k / vT
             HIPCHK(ev_record(p->ev_join[i], ts));
             HIPCHK(ev_wait(st, p->ev_join[i]));
@@ -464,15 +492,15 @@ int forward_core(mi355_flux_plan* p, hipStream_t st, const void* latents, int la
             HIPCHK(ev_record(p->ev_fork[i], st));
             HIPCHK(ev_wait(ts, p->ev_fork[i]));
         }
-        CHK(gate_res(p, st, o_img, D, D, b.w_o, b.b_o, p->x, p->Mi, Ni, mod, mi + 2 * D));
+        CHK(gate_res(p, st, o_img, D, D, b.w_o, b.b_o, p->x, Mx, Nx, mod, mi + 2 * D));
         CHK(gate_res(p, ts, o_ctx, D, D, b.w_co, b.b_co, p->c, p->Mc, Nt, mod, mc + 2 * D));
         bf16_t* xn2 = tb ? tb->xn_mlp : p->xn;
         if (tb) HIPCHK(copy_d2d(tb->x_mid, p->x, xi_b, st));
-        CHK(ln_mod(p, st, p->x, xn2, mod, p->Mi, Ni, mi + 3 * D, mi + 4 * D));
-        GemmParams f1 = make_gemm(xn2, D, b.w_ff1, D, p->Mi, F, D, EPI_BIAS_GELU, b.b_ff1, p->big, F);
+        CHK(ln_mod(p, st, p->x, xn2, mod, Mx, Nx, mi + 3 * D, mi + 4 * D));
+        GemmParams f1 = make_gemm(xn2, D, b.w_ff1, D, Mx, F, D, EPI_BIAS_GELU, b.b_ff1, p->big, F);
         if (tb) { f1.stash = tb->pre; f1.ld_stash = F; }
         HIPCHK(launch_gemm(f1, st));
-        CHK(gate_res(p, st, p->big, F, F, b.w_ff2, b.b_ff2, p->x, p->Mi, Ni, mod, mi + 5 * D));
+        CHK(gate_res(p, st, p->big, F, F, b.w_ff2, b.b_ff2, p->x, Mx, Nx, mod, mi + 5 * D));
         bf16_t* cn2 = tb ? tb->cn_mlp : p->cn;
         if (tb) HIPCHK(copy_d2d(tb->c_mid, p->c, xc_b, ts));
         CHK(ln_mod(p, ts, p->c, cn2, mod, p->Mc, Nt, mc + 3 * D, mc + 4 * D));
@@ -489,10 +517,10 @@ int forward_core(mi355_flux_plan* p, hipStream_t st, const void* latents, int la
     const size_t rowb = (size_t)D * 2;
     if (sched_trace_on()) {
         sched_trace_launch("copy2d.c->y", st, {treg(p->c, (size_t)p->B * Nt * rowb)}, {tregs(p->y, (size_t)Nt * rowb, (size_t)S * rowb, (size_t)p->B)});
-        sched_trace_launch("copy2d.x->y", st, {treg(p->x, (size_t)p->B * Ni * rowb)}, {tregs(p->y + (size_t)Nt * D, (size_t)Ni * rowb, (size_t)S * rowb, (size_t)p->B)});
+        sched_trace_launch("copy2d.x->y", st, {treg(p->x, (size_t)p->B * Nx * rowb)}, {tregs(p->y + (size_t)Nt * D, (size_t)Nx * rowb, (size_t)S * rowb, (size_t)p->B)});
     }
     HIPCHK(hipMemcpy2DAsync(p->y, (size_t)S * rowb, p->c, (size_t)Nt * rowb, (size_t)Nt * rowb, p->B, hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipMemcpy2DAsync(p->y + (size_t)Nt * D, (size_t)S * rowb, p->x, (size_t)Ni * rowb, (size_t)Ni * rowb, p->B,
+    HIPCHK(hipMemcpy2DAsync(p->y + (size_t)Nt * D, (size_t)S * rowb, p->x, (size_t)Nx * rowb, (size_t)Nx * rowb, p->B,
                             hipMemcpyDeviceToDevice, st));
     for (int i = 0; i < e->LS; ++i) {
         const SingleW& b = e->sgl[i];
@@ -514,15 +542,42 @@ int forward_core(mi355_flux_plan* p, hipStream_t st, const void* latents, int la
         }
         CHK(gate_res(p, st, p->big, D + F, D + F, b.w_out, b.b_out, p->y, p->M, S, mod, m0 + 2 * D));
     }
-    // image rows back to a contiguous stream, AdaLayerNormContinuous (scale first), proj_out
+    // the target rows back to a contiguous stream (the condition rows have no consumer), AdaLayerNormContinuous (scale first), proj_out
     if (sched_trace_on())
         sched_trace_launch("copy2d.y->x", st, {tregs(p->y + (size_t)Nt * D, (size_t)Ni * rowb, (size_t)S * rowb, (size_t)p->B)}, {treg(p->x, (size_t)p->B * Ni * rowb)});
     HIPCHK(hipMemcpy2DAsync(p->x, (size_t)Ni * rowb, p->y + (size_t)Nt * D, (size_t)S * rowb, (size_t)Ni * rowb, p->B,
                             hipMemcpyDeviceToDevice, st));
-    if (x_final) HIPCHK(copy_d2d(x_final, p->x, xi_b, st));
+    if (x_final) HIPCHK(copy_d2d(x_final, p->x, (size_t)p->Mi * D * 2, st));
     CHK(ln_mod(p, st, p->x, p->xn, mod, p->Mi, Ni, e->mod_out + D, e->mod_out));
     GemmParams go = make_gemm(p->xn, D, e->w_proj, D, p->Mi, C, D, EPI_BIAS, e->b_proj, v_out, C);
     HIPCHK(launch_gemm(go, st));
+    return 0;
+}
+
+// condition plan: the staged condition latents [B][Nc][C] -> bf16 -> x_embedder -> cemb [B][Nc][D], the rows forward_core places behind each
+// sample's target rows.  Constant over a rollout: run once per call, outside the step loop.
+int prepare_condition(mi355_flux_plan* p, hipStream_t st, const void* image_latents, int image_dt) {
+    mi355_flux* e = p->e;
+    const int C = e->cfg.in_channels, Mn = p->B * p->Nc;
+    const bf16_t* c16 = (const bf16_t*)image_latents;
+    if (image_dt != DT_BF16) {
+        HIPCHK(launch_convert(image_latents, image_dt, p->cond16, DT_BF16, (long)Mn * C, st));
+        c16 = p->cond16;
+    }
+    GemmParams g = make_gemm(c16, C, e->w_x, C, Mn, e->D, C, EPI_BIAS, e->b_x, p->cemb, e->D);
+    HIPCHK(launch_gemm(g, st));
+    return 0;
+}
+
+// the plain entry points serve plain plans, the _cond ones condition plans (`cond_entry`): anything else is refused before any launch
+int check_condition(const char* who, const mi355_flux_plan* p, bool cond_entry, const void* image_latents, int image_dt) {
+    if (!cond_entry) {
+        if (p->Nc) return errorf("%s: this plan has %d condition tokens per sample (mi355_flux_plan_create_cond): call %s_cond with image_latents", who, p->Nc, who);
+        return 0;
+    }
+    if (!p->Nc) return errorf("%s_cond: this plan has no condition grid (mi355_flux_plan_create): call %s", who, who);
+    if (!image_latents) return errorf("%s_cond: image_latents is NULL", who);
+    if (image_dt < 0 || image_dt > 2) return errorf("%s_cond: bad image_latents dtype %d", who, image_dt);
     return 0;
 }
 
@@ -550,11 +605,12 @@ void set_flux_graph(int on) { g_flux_graph = on; }
 
 // transformer only (replay / tests): t_model[B] and guidance_model[B] are the values the network embeds (device fp32):
 // the adapter passes t/1000 and the model multiplies by 1000 in the latents' dtype (see mi355_flux_rollout)
-extern "C" int mi355_flux_forward(mi355_flux_plan* p, void* stream, const void* latents, int lat_dtype, const float* t_model,
-                                  const float* guidance_model, const void* prompt_embeds, const void* pooled, void* v_out) {
+static int flux_forward(mi355_flux_plan* p, void* stream, const void* latents, int lat_dtype, const float* t_model, const float* guidance_model,
+                        const void* prompt_embeds, const void* pooled, void* v_out, bool cond_entry, const void* image_latents, int image_dtype) {
     if (!p || !latents || !t_model || !prompt_embeds || !pooled || !v_out) return errorf("mi355_flux_forward: null argument");
     if (p->e->cfg.guidance_embeds && !guidance_model) return errorf("mi355_flux_forward: this model embeds guidance, guidance_model is NULL");
     if (lat_dtype < 0 || lat_dtype > 2) return errorf("mi355_flux_forward: bad latent dtype %d", lat_dtype);
+    CHK(check_condition("mi355_flux_forward", p, cond_entry, image_latents, image_dtype));
     CHK(mi355_flux_weights_ready(p->e));
     hipStream_t st = (hipStream_t)stream;
     CHK(update_score_bounds(p->e, st));
@@ -562,19 +618,31 @@ extern "C" int mi355_flux_forward(mi355_flux_plan* p, void* stream, const void* 
     if (guidance_model) HIPCHK(copy_d2d(p->g_dev, guidance_model, (size_t)p->B * 4, st));
     CHK(prepare_prompt(p, st, prompt_embeds, pooled));
     CHK(prepare_conditioning(p, st, 1));
+    if (cond_entry) CHK(prepare_condition(p, st, image_latents, image_dtype));
     return forward_core(p, st, latents, lat_dtype, p->mod_all, (bf16_t*)v_out);
+}
+extern "C" int mi355_flux_forward(mi355_flux_plan* p, void* stream, const void* latents, int lat_dtype, const float* t_model,
+                                  const float* guidance_model, const void* prompt_embeds, const void* pooled, void* v_out) {
+    return flux_forward(p, stream, latents, lat_dtype, t_model, guidance_model, prompt_embeds, pooled, v_out, false, nullptr, 0);
+}
+// FLUX.1 Kontext: mi355_flux_forward on a condition plan; image_latents [B][Nc][in_channels] packed, per call (not plan state)
+extern "C" int mi355_flux_forward_cond(mi355_flux_plan* p, void* stream, const void* latents, int lat_dtype, const float* t_model,
+                                       const float* guidance_model, const void* prompt_embeds, const void* pooled, void* v_out,
+                                       const void* image_latents, int image_dtype) {
+    return flux_forward(p, stream, latents, lat_dtype, t_model, guidance_model, prompt_embeds, pooled, v_out, true, image_latents, image_dtype);
 }
 
 // The whole N-step rollout (flux1.py:222-259) with zero host syncs.  timesteps_host: scheduler timesteps in [0, 1000];
 // sigmas_host: scheduler sigmas (sigma_max = sigmas[1]); noise_levels_host: eta per step; guidance_scale: embedded guidance.
 // Latents are PACKED [B][Ni][in_channels]; step_noise fp32 [n_steps][B][Ni*in_channels].
-extern "C" int mi355_flux_rollout(mi355_flux_plan* p, void* stream, int n_steps, const float* timesteps_host, const float* sigmas_host,
-                                  const float* noise_levels_host, int dynamics, float guidance_scale, const void* init_latents,
-                                  int init_dtype, int storage_dtype, const float* step_noise, const void* prompt_embeds,
-                                  const void* pooled, const int32_t* keep_slot_host, void* out_latents, float* out_log_probs,
-                                  void* out_final, int compute_log_prob) {
+static int flux_rollout(mi355_flux_plan* p, void* stream, int n_steps, const float* timesteps_host, const float* sigmas_host,
+                        const float* noise_levels_host, int dynamics, float guidance_scale, const void* init_latents, int init_dtype,
+                        int storage_dtype, const float* step_noise, const void* prompt_embeds, const void* pooled,
+                        const int32_t* keep_slot_host, void* out_latents, float* out_log_probs, void* out_final, int compute_log_prob,
+                        bool cond_entry, const void* image_latents, int image_dtype) {
     if (!p || !timesteps_host || !sigmas_host || !noise_levels_host || !init_latents || !prompt_embeds || !pooled)
         return errorf("mi355_flux_rollout: null argument");
+    CHK(check_condition("mi355_flux_rollout", p, cond_entry, image_latents, image_dtype));
     if (n_steps < 1 || n_steps > p->max_steps) return errorf("mi355_flux_rollout: n_steps %d exceeds the plan's max_steps %d", n_steps, p->max_steps);
     if (storage_dtype < 0 || storage_dtype > 2 || init_dtype < 0 || init_dtype > 2) return errorf("mi355_flux_rollout: bad dtype");
     if (!step_noise && dynamics != MI355_ODE) return errorf("mi355_flux_rollout: step_noise is NULL");
@@ -609,6 +677,8 @@ extern "C" int mi355_flux_rollout(mi355_flux_plan* p, void* stream, int n_steps,
     if (step_noise) HIPCHK(copy_d2d(p->io_noise, step_noise, (size_t)n_steps * nl * 4, st));
     HIPCHK(copy_d2d(p->io_pe, prompt_embeds, (size_t)B * p->Nt * p->e->cfg.joint_attention_dim * 2, st));
     HIPCHK(copy_d2d(p->io_pp, pooled, (size_t)B * p->e->cfg.pooled_projection_dim * 2, st));
+    if (cond_entry)
+        HIPCHK(copy_d2d(p->io_cond, image_latents, (size_t)B * p->Nc * p->e->cfg.in_channels * (image_dtype == MI355_F32 ? 4 : 2), st));
     const float sigma_max = sigmas_host[1];
     const int clp = compute_log_prob && out_log_probs;
     const size_t esz = storage_dtype == MI355_F32 ? 4 : 2;
@@ -617,6 +687,7 @@ extern "C" int mi355_flux_rollout(mi355_flux_plan* p, void* stream, int n_steps,
     auto body = [&](hipStream_t s) -> int {
         CHK(prepare_prompt(p, s, p->io_pe, p->io_pp));
         CHK(prepare_conditioning(p, s, n_steps));
+        if (cond_entry) CHK(prepare_condition(p, s, p->io_cond, image_dtype));       // once per rollout: the condition does not change with the step
         HIPCHK(launch_convert(p->io_init, init_dtype, p->io_traj, storage_dtype, (long)nl, s));      // cast_latents(init)
         for (int i = 0; i < n_steps; ++i) {
             const bf16_t* mod = p->mod_all + (int64_t)i * B * p->e->mod_cols;
@@ -632,7 +703,7 @@ extern "C" int mi355_flux_rollout(mi355_flux_plan* p, void* stream, int n_steps,
     if (g_flux_graph && p->graph.warmed) {
         const int two = (int)flux_two_stream_wanted(p);
         const int key[RolloutGraph::NKEY] = {n_steps, dynamics, storage_dtype, init_dtype, clp, (int)(step_noise != nullptr), float_bits(sigma_max),
-                                             p->e->bounds_ver, two, get_gemm_variant(), get_attn128_variant(), tune_epoch()};
+                                             p->e->bounds_ver, two, get_gemm_variant(), get_attn128_variant(), tune_epoch(), (int)cond_entry, cond_entry ? image_dtype : 0};
         // (streams / events / buffers are created outside the capture)
         CHK(p->graph.launch(key, st, "mi355_flux_rollout", n_steps, 16, [&] { return two ? flux_two_stream_init(p) : 0; }, body));
     } else {
@@ -651,6 +722,25 @@ extern "C" int mi355_flux_rollout(mi355_flux_plan* p, void* stream, int n_steps,
     if (out_final)
         HIPCHK(copy_d2d(out_final, p->io_traj + (size_t)n_steps * lat_bytes, lat_bytes, st));
     return 0;
+}
+extern "C" int mi355_flux_rollout(mi355_flux_plan* p, void* stream, int n_steps, const float* timesteps_host, const float* sigmas_host,
+                                  const float* noise_levels_host, int dynamics, float guidance_scale, const void* init_latents,
+                                  int init_dtype, int storage_dtype, const float* step_noise, const void* prompt_embeds,
+                                  const void* pooled, const int32_t* keep_slot_host, void* out_latents, float* out_log_probs,
+                                  void* out_final, int compute_log_prob) {
+    return flux_rollout(p, stream, n_steps, timesteps_host, sigmas_host, noise_levels_host, dynamics, guidance_scale, init_latents, init_dtype,
+                        storage_dtype, step_noise, prompt_embeds, pooled, keep_slot_host, out_latents, out_log_probs, out_final, compute_log_prob,
+                        false, nullptr, 0);
+}
+// FLUX.1 Kontext: mi355_flux_rollout on a condition plan; the condition is staged, converted and embedded once per call
+extern "C" int mi355_flux_rollout_cond(mi355_flux_plan* p, void* stream, int n_steps, const float* timesteps_host, const float* sigmas_host,
+                                       const float* noise_levels_host, int dynamics, float guidance_scale, const void* init_latents,
+                                       int init_dtype, int storage_dtype, const float* step_noise, const void* prompt_embeds,
+                                       const void* pooled, const int32_t* keep_slot_host, void* out_latents, float* out_log_probs,
+                                       void* out_final, int compute_log_prob, const void* image_latents, int image_dtype) {
+    return flux_rollout(p, stream, n_steps, timesteps_host, sigmas_host, noise_levels_host, dynamics, guidance_scale, init_latents, init_dtype,
+                        storage_dtype, step_noise, prompt_embeds, pooled, keep_slot_host, out_latents, out_log_probs, out_final, compute_log_prob,
+                        true, image_latents, image_dtype);
 }
 
 // ----------------------------------------------------------------------- operator-level API

@@ -334,7 +334,28 @@ __global__ __launch_bounds__(256) void cfg_rescale_bwd_kernel(const bf16_t* neg,
     dpos[m * 64 + lane] = f2bf(g * dcomb + dot * c / (cn * nn));
 }
 
+// out[b] = [a[b] (Na rows) | c[b] (Nc rows)] for every sample b: rows of W 16-byte chunks, one chunk per thread
+__global__ __launch_bounds__(256) void concat_rows_kernel(const uint4* a, int Na, const uint4* c, int Nc, uint4* out, long total, int W) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const long row = i / W;
+    const int col = (int)(i - row * W);
+    const long b = row / (Na + Nc);
+    const int r = (int)(row - b * (Na + Nc));
+    out[i] = r < Na ? a[(b * Na + r) * W + col] : c[(b * Nc + (r - Na)) * W + col];
+}
+
 }  // namespace
+
+hipError_t launch_concat_rows(const bf16_t* a, int Na, const bf16_t* c, int Nc, bf16_t* out, int B, int D, hipStream_t stream) {
+    if (B <= 0 || Na <= 0 || Nc <= 0 || D <= 0 || (D & 7) || (((uintptr_t)a | (uintptr_t)c | (uintptr_t)out) & 15)) return hipErrorInvalidValue;
+    if (sched_trace_on())
+        sched_trace_launch("concat_rows", stream, {treg(a, (size_t)B * Na * D * 2), treg(c, (size_t)B * Nc * D * 2)}, {treg(out, (size_t)B * (Na + Nc) * D * 2)});
+    const long total = (long)B * (Na + Nc) * (D / 8);
+    hipLaunchKernelGGL(concat_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, (const uint4*)a, Na, (const uint4*)c, Nc, (uint4*)out,
+                       total, D / 8);
+    return hipGetLastError();
+}
 
 hipError_t launch_rms_rows(const bf16_t* x, long ldx, const float* w, bf16_t* out, long ldo, int M, int D, float eps, hipStream_t stream) {
     if (M <= 0 || D <= 0 || (D & 1) || (ldx & 1) || (ldo & 1)) return hipErrorInvalidValue;      // (validation first: the trace's region arithmetic assumes M >= 1)

@@ -37,7 +37,7 @@ struct mi355_flux_train : PlanTrain {      // per plan
     std::vector<FTrainSgl> sgl;
     bf16_t *x_final, *mod;
     bf16_t *dyj, *dx, *dc, *dvb;            // backward: residual-stream gradients
-    int M_pad, Mi_pad, Mc_pad;
+    int M_pad, Mi_pad, Mx_pad, Mc_pad;      // Mi: the target rows (what the final layer sees), Mx: every image-stream row
 };
 
 }  // namespace
@@ -109,22 +109,22 @@ static int flux_train_of(mi355_flux_plan* p, mi355_flux_train** out) {
     if (p->train) { *out = static_cast<mi355_flux_train*>(p->train); return 0; }
     mi355_flux* e = p->e;
     const int D = e->D, F = e->F, L = e->L, LS = e->LS, H = e->H, C = e->cfg.in_channels;
-    const int Mi = p->Mi, Mc = p->Mc, M = p->M;
+    const int Mi = p->Mi, Mx = p->Mx, Mc = p->Mc, M = p->M;
     const int64_t qk_el = (int64_t)p->B * H * p->S_pad * 128;
     const int64_t bhs = (int64_t)p->B * H * p->S_pad;
     mi355_flux_train* t = new mi355_flux_train();
-    t->M_pad = (M + 63) / 64 * 64; t->Mi_pad = (Mi + 63) / 64 * 64; t->Mc_pad = (Mc + 63) / 64 * 64;
+    t->M_pad = (M + 63) / 64 * 64; t->Mi_pad = (Mi + 63) / 64 * 64; t->Mx_pad = (Mx + 63) / 64 * 64; t->Mc_pad = (Mc + 63) / 64 * 64;
     TrainScratch& sc = t->sc;
     Carver c;
     t->dbl.resize(L); t->sgl.resize(LS);
-    for (DoubleStash& k : t->dbl) t_double_stash_take(c, k, Mi, Mc, D, F, H, qk_el, bhs);
+    for (DoubleStash& k : t->dbl) t_double_stash_take(c, k, Mx, Mc, D, F, H, qk_el, bhs);
     for (FTrainSgl& k : t->sgl) {
         c.take(k.y_in, (int64_t)M * D); c.take(k.yn, (int64_t)M * D); c.take(k.pre, (int64_t)M * F); c.take(k.o, (int64_t)M * D);
         c.take(k.q, qk_el); c.take(k.k, qk_el); c.take(k.vT, qk_el);
         c.take(k.lse, bhs); c.take(k.rstd, (int64_t)M * 2 * H);
     }
     c.take(t->x_final, (int64_t)Mi * D); c.take(t->mod, (int64_t)p->B * e->mod_cols);
-    c.take(t->dyj, (int64_t)M * D); c.take(t->dx, (int64_t)Mi * D); c.take(t->dc, (int64_t)Mc * D);
+    c.take(t->dyj, (int64_t)M * D); c.take(t->dx, (int64_t)Mx * D); c.take(t->dc, (int64_t)Mc * D);
     c.take(sc.g1, (int64_t)M * D); c.take(sc.g1c, (int64_t)Mc * D); c.take(sc.g2, (int64_t)M * D); c.take(sc.g2c, (int64_t)Mc * D);
     c.take(sc.g3, (int64_t)M * D); c.take(sc.g3c, (int64_t)Mc * D);
     c.take(sc.wide, (int64_t)M * (3 * D + F)); c.take(sc.widec, (int64_t)Mc * (3 * D + F)); c.take(sc.hid, (int64_t)M * F);
@@ -139,11 +139,12 @@ static int flux_train_of(mi355_flux_plan* p, mi355_flux_train** out) {
 // ---- training-mode forward: forward_core (flux_engine.hip) on the per-block stash ------------------------------------------------------
 // transformer only, training mode: arguments as mi355_flux_forward; the activations the backward needs stay in the plan's training stash
 // (ONE stash per plan, overwritten by every call)
-extern "C" int mi355_flux_forward_train(mi355_flux_plan* p, void* stream, const void* latents, int lat_dtype, const float* t_model,
-                                        const float* guidance_model, const void* prompt_embeds, const void* pooled, void* v_out) {
+static int flux_forward_train(mi355_flux_plan* p, void* stream, const void* latents, int lat_dtype, const float* t_model, const float* guidance_model,
+                              const void* prompt_embeds, const void* pooled, void* v_out, bool cond_entry, const void* image_latents, int image_dtype) {
     if (!p || !latents || !t_model || !prompt_embeds || !pooled || !v_out) return errorf("mi355_flux_forward_train: null argument");
     if (p->e->cfg.guidance_embeds && !guidance_model) return errorf("mi355_flux_forward_train: this model embeds guidance, guidance_model is NULL");
     if (lat_dtype < 0 || lat_dtype > 2) return errorf("mi355_flux_forward_train: bad latent dtype %d", lat_dtype);
+    CHK(check_condition("mi355_flux_forward_train", p, cond_entry, image_latents, image_dtype));
     CHK(mi355_flux_weights_ready(p->e));
     hipStream_t st = (hipStream_t)stream;
     CHK(update_score_bounds(p->e, st));
@@ -153,11 +154,23 @@ extern "C" int mi355_flux_forward_train(mi355_flux_plan* p, void* stream, const 
     if (guidance_model) HIPCHK(copy_d2d(p->g_dev, guidance_model, (size_t)p->B * 4, st));
     CHK(prepare_prompt(p, st, prompt_embeds, pooled));
     CHK(prepare_conditioning(p, st, 1));
+    if (cond_entry) CHK(prepare_condition(p, st, image_latents, image_dtype));
     CHK(forward_core(p, st, latents, lat_dtype, p->mod_all, (bf16_t*)v_out, t->dbl.data(), t->sgl.data(), t->x_final));
     // this step's modulation rows: the plan's own copy may be overwritten by a no-grad forward (the KL reference pass) before the backward runs
     HIPCHK(copy_d2d(t->mod, p->mod_all, (size_t)p->B * p->e->mod_cols * 2, st));
     t->have_forward = true;
     return 0;
+}
+extern "C" int mi355_flux_forward_train(mi355_flux_plan* p, void* stream, const void* latents, int lat_dtype, const float* t_model,
+                                        const float* guidance_model, const void* prompt_embeds, const void* pooled, void* v_out) {
+    return flux_forward_train(p, stream, latents, lat_dtype, t_model, guidance_model, prompt_embeds, pooled, v_out, false, nullptr, 0);
+}
+// FLUX.1 Kontext: mi355_flux_forward_train on a condition plan (arguments as mi355_flux_forward_cond).  No gradient flows to image_latents:
+// x_embedder is outside the native gradient scope.
+extern "C" int mi355_flux_forward_train_cond(mi355_flux_plan* p, void* stream, const void* latents, int lat_dtype, const float* t_model,
+                                             const float* guidance_model, const void* prompt_embeds, const void* pooled, void* v_out,
+                                             const void* image_latents, int image_dtype) {
+    return flux_forward_train(p, stream, latents, lat_dtype, t_model, guidance_model, prompt_embeds, pooled, v_out, true, image_latents, image_dtype);
 }
 
 // ---- backward (helpers: train_common.h) ------------------------------------------------------------------------------------------
@@ -172,7 +185,7 @@ extern "C" int mi355_flux_backward(mi355_flux_plan* p, void* stream, const float
     CHK(flux_ensure_transposed(e, st));
     FluxTrainState* ts = flux_train_state(e);
     const int D = e->D, F = e->F, C = e->cfg.in_channels;
-    const int Ni = p->Ni, Nt = p->Nt, S = p->S, Mi = p->Mi, Mc = p->Mc, M = p->M;
+    const int Ni = p->Ni, Nx = p->Nx, Nt = p->Nt, S = p->S, Mi = p->Mi, Mx = p->Mx, Mc = p->Mc, M = p->M;
     const bf16_t* mod = t->mod;
     const long mld = e->mod_cols;
     const size_t rowb = (size_t)D * 2;
@@ -180,13 +193,14 @@ extern "C" int mi355_flux_backward(mi355_flux_plan* p, void* stream, const float
     const AttnGeom ag{p->B, e->H, D, S, p->S_pad, p->cs, nullptr};
     const ModRows mr{mod, mld, e->cfg.eps};
     const TrainChain joint{st, M, t->M_pad, S, sc.g1, sc.g2, sc.g3, sc.wide, sc.hid, false};
-    const TrainChain im{st, Mi, t->Mi_pad, Ni, sc.g1, sc.g2, sc.g3, sc.wide, sc.hid, false};
+    const TrainChain im{st, Mx, t->Mx_pad, Nx, sc.g1, sc.g2, sc.g3, sc.wide, sc.hid, false};       // the image stream of the double blocks
+    const TrainChain fin{st, Mi, t->Mi_pad, Ni, sc.g1, sc.g2, sc.g3, sc.wide, sc.hid, false};      // the final layer: target rows only
     auto GS = [&](int i, const char* leaf) { return ts->grads.find("single_transformer_blocks." + std::to_string(i) + leaf); };
     // ---- proj_out and norm_out (AdaLayerNormContinuous: scale first)
     HIPCHK(launch_convert(dv, DT_F32, t->dvb, DT_BF16, (long)Mi * C, st));
     CHK(t_dgrad(sc, st, t->dvb, C, C, ts->projT, Mi, D, sc.g3, D, nullptr, 0));
-    CHK(t_ln_back(im, mr, D, t->x_final, sc.g3, t->dx, e->mod_out + D, e->mod_out, 0));
-    // ---- joint stream gradient: the text rows of the last single block's output have no consumer
+    CHK(t_ln_back(fin, mr, D, t->x_final, sc.g3, t->dx, e->mod_out + D, e->mod_out, 0));
+    // ---- joint stream gradient: the text rows (and a condition plan's condition rows) of the last single block's output have no consumer
     HIPCHK(hipMemsetAsync(t->dyj, 0, (size_t)M * rowb, st));
     HIPCHK(hipMemcpy2DAsync(t->dyj + (size_t)Nt * D, (size_t)S * rowb, t->dx, (size_t)Ni * rowb, (size_t)Ni * rowb, p->B, hipMemcpyDeviceToDevice, st));
     const long ldw = 3L * D + F;
@@ -219,7 +233,7 @@ extern "C" int mi355_flux_backward(mi355_flux_plan* p, void* stream, const float
     }
     // ---- split the joint gradient: context rows first
     HIPCHK(hipMemcpy2DAsync(t->dc, (size_t)Nt * rowb, t->dyj, (size_t)S * rowb, (size_t)Nt * rowb, p->B, hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipMemcpy2DAsync(t->dx, (size_t)Ni * rowb, t->dyj + (size_t)Nt * D, (size_t)S * rowb, (size_t)Ni * rowb, p->B, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpy2DAsync(t->dx, (size_t)Nx * rowb, t->dyj + (size_t)Nt * D, (size_t)S * rowb, (size_t)Nx * rowb, p->B, hipMemcpyDeviceToDevice, st));
     // The text chain of the double blocks on the plan's side stream (key 28; the stream and events of the forward's text chain, key 14's size
     // rule; only with the weight-gradient stream, whose events order the shared operand slots).  Per-chain scratch: g?c, widec, hid_c, csum_c.
     const bool two = get_train_text_side() != 0 && flux_two_stream_wanted(p) && sc.wside != nullptr && e->L > 0;

@@ -192,6 +192,9 @@ struct RopeNormParams {
     float* rstd_out;                          // optional [M][2H] fp32: 1 / rms per (row, head) of q ([0, H)) and k ([H, 2H)) (training-mode forward; runtime branch)
 };
 hipError_t launch_rope_norm(const RopeNormParams& p, hipStream_t stream);
+// per-sample row concatenation (flux_ops.hip): out [B][Na + Nc][D] = [a [B][Na][D] | c [B][Nc][D]] (bf16, D a multiple of 8, 16-byte aligned):
+// the image stream of a FLUX.1 Kontext step = the freshly embedded target rows followed by the condition rows embedded once per rollout
+hipError_t launch_concat_rows(const bf16_t* a, int Na, const bf16_t* c, int Nc, bf16_t* out, int B, int D, hipStream_t stream);
 
 // Wan: RMSNorm ACROSS heads (over the whole row of H*128 features, weight [H*128]) + optional rotary embedding (cs == nullptr: none)
 // of ONE projection: src rows [M][src_ld] at column `col` -> out [B][H][S_pad][128] (row m = sample m / rows_per_sample, position

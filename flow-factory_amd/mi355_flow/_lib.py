@@ -133,11 +133,17 @@ SIGNATURES = {
     "mi355_flux_num_params": (_I, [_P]),
     "mi355_flux_param_name": (C.c_char_p, [_P, _I]),
     "mi355_flux_plan_create": (_I, [_P, _I, _I, _I, _I, _I, C.POINTER(_P)]),
+    "mi355_flux_plan_create_cond": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_P)]),
+    "mi355_flux_plan_rope_table": (_I, [_P, _P]),
     "mi355_flux_plan_destroy": (_I, [_P]),
     "mi355_flux_plan_workspace_bytes": (_L, [_P]),
     "mi355_flux_forward": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P]),
     "mi355_flux_rollout": (_I, [_P, _P, _I, C.POINTER(_F), C.POINTER(_F), C.POINTER(_F), _I, _F, _P, _I, _I, _P, _P, _P,
                                 C.POINTER(C.c_int32), _P, _P, _P, _I]),
+    "mi355_flux_forward_cond": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I]),
+    "mi355_flux_rollout_cond": (_I, [_P, _P, _I, C.POINTER(_F), C.POINTER(_F), C.POINTER(_F), _I, _F, _P, _I, _I, _P, _P, _P,
+                                     C.POINTER(C.c_int32), _P, _P, _P, _I, _P, _I]),
+    "mi355_flux_forward_train_cond": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I]),
     "mi355_flux_set_grad": (_I, [_P, C.c_char_p, _P]),
     "mi355_flux_set_grad_typed": (_I, [_P, C.c_char_p, _P, _I]),
     "mi355_flux_clear_grads": (_I, [_P]),

@@ -220,13 +220,14 @@ class PlanBase:
     marshalling of the fused `rollout`.  `_PRE` is what follows `mi355_` in the plan's C symbols -- and is the label `_lib.check` reports."""
 
     _PRE = ""
+    _CREATE = "plan_create"       # the C constructor: (engine, *shape, max_steps, &plan)
 
     def __init__(self, engine: EngineBase, shape: Tuple[int, ...], max_steps: int):
         self.engine, self.lib, self.max_steps = engine, engine.lib, max_steps
         self.C = engine.cfg.in_channels
         self._train_serial = 0        # the plan owns ONE activation stash: every training forward takes a number, the backward checks it
         h = C.c_void_p()
-        self._call("plan_create", engine._h, *shape, max_steps, C.byref(h))
+        self._call(self._CREATE, engine._h, *shape, max_steps, C.byref(h))
         self._h = h
 
     def _call(self, suffix: str, *args) -> None:
@@ -254,10 +255,11 @@ class PlanBase:
 
     def _rollout(self, shape: Tuple[int, ...], timesteps: Sequence[float], sigmas: Sequence[float], noise_levels: Sequence[float],
                  dynamics: str, guidance: float, init_latents: torch.Tensor, storage_dtype: torch.dtype,
-                 step_noise: Optional[torch.Tensor], cond: tuple, keep_positions: Optional[Sequence[int]], compute_log_prob: bool):
+                 step_noise: Optional[torch.Tensor], cond: tuple, keep_positions: Optional[Sequence[int]], compute_log_prob: bool,
+                 symbol: str = "rollout", tail: tuple = ()):
         """The whole N-step rollout in one C call.  `shape`: one latent state; `cond`: the family's conditioning arguments as the C
-        function takes them.  Returns (kept_latents [n_kept, *shape] storage dtype, log_probs [N, B] fp32 (nan where not computed),
-        final_latents [*shape])."""
+        function takes them; `symbol` / `tail`: a variant of the family's rollout and the arguments it takes after the common ones.
+        Returns (kept_latents [n_kept, *shape] storage dtype, log_probs [N, B] fp32 (nan where not computed), final_latents [*shape])."""
         N, B = len(timesteps), self.batch
         assert len(sigmas) == N + 1 and len(noise_levels) == N
         dev = init_latents.device
@@ -276,9 +278,9 @@ class PlanBase:
         if step_noise is not None:
             step_noise = step_noise.contiguous()
             assert step_noise.dtype == torch.float32 and tuple(step_noise.shape) == (N,) + shape, step_noise.shape
-        self._call("rollout", self._h, _stream(), N, ts_c, sg_c, nl_c, DYNAMICS[dynamics], float(guidance), _ptr(init_latents),
+        self._call(symbol, self._h, _stream(), N, ts_c, sg_c, nl_c, DYNAMICS[dynamics], float(guidance), _ptr(init_latents),
                    dtype_code(init_latents.dtype), dtype_code(storage_dtype), _ptr(step_noise), *cond, sl_c, _ptr(out_lat), _ptr(out_lp),
-                   _ptr(out_fin), int(bool(compute_log_prob)))
+                   _ptr(out_fin), int(bool(compute_log_prob)), *tail)
         return out_lat, out_lp, out_fin
 
 

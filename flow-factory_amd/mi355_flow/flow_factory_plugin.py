@@ -1,5 +1,5 @@
 """The binding a Flow-Factory installation uses:  `model.model_type: mi355_flow.flow_factory_plugin.SD3_5NativeAdapter`
-(also `...Flux1NativeAdapter`, `...Wan2T2VNativeAdapter`, `...QwenImageNativeAdapter`).
+(also `...Flux1NativeAdapter`, `...Flux1KontextNativeAdapter`, `...Wan2T2VNativeAdapter`, `...QwenImageNativeAdapter`).
 
 Flow-Factory resolves an unknown `model_type` as a python path (reference src/flow_factory/models/registry.py:69-82) and
 constructs `cls(config=config, accelerator=accelerator)` (models/loader.py:61-64).  Each class below IS the reference's own
@@ -271,6 +271,17 @@ if _RefAdapter is not None:
     if _RefFlux is not None:
         from .flux import FluxConfig, FluxEngine, FluxRolloutMixin, unpack_latents
 
+        def _init_flux_live(self):
+            """The FLUX engine of the loaded pipeline's transformer, bound live, and the native VAE decoder (FLUX.1 and FLUX.1 Kontext)."""
+            tc = self.pipeline.transformer.config
+            self._init_live(FluxEngine(FluxConfig(
+                in_channels=tc.in_channels, num_layers=tc.num_layers, num_single_layers=tc.num_single_layers,
+                num_attention_heads=tc.num_attention_heads, attention_head_dim=tc.attention_head_dim,
+                joint_attention_dim=tc.joint_attention_dim, pooled_projection_dim=tc.pooled_projection_dim,
+                guidance_embeds=bool(tc.guidance_embeds), axes_dims_rope=tuple(tc.axes_dims_rope))))
+            self.vae_max_batch = 4
+            self.vae_decoder = _native_vae(self.pipeline)
+
         class Flux1NativeAdapter(_LiveBinding, FluxRolloutMixin, _RefFlux):
             """`Flux1Adapter` (reference models/flux/flux1.py) with the GRPO rollout on the MI355X engine."""
 
@@ -280,14 +291,7 @@ if _RefAdapter is not None:
 
             def __init__(self, config, accelerator):
                 _RefFlux.__init__(self, config, accelerator)
-                tc = self.pipeline.transformer.config
-                self._init_live(FluxEngine(FluxConfig(
-                    in_channels=tc.in_channels, num_layers=tc.num_layers, num_single_layers=tc.num_single_layers,
-                    num_attention_heads=tc.num_attention_heads, attention_head_dim=tc.attention_head_dim,
-                    joint_attention_dim=tc.joint_attention_dim, pooled_projection_dim=tc.pooled_projection_dim,
-                    guidance_embeds=bool(tc.guidance_embeds), axes_dims_rope=tuple(tc.axes_dims_rope))))
-                self.vae_max_batch = 4
-                self.vae_decoder = _native_vae(self.pipeline)
+                _init_flux_live(self)
 
             @torch.no_grad()
             def decode_latents(self, latents, height, width, output_type="pil"):
@@ -308,6 +312,35 @@ if _RefAdapter is not None:
                     logger.warning("mi355_flow: grad-mode forward() differentiates through the reference path (%s); values stay the engine's", why)
                     self._warned_ref_grad = True
                 return self._replay_on_reference(_RefFlux.forward, FluxRolloutMixin._forward_nograd, (), kwargs)
+
+        try:
+            from flow_factory.models.flux.flux1_kontext import Flux1KontextAdapter as _RefKontext, Flux1KontextSample as _RefKontextSample
+        except Exception:  # noqa: BLE001
+            _RefKontext = None
+
+        if _RefKontext is not None:
+            from .flux import FluxKontextRolloutMixin
+
+            class Flux1KontextNativeAdapter(_LiveBinding, FluxKontextRolloutMixin, _RefKontext):
+                """`Flux1KontextAdapter` (reference models/flux/flux1_kontext.py) with the GRPO rollout on the MI355X engine: the FLUX.1 engine
+                on a condition plan.  `encode_image` (the VAE encoder) and the image standardisation are the reference's own."""
+
+                _sample_cls = _RefKontextSample
+                _output_cls = _RefOutput
+                _set_timesteps = staticmethod(_ref_set_timesteps)
+
+                def __init__(self, config, accelerator):
+                    _RefKontext.__init__(self, config, accelerator)
+                    _init_flux_live(self)
+
+                decode_latents = Flux1NativeAdapter.decode_latents
+
+                def _grad_fallback(self, why, kwargs):
+                    _require_reference_autograd("FLUX.1 Kontext", why)
+                    if not getattr(self, "_warned_ref_grad", False):
+                        logger.warning("mi355_flow: grad-mode forward() differentiates through the reference path (%s); values stay the engine's", why)
+                        self._warned_ref_grad = True
+                    return self._replay_on_reference(_RefKontext.forward, FluxKontextRolloutMixin._forward_nograd, (), kwargs)
 
     try:
         from flow_factory.models.wan.wan2_t2v import Wan2_T2V_Adapter as _RefWan, WanT2VSample as _RefWanSample
@@ -455,5 +488,6 @@ else:
 
     SD3_5NativeAdapter = _unavailable("SD3_5NativeAdapter", "mi355_flow.adapter.SD3_5NativeAdapter")
     Flux1NativeAdapter = _unavailable("Flux1NativeAdapter", "mi355_flow.flux.Flux1NativeAdapter")
+    Flux1KontextNativeAdapter = _unavailable("Flux1KontextNativeAdapter", "mi355_flow.flux.Flux1KontextNativeAdapter")
     Wan2T2VNativeAdapter = _unavailable("Wan2T2VNativeAdapter", "mi355_flow.wan.Wan2T2VNativeAdapter")
     QwenImageNativeAdapter = _unavailable("QwenImageNativeAdapter", "mi355_flow.qwen.QwenImageNativeAdapter")

@@ -1,5 +1,5 @@
 """Result containers of a rollout, API-compatible with the reference's `BaseSample` / `SD3_5Sample` / `Flux1Sample` /
-`WanT2VSample` (reference src/flow_factory/samples/samples.py:68-375, models/stable_diffusion/sd3_5.py:50-58,
+`Flux1KontextSample` / `WanT2VSample` (reference src/flow_factory/samples/samples.py:68-375, models/stable_diffusion/sd3_5.py:50-58,
 models/flux/flux1.py:53-59, models/wan/wan2_t2v.py:49-51) for everything the GRPO trainer touches:
 
   * field set + `extra_kwargs` overflow (`to_dict` flattens it, `sample['key']` / `sample.key` read through it);
@@ -220,6 +220,43 @@ class Flux1Sample(BaseSample):
     _shared_fields: ClassVar[frozenset] = frozenset({"img_ids"})
     pooled_prompt_embeds: Optional[torch.Tensor] = None
     img_ids: Optional[torch.Tensor] = None
+
+
+@dataclass
+class ImageConditionSample(BaseSample):
+    """reference samples.py:379-403 (`I2ISample` adds nothing to it): `condition_images` canonicalised to a list of `(C, H, W)` tensors and
+    part of the group identity.  The reference hashes 32-pixel PIL thumbnails of the images; this mirror hashes their 8-bit pixels, so its
+    `unique_id` separates the same groups but is not the reference's number (the plugin returns the reference's own class)."""
+    _id_fields: ClassVar[frozenset] = BaseSample._id_fields | frozenset({"condition_images"})
+    condition_images: Optional[Any] = None
+
+    def __post_init__(self):
+        super().__post_init__()
+        if self.condition_images is not None:
+            imgs = self.condition_images
+            if isinstance(imgs, (torch.Tensor, np.ndarray)) and imgs.ndim == 4:
+                imgs = list(imgs)
+            elif not isinstance(imgs, (list, tuple)):
+                imgs = [imgs]
+            object.__setattr__(self, "condition_images", [_image_to_chw(i) for i in imgs])
+
+    def _hash_id_fields(self, hasher) -> None:
+        super()._hash_id_fields(hasher)
+        for img in self.condition_images or ():
+            t = img.detach().float().cpu()
+            if img.dtype != torch.uint8:
+                t = t.clamp(0, 1) * 255.0
+            hasher.update(t.round().to(torch.uint8).numpy().tobytes())
+
+
+@dataclass
+class Flux1KontextSample(ImageConditionSample):
+    """reference flux1_kontext.py:83-91: `Flux1Sample`'s trajectory of the Ni target tokens, the packed condition latents `(Nc, 64)` of the
+    sample, and `latent_ids` `(Ni + Nc, 3)` = target ids followed by the condition ids, shared by the batch."""
+    _shared_fields: ClassVar[frozenset] = frozenset({"latent_ids"})
+    pooled_prompt_embeds: Optional[torch.Tensor] = None
+    image_latents: Optional[torch.Tensor] = None
+    latent_ids: Optional[torch.Tensor] = None
 
 
 @dataclass

@@ -286,17 +286,36 @@ const char* mi355_flux_param_name(mi355_flux* e, int i);
 /* latent_h x latent_w = the UNPACKED latent grid (e.g. 128 x 128 for 1024^2); n_text = T5 sequence length */
 int mi355_flux_plan_create(mi355_flux* e, int batch, int latent_h, int latent_w, int n_text, int max_steps,
                            mi355_flux_plan** out);
+/* FLUX.1 Kontext (reference models/flux/flux1_kontext.py:510-589): the image stream of a sample is cat([latents, image_latents], dim=1) -- Ni
+ * target tokens followed by Nc = (cond_h/2)*(cond_w/2) condition tokens with rotary ids (1, row, col) on the condition image's own grid -- and
+ * only the first Ni rows of the prediction reach the scheduler step.  cond_h x cond_w = the UNPACKED latent grid of the condition image (both
+ * even and >= 2), or 0 x 0 = mi355_flux_plan_create.  A condition plan is served by the *_cond entry points below and a plain plan by the plain
+ * ones; the other pairing returns an error before any launch.  Latents, velocity, step noise and d v keep their [B][Ni][C] shapes. */
+int mi355_flux_plan_create_cond(mi355_flux* e, int batch, int latent_h, int latent_w, int cond_h, int cond_w, int n_text, int max_steps,
+                                mi355_flux_plan** out);
+/* the plan's rotary table of the joint sequence [text | target | condition]: [n_text + Ni + Nc][64] (cos, sin) fp32 -> host (synchronises) */
+int mi355_flux_plan_rope_table(mi355_flux_plan* plan, float* out_host);
 int mi355_flux_plan_destroy(mi355_flux_plan* plan);
 int64_t mi355_flux_plan_workspace_bytes(mi355_flux_plan* plan);
 /* transformer only: t_model / guidance_model = the values the network embeds (device fp32 [B]); v_out bf16 packed */
 int mi355_flux_forward(mi355_flux_plan* plan, void* stream, const void* latents, int lat_dtype, const float* t_model,
                        const float* guidance_model, const void* prompt_embeds, const void* pooled, void* v_out);
+/* ... on a condition plan: image_latents [B][Nc][in_channels] packed, dtype image_dtype; a per-call argument, not plan state */
+int mi355_flux_forward_cond(mi355_flux_plan* plan, void* stream, const void* latents, int lat_dtype, const float* t_model,
+                            const float* guidance_model, const void* prompt_embeds, const void* pooled, void* v_out,
+                            const void* image_latents, int image_dtype);
 /* the whole N-step loop, zero host syncs; arguments as mi355_rollout (no negative prompt: guidance is embedded) */
 int mi355_flux_rollout(mi355_flux_plan* plan, void* stream, int n_steps, const float* timesteps_host, const float* sigmas_host,
                        const float* noise_levels_host, int dynamics, float guidance_scale, const void* init_latents,
                        int init_dtype, int storage_dtype, const float* step_noise, const void* prompt_embeds, const void* pooled,
                        const int32_t* keep_slot_host, void* out_latents, float* out_log_probs, void* out_final,
                        int compute_log_prob);
+/* ... on a condition plan: the condition is staged, converted and embedded once per call (it does not change with the step) */
+int mi355_flux_rollout_cond(mi355_flux_plan* plan, void* stream, int n_steps, const float* timesteps_host, const float* sigmas_host,
+                            const float* noise_levels_host, int dynamics, float guidance_scale, const void* init_latents,
+                            int init_dtype, int storage_dtype, const float* step_noise, const void* prompt_embeds, const void* pooled,
+                            const int32_t* keep_slot_host, void* out_latents, float* out_log_probs, void* out_final,
+                            int compute_log_prob, const void* image_latents, int image_dtype);
 /* ---- FLUX.1 `optimize()` replay with gradients (SURVEY.md 8(f) N1 over N3) --------------------------------------------------
  * Replaces the grad-mode `Flux1Adapter.forward(..., next_latents=x_{i+1})` + `accelerator.backward(loss)` of GRPOTrainer.optimize (reference
  * src/flow_factory/trainers/grpo.py:263, :326-330 over models/flux/flux1.py:294-346):
@@ -317,6 +336,10 @@ int mi355_flux_grad_supported(mi355_flux* e, const char* name);
 int64_t mi355_flux_plan_training_bytes(mi355_flux_plan* plan);
 int mi355_flux_forward_train(mi355_flux_plan* plan, void* stream, const void* latents, int lat_dtype, const float* t_model,
                              const float* guidance_model, const void* prompt_embeds, const void* pooled, void* v_out);
+/* ... on a condition plan (mi355_flux_backward serves both: d v is [B][Ni][C]; no gradient flows to image_latents) */
+int mi355_flux_forward_train_cond(mi355_flux_plan* plan, void* stream, const void* latents, int lat_dtype, const float* t_model,
+                                  const float* guidance_model, const void* prompt_embeds, const void* pooled, void* v_out,
+                                  const void* image_latents, int image_dtype);
 int mi355_flux_backward(mi355_flux_plan* plan, void* stream, const float* dv);
 /* unit-test helpers of the head_dim-128 backward kernels: attention forward (q pre-scaled by log2(e)/sqrt(128)) + flash backward, d_o / o
  * token-major [B*S][H*128], dq / dk / dv head-major (synchronises); q | k producer (per-head RMSNorm + RoPE) forward with its 1/rms output
