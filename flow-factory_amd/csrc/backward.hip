@@ -313,7 +313,8 @@ __device__ __forceinline__ float half8_sum_dpp(float v) {
 //   moves a tile's 128 floats into LDS with one LDS-DMA instruction per wave and feeds them to its MFMA chains as C operands)
 // one workgroup = 64 tokens of one (b, h); padded rows (S <= s < S_pad) are written as ZEROS (round 6: the scratch these three buffers live in is
 // shared by attentions of different lengths -- SD3.5's joint and dual attention -- so "zero-initialised" did not stay true for the padding, and
-// the software-pipelined backward passes carry no tail masks: attention_bwd.hip states the contract)
+// the software-pipelined backward passes carry no tail masks: attention_bwd.hip states the contract).  The launcher's grid has one workgroup
+// per 64-row tile of S_pad, so this holds for a padding of more than one tile too (tests/test_gpu_backward_ops.py)
 __global__ __launch_bounds__(256) void attn_bwd_prep_kernel(AttnBwdPrepParams p) {
     const int s0 = blockIdx.x * 64, h = blockIdx.y, b = blockIdx.z;
     const int D = p.H * 64, n_ctx = p.S - p.n_img;
@@ -956,8 +957,11 @@ hipError_t launch_attn_bwd_prep(const AttnBwdPrepParams& p, hipStream_t st) {
         sched_trace_launch("attn_bwd_prep", st, {treg(p.o_img, ri * D2), treg(p.o_ctx, p.o_ctx ? rc * D2 : 0), treg(p.do_img, ri * D2), treg(p.do_ctx, p.do_ctx ? rc * D2 : 0), treg(p.lse, bhs * 4)},
                            {treg(p.doh, bhs * 128), treg(p.delta, bhs * 4), treg(p.nld, bhs * 8)});
     }
-    if (g_rms_bwd_fast) hipLaunchKernelGGL(attn_bwd_prep_fast_kernel, dim3((p.S + 63) / 64, p.H, p.B), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL(attn_bwd_prep_kernel, dim3((p.S + 63) / 64, p.H, p.B), dim3(256), 0, st, p);
+    if (p.B <= 0 || p.H <= 0 || p.S <= 0 || p.S_pad < p.S || p.S_pad % 64 || p.n_img < 0 || p.n_img > p.S) return hipErrorInvalidValue;
+    // one workgroup per 64-row tile of S_pad, not of S: the kernels promise zeros in ALL of [S, S_pad), and a caller may pad by more than one
+    // tile (mi355_op_attention_fwd_bwd_ex takes any multiple of 64).  The engines' S_pad is S rounded up to 64: the same grid as before there.
+    if (g_rms_bwd_fast) hipLaunchKernelGGL(attn_bwd_prep_fast_kernel, dim3(p.S_pad / 64, p.H, p.B), dim3(256), 0, st, p);
+    else hipLaunchKernelGGL(attn_bwd_prep_kernel, dim3(p.S_pad / 64, p.H, p.B), dim3(256), 0, st, p);
     return hipGetLastError();
 }
 

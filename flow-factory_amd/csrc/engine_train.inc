@@ -688,6 +688,7 @@ extern "C" int mi355_denoise_step_backward(mi355_plan* p, void* stream, const vo
 extern "C" int mi355_op_attention_fwd_bwd(void* stream, const void* q, const void* k, const void* vT, const void* d_o, void* o, void* dq, void* dk,
                                           void* dv, int B, int H, int S, int S_pad) {
     if (!q || !k || !vT || !d_o || !o || !dq || !dk || !dv) return errorf("mi355_op_attention_fwd_bwd: null argument");
+    if (B <= 0 || H <= 0 || S <= 0 || S_pad < S || S_pad % 64) return errorf("mi355_op_attention_fwd_bwd: bad shape (S %d, S_pad %d)", S, S_pad);
     hipStream_t st = (hipStream_t)stream;
     const size_t el = (size_t)B * H * S_pad * 64;
     char* ws = nullptr;
@@ -746,5 +747,184 @@ extern "C" int mi355_op_attention_fwd_bwd_ex(void* stream, const void* q, const 
     if (err == hipSuccess) err = hipStreamSynchronize(st);
     (void)hipFree(ws);
     if (err != hipSuccess) return errorf("mi355_op_attention_fwd_bwd_ex: %s", hipGetErrorString(err));
+    return 0;
+}
+
+// ---- operator-level entry points of the backward's streaming / reduction kernels (backward.hip; tests/test_gpu_backward_ops.py) ----------
+// One per launcher family: arguments are checked before any HIP call, the launch goes to the caller's stream, nothing is allocated and
+// nothing synchronises.  Buffer extents are the caller's business (the launchers' header comments in kernels.h state them).
+// An output that may be a bf16 gradient buffer carries a dtype: it is marked for the launch and un-marked after it.
+static int op_out_dtype_ok(int dt) { return dt == DT_F32 || dt == DT_BF16; }
+
+extern "C" int mi355_op_ln_mod_bwd(void* stream, const void* x, const void* dy, const void* dy2, void* dres, const void* mod, int64_t mod_ld,
+                                   int shift_off, int scale_off, int shift2_off, int scale2_off, int M, int D, int rows_per_sample, float eps,
+                                   int accumulate, float* dmod) {
+    if (!x || !dy || !dres || !mod) return errorf("mi355_op_ln_mod_bwd: null argument");
+    if (M <= 0 || rows_per_sample <= 0) return errorf("mi355_op_ln_mod_bwd: bad shape (M %d, rows_per_sample %d)", M, rows_per_sample);
+    if (D <= 0 || D % 8) return errorf("mi355_op_ln_mod_bwd: D = %d is not a positive multiple of 8", D);
+    if (D > (dmod ? 4096 : 6144)) return errorf("mi355_op_ln_mod_bwd: D = %d is wider than %d (%s modulation gradients)", D, dmod ? 4096 : 6144, dmod ? "with" : "without");
+    if (scale_off < 0 || (dy2 && scale2_off < 0) || (dmod && (shift_off < 0 || (dy2 && shift2_off < 0))) || mod_ld < D)
+        return errorf("mi355_op_ln_mod_bwd: bad modulation layout (mod_ld %lld)", (long long)mod_ld);
+    LnModBwdParams p{(const bf16_t*)x, (const bf16_t*)dy, (const bf16_t*)dy2, (bf16_t*)dres, (const bf16_t*)mod, (long)mod_ld, scale_off, scale2_off,
+                     M, D, rows_per_sample, eps, accumulate, dmod, shift_off, shift2_off};
+    hipError_t err = launch_ln_mod_bwd(p, (hipStream_t)stream);
+    if (err != hipSuccess) return errorf("mi355_op_ln_mod_bwd: %s", hipGetErrorString(err));
+    return 0;
+}
+
+// y == NULL && dgate == NULL: dy = gate * dx only (launch_gate_mul); both given: dgate += sum dx * y as well (launch_gate_bwd)
+extern "C" int mi355_op_gate_bwd(void* stream, const void* dx, const void* gate, int64_t gate_ld, const void* y, void* dy, float* dgate, int64_t dg_ld,
+                                 int64_t M, int D, int rows_per_sample) {
+    if (!dx || !gate || !dy) return errorf("mi355_op_gate_bwd: null argument");
+    if ((y == nullptr) != (dgate == nullptr)) return errorf("mi355_op_gate_bwd: y and dgate go together (both NULL: the product only)");
+    if (M <= 0 || rows_per_sample <= 0) return errorf("mi355_op_gate_bwd: bad shape (M %lld, rows_per_sample %d)", (long long)M, rows_per_sample);
+    if (D <= 0 || D % 8) return errorf("mi355_op_gate_bwd: D = %d is not a positive multiple of 8", D);
+    if (gate_ld < D || (dgate && dg_ld < D)) return errorf("mi355_op_gate_bwd: a row stride is below D = %d", D);
+    hipError_t err = y ? launch_gate_bwd((const bf16_t*)dx, (const bf16_t*)gate, (long)gate_ld, (const bf16_t*)y, (bf16_t*)dy, dgate, (long)dg_ld, (long)M, D,
+                                         rows_per_sample, (hipStream_t)stream)
+                       : launch_gate_mul((const bf16_t*)dx, (const bf16_t*)gate, (long)gate_ld, (bf16_t*)dy, (long)M, D, rows_per_sample, (hipStream_t)stream);
+    if (err != hipSuccess) return errorf("mi355_op_gate_bwd: %s", hipGetErrorString(err));
+    return 0;
+}
+
+extern "C" int mi355_op_silu_bwd(void* stream, const void* dy, const void* pre, void* dx, int64_t n) {
+    if (!dy || !pre || !dx) return errorf("mi355_op_silu_bwd: null argument");
+    if (n <= 0 || n % 8) return errorf("mi355_op_silu_bwd: n = %lld is not a positive multiple of 8", (long long)n);
+    hipError_t err = launch_silu_bwd((const bf16_t*)dy, (const bf16_t*)pre, (bf16_t*)dx, (long)n, (hipStream_t)stream);
+    if (err != hipSuccess) return errorf("mi355_op_silu_bwd: %s", hipGetErrorString(err));
+    return 0;
+}
+
+extern "C" int mi355_op_gelu_fwd(void* stream, const void* pre, void* out, int64_t n) {
+    if (!pre || !out) return errorf("mi355_op_gelu_fwd: null argument");
+    if (n <= 0 || n % 8) return errorf("mi355_op_gelu_fwd: n = %lld is not a positive multiple of 8", (long long)n);
+    hipError_t err = launch_gelu_fwd((const bf16_t*)pre, (bf16_t*)out, (long)n, (hipStream_t)stream);
+    if (err != hipSuccess) return errorf("mi355_op_gelu_fwd: %s", hipGetErrorString(err));
+    return 0;
+}
+
+// scratch == NULL && colsum == NULL: launch_transpose (with batch strides); both given (batch 1): launch_transpose_colsum, `finish` = 0 leaves
+// the ((rows_pad + 63) / 64) x cols row-tile partials in `scratch` for mi355_op_splitk_reduce to finish
+extern "C" int mi355_op_transpose(void* stream, const void* in, int64_t ld_in, int64_t bs_in, void* out, int64_t ld_out, int64_t bs_out, int rows, int cols,
+                                  int rows_pad, int batch, float* scratch, void* colsum, int colsum_dtype, int finish) {
+    if (!in || !out) return errorf("mi355_op_transpose: null argument");
+    if (rows <= 0 || cols <= 0 || batch <= 0) return errorf("mi355_op_transpose: bad shape (rows %d, cols %d, batch %d)", rows, cols, batch);
+    if (rows_pad < rows) return errorf("mi355_op_transpose: rows_pad = %d is below rows = %d", rows_pad, rows);
+    if (ld_in < cols || ld_out < rows_pad) return errorf("mi355_op_transpose: a row stride is below its row (ld_in %lld, ld_out %lld)", (long long)ld_in, (long long)ld_out);
+    if ((scratch == nullptr) != (colsum == nullptr)) return errorf("mi355_op_transpose: scratch and colsum go together");
+    hipError_t err;
+    if (!scratch) {
+        err = launch_transpose((const bf16_t*)in, (long)ld_in, (long)bs_in, (bf16_t*)out, (long)ld_out, (long)bs_out, rows, cols, rows_pad, batch, (hipStream_t)stream);
+    } else {
+        if (batch != 1) return errorf("mi355_op_transpose: the column sums are taken of one matrix (batch %d)", batch);
+        if (!op_out_dtype_ok(colsum_dtype)) return errorf("mi355_op_transpose: column sums are fp32 or bf16 (dtype %d)", colsum_dtype);
+        grad_buf_mark(colsum, colsum_dtype);
+        err = launch_transpose_colsum((const bf16_t*)in, (long)ld_in, (bf16_t*)out, (long)ld_out, rows, cols, rows_pad, scratch, (float*)colsum,
+                                      (hipStream_t)stream, finish != 0);
+        grad_buf_mark(colsum, DT_F32);
+    }
+    if (err != hipSuccess) return errorf("mi355_op_transpose: %s", hipGetErrorString(err));
+    return 0;
+}
+
+// out[n] (+)= sum_m dy[m][n]; scratch: 64 * N floats
+extern "C" int mi355_op_colsum(void* stream, const void* dy, int64_t ld, int64_t M, int N, float* scratch, void* out, int out_dtype, int accumulate) {
+    if (!dy || !scratch || !out) return errorf("mi355_op_colsum: null argument");
+    if (M <= 0 || N <= 0 || ld < N) return errorf("mi355_op_colsum: bad shape (M %lld, N %d, ld %lld)", (long long)M, N, (long long)ld);
+    if (!op_out_dtype_ok(out_dtype)) return errorf("mi355_op_colsum: the output is fp32 or bf16 (dtype %d)", out_dtype);
+    grad_buf_mark(out, out_dtype);
+    hipError_t err = launch_colsum((const bf16_t*)dy, (long)ld, (long)M, N, scratch, (float*)out, accumulate, (hipStream_t)stream);
+    grad_buf_mark(out, DT_F32);
+    if (err != hipSuccess) return errorf("mi355_op_colsum: %s", hipGetErrorString(err));
+    return 0;
+}
+
+// out[i] (+)= sum_s part[s * stride + i].  cs_scratch / colsum given: the one-launch pair launch_splitk_reduce_colsum (out overwritten, colsum =
+// fixed-order sum of `nslab` x `cols` partials); a pair that does not qualify returns 2 with nothing launched -- its own value, not an error of the call.
+extern "C" int mi355_op_splitk_reduce(void* stream, const float* part, int64_t stride, int nsplit, void* out, int out_dtype, int64_t n, int accumulate,
+                                      const float* cs_scratch, int nslab, int cols, void* colsum, int colsum_dtype) {
+    if (!part || !out) return errorf("mi355_op_splitk_reduce: null argument");
+    if (nsplit <= 0) return errorf("mi355_op_splitk_reduce: nsplit = %d", nsplit);
+    if (n <= 0 || stride < n) return errorf("mi355_op_splitk_reduce: bad shape (n %lld, stride %lld)", (long long)n, (long long)stride);
+    if (!op_out_dtype_ok(out_dtype)) return errorf("mi355_op_splitk_reduce: the output is fp32 or bf16 (dtype %d)", out_dtype);
+    if ((cs_scratch == nullptr) != (colsum == nullptr)) return errorf("mi355_op_splitk_reduce: cs_scratch and colsum go together");
+    hipError_t err;
+    if (!colsum) {
+        grad_buf_mark(out, out_dtype);
+        err = launch_splitk_reduce(part, (long)stride, nsplit, (float*)out, (long)n, accumulate, (hipStream_t)stream);
+        grad_buf_mark(out, DT_F32);
+    } else {
+        if (nslab <= 0 || cols <= 0) return errorf("mi355_op_splitk_reduce: bad column-sum shape (nslab %d, cols %d)", nslab, cols);
+        if (!op_out_dtype_ok(colsum_dtype)) return errorf("mi355_op_splitk_reduce: column sums are fp32 or bf16 (dtype %d)", colsum_dtype);
+        if (accumulate) return errorf("mi355_op_splitk_reduce: the one-launch pair overwrites its outputs (accumulate must be 0)");
+        grad_buf_mark(out, out_dtype);
+        grad_buf_mark(colsum, colsum_dtype);
+        err = launch_splitk_reduce_colsum(part, (long)stride, nsplit, (float*)out, (long)n, cs_scratch, nslab, cols, (float*)colsum, (hipStream_t)stream);
+        grad_buf_mark(colsum, DT_F32);
+        grad_buf_mark(out, DT_F32);
+        if (err == hipErrorNotSupported) {
+            errorf("mi355_op_splitk_reduce: this pair takes two launches (n %% 4, stride %% 4, 16-byte alignment or mixed output dtypes)");
+            return 2;
+        }
+    }
+    if (err != hipSuccess) return errorf("mi355_op_splitk_reduce: %s", hipGetErrorString(err));
+    return 0;
+}
+
+extern "C" int mi355_op_f32_to_bf16_pad(void* stream, const float* in, void* out, int64_t rows, int64_t rows_pad, int64_t cols) {
+    if (!in || !out) return errorf("mi355_op_f32_to_bf16_pad: null argument");
+    if (rows <= 0 || cols <= 0) return errorf("mi355_op_f32_to_bf16_pad: bad shape (rows %lld, cols %lld)", (long long)rows, (long long)cols);
+    if (rows_pad < rows) return errorf("mi355_op_f32_to_bf16_pad: rows_pad = %lld is below rows = %lld", (long long)rows_pad, (long long)rows);
+    hipError_t err = launch_f32_to_bf16_pad(in, (bf16_t*)out, (long)rows, (long)rows_pad, (long)cols, (hipStream_t)stream);
+    if (err != hipSuccess) return errorf("mi355_op_f32_to_bf16_pad: %s", hipGetErrorString(err));
+    return 0;
+}
+
+extern "C" int mi355_op_unpatch_bwd(void* stream, const float* dv, void* out, int Bp, int C, int hp, int wp, int patch) {
+    if (!dv || !out) return errorf("mi355_op_unpatch_bwd: null argument");
+    if (Bp <= 0 || C <= 0 || hp <= 0 || wp <= 0 || patch <= 0)
+        return errorf("mi355_op_unpatch_bwd: bad shape (Bp %d, C %d, hp %d, wp %d, patch %d)", Bp, C, hp, wp, patch);
+    hipError_t err = launch_unpatch_bwd(dv, (bf16_t*)out, Bp, C, hp, wp, patch, (hipStream_t)stream);
+    if (err != hipSuccess) return errorf("mi355_op_unpatch_bwd: %s", hipGetErrorString(err));
+    return 0;
+}
+
+static const char* op_attn_split_error(int B, int H, int S, int S_pad, int n_img) {
+    if (B <= 0 || H <= 0 || S <= 0) return "B, H and S must be positive";
+    if (S_pad % 64) return "S_pad is not a multiple of 64";
+    if (S_pad < S) return "S_pad is below S";
+    if (n_img < 0 || n_img > S) return "n_img outside [0, S]";
+    return nullptr;
+}
+
+// the general or the 16-byte form by mi355_tune_set(25, .)
+extern "C" int mi355_op_attn_bwd_prep(void* stream, const void* o_img, const void* o_ctx, const void* do_img, const void* do_ctx, const float* lse, void* doh,
+                                      float* delta, float* nld, int B, int H, int S, int S_pad, int n_img) {
+    if (!lse || !doh || !delta || !nld) return errorf("mi355_op_attn_bwd_prep: null argument");
+    if (const char* why = op_attn_split_error(B, H, S, S_pad, n_img)) return errorf("mi355_op_attn_bwd_prep: %s (S %d, S_pad %d, n_img %d)", why, S, S_pad, n_img);
+    if (n_img > 0 && (!o_img || !do_img)) return errorf("mi355_op_attn_bwd_prep: o_img / do_img is NULL but n_img > 0");
+    if (n_img < S && !o_ctx) return errorf("mi355_op_attn_bwd_prep: o_ctx is NULL but S > n_img");
+    AttnBwdPrepParams pp{(const bf16_t*)o_img, (const bf16_t*)o_ctx, (const bf16_t*)do_img, (const bf16_t*)do_ctx, lse, (bf16_t*)doh, delta, nld, B, H, S, S_pad, n_img};
+    hipError_t err = launch_attn_bwd_prep(pp, (hipStream_t)stream);
+    if (err != hipSuccess) return errorf("mi355_op_attn_bwd_prep: %s", hipGetErrorString(err));
+    return 0;
+}
+
+// dw_part given ([rms_bwd_grid(B, S)][4][64] floats): the general kernel at 8 tokens per wave leaves its norm-weight partials there and
+// launch_rms_dw_finish sums them into whichever of dw_q / dw_k / dw_cq / dw_ck is not NULL; otherwise the general or the 16-byte form by key 25
+extern "C" int mi355_op_rms_bwd_gather(void* stream, const void* q, const void* k, const void* dq, const void* dk, const void* dv, const float* rstd_img,
+                                       const float* rstd_ctx, const float* nw_q, const float* nw_k, const float* nw_cq, const float* nw_ck, float q_scale,
+                                       void* out_img, void* out_ctx, int B, int H, int S, int S_pad, int n_img, float* dw_part, float* dw_q, float* dw_k,
+                                       float* dw_cq, float* dw_ck) {
+    if (!q || !k || !dq || !dk || !dv) return errorf("mi355_op_rms_bwd_gather: null argument");
+    if (const char* why = op_attn_split_error(B, H, S, S_pad, n_img)) return errorf("mi355_op_rms_bwd_gather: %s (S %d, S_pad %d, n_img %d)", why, S, S_pad, n_img);
+    if (n_img > 0 && (!rstd_img || !nw_q || !nw_k || !out_img)) return errorf("mi355_op_rms_bwd_gather: an image-stream tensor is NULL but n_img > 0");
+    if (n_img < S && (!rstd_ctx || !nw_cq || !nw_ck || !out_ctx)) return errorf("mi355_op_rms_bwd_gather: a context-stream tensor is NULL but S > n_img");
+    if (!dw_part && (dw_q || dw_k || dw_cq || dw_ck)) return errorf("mi355_op_rms_bwd_gather: norm-weight gradients need dw_part");
+    RmsBwdParams rb{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)dq, (const bf16_t*)dk, (const bf16_t*)dv, rstd_img, rstd_ctx, nw_q, nw_k, nw_cq, nw_ck,
+                    q_scale, (bf16_t*)out_img, (bf16_t*)out_ctx, B, H, S, S_pad, n_img, dw_part};
+    hipError_t err = launch_rms_bwd_gather(rb, (hipStream_t)stream);
+    if (err == hipSuccess && dw_part) err = launch_rms_dw_finish(dw_part, rms_bwd_grid(B, S), q_scale, dw_q, dw_k, dw_cq, dw_ck, (hipStream_t)stream);
+    if (err != hipSuccess) return errorf("mi355_op_rms_bwd_gather: %s", hipGetErrorString(err));
     return 0;
 }

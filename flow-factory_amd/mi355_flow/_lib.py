@@ -113,6 +113,17 @@ SIGNATURES = {
     "mi355_op_linear_gate_res": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I]),
     "mi355_op_wgrad": (_I, [_P, _P, C.c_int64, _P, C.c_int64, _P, _I, _I, _I, _I, _I, _P, _P]),
     "mi355_clock_probe": (_I, [_P, _P, _I, _I]),
+    "mi355_op_ln_mod_bwd": (_I, [_P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _F, _I, _P]),
+    "mi355_op_gate_bwd": (_I, [_P, _P, _P, _L, _P, _P, _P, _L, _L, _I, _I]),
+    "mi355_op_silu_bwd": (_I, [_P, _P, _P, _P, _L]),
+    "mi355_op_gelu_fwd": (_I, [_P, _P, _P, _L]),
+    "mi355_op_transpose": (_I, [_P, _P, _L, _L, _P, _L, _L, _I, _I, _I, _I, _P, _P, _I, _I]),
+    "mi355_op_colsum": (_I, [_P, _P, _L, _L, _I, _P, _P, _I, _I]),
+    "mi355_op_splitk_reduce": (_I, [_P, _P, _L, _I, _P, _I, _L, _I, _P, _I, _I, _P, _I]),
+    "mi355_op_f32_to_bf16_pad": (_I, [_P, _P, _P, _L, _L, _L]),
+    "mi355_op_unpatch_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _I]),
+    "mi355_op_attn_bwd_prep": (_I, [_P] * 9 + [_I] * 5),
+    "mi355_op_rms_bwd_gather": (_I, [_P] * 12 + [_F, _P, _P] + [_I] * 5 + [_P] * 5),
     "mi355_op_attention": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I]),
     "mi355_op_attention_ex": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P]),
     "mi355_op_ln_modulate": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _F]),

@@ -562,6 +562,89 @@ def op_wgrad(dy: torch.Tensor, x: torch.Tensor, k_split: int = 1, variant: int =
     return (out, colsum) if want_colsum else out
 
 
+# ---- operators of the backward's streaming / reduction kernels (csrc/backward.hip).  Thin on purpose: the caller owns every buffer (so a test
+# can fill it with a sentinel, leave a guard band behind it, or pass a view that starts off an alignment boundary) and every size; a tensor
+# goes in by its data pointer, strides are given in elements.  Nothing synchronises.
+def _dp(t: Optional[torch.Tensor]):
+    if t is None:
+        return None
+    if not t.is_cuda:
+        raise ValueError("mi355_flow: expected a tensor on the GPU (there is no CPU fallback)")
+    return C.c_void_p(t.data_ptr())
+
+
+def op_ln_mod_bwd(x, dy, dy2, dres, mod, mod_ld: int, shift_off: int, scale_off: int, shift2_off: int, scale2_off: int, M: int, D: int,
+                  rows_per_sample: int, eps: float, accumulate: bool, dmod=None) -> None:
+    lib = _lib.load()
+    _lib.check(lib.mi355_op_ln_mod_bwd(_stream(), _dp(x), _dp(dy), _dp(dy2), _dp(dres), _dp(mod), mod_ld, shift_off, scale_off, shift2_off,
+                                       scale2_off, M, D, rows_per_sample, eps, int(accumulate), _dp(dmod)), "op_ln_mod_bwd")
+
+
+def op_gate_bwd(dx, gate, gate_ld: int, y, dy, dgate, dg_ld: int, M: int, D: int, rows_per_sample: int) -> None:
+    """y is None and dgate is None: dy = gate * dx only."""
+    lib = _lib.load()
+    _lib.check(lib.mi355_op_gate_bwd(_stream(), _dp(dx), _dp(gate), gate_ld, _dp(y), _dp(dy), _dp(dgate), dg_ld, M, D, rows_per_sample), "op_gate_bwd")
+
+
+def op_silu_bwd(dy, pre, dx, n: int) -> None:
+    lib = _lib.load()
+    _lib.check(lib.mi355_op_silu_bwd(_stream(), _dp(dy), _dp(pre), _dp(dx), n), "op_silu_bwd")
+
+
+def op_gelu_fwd(pre, out, n: int) -> None:
+    lib = _lib.load()
+    _lib.check(lib.mi355_op_gelu_fwd(_stream(), _dp(pre), _dp(out), n), "op_gelu_fwd")
+
+
+def op_transpose(inp, ld_in: int, bs_in: int, out, ld_out: int, bs_out: int, rows: int, cols: int, rows_pad: int, batch: int = 1, scratch=None,
+                 colsum=None, finish: bool = True) -> None:
+    """scratch + colsum: the column sums as well (colsum fp32 or bf16 by its dtype); finish = False leaves the row-tile partials in scratch."""
+    lib = _lib.load()
+    _lib.check(lib.mi355_op_transpose(_stream(), _dp(inp), ld_in, bs_in, _dp(out), ld_out, bs_out, rows, cols, rows_pad, batch, _dp(scratch), _dp(colsum),
+                                      dtype_code(colsum.dtype) if colsum is not None else F32, int(finish)), "op_transpose")
+
+
+def op_colsum(dy, ld: int, M: int, N: int, scratch, out, accumulate: bool) -> None:
+    lib = _lib.load()
+    _lib.check(lib.mi355_op_colsum(_stream(), _dp(dy), ld, M, N, _dp(scratch), _dp(out), dtype_code(out.dtype), int(accumulate)), "op_colsum")
+
+
+def op_splitk_reduce(part, stride: int, nsplit: int, out, n: int, accumulate: bool = False, cs_scratch=None, nslab: int = 0, cols: int = 0,
+                     colsum=None) -> bool:
+    """cs_scratch + colsum: the one-launch pair; returns False (nothing written) when the pair does not qualify for it, True otherwise."""
+    lib = _lib.load()
+    rc = lib.mi355_op_splitk_reduce(_stream(), _dp(part), stride, nsplit, _dp(out), dtype_code(out.dtype), n, int(accumulate), _dp(cs_scratch), nslab, cols,
+                                    _dp(colsum), dtype_code(colsum.dtype) if colsum is not None else F32)
+    if rc == 2:
+        return False
+    _lib.check(rc, "op_splitk_reduce")
+    return True
+
+
+def op_f32_to_bf16_pad(inp, out, rows: int, rows_pad: int, cols: int) -> None:
+    lib = _lib.load()
+    _lib.check(lib.mi355_op_f32_to_bf16_pad(_stream(), _dp(inp), _dp(out), rows, rows_pad, cols), "op_f32_to_bf16_pad")
+
+
+def op_unpatch_bwd(dv, out, Bp: int, Cc: int, hp: int, wp: int, patch: int) -> None:
+    lib = _lib.load()
+    _lib.check(lib.mi355_op_unpatch_bwd(_stream(), _dp(dv), _dp(out), Bp, Cc, hp, wp, patch), "op_unpatch_bwd")
+
+
+def op_attn_bwd_prep(o_img, o_ctx, do_img, do_ctx, lse, doh, delta, nld, B: int, H: int, S: int, S_pad: int, n_img: int) -> None:
+    lib = _lib.load()
+    _lib.check(lib.mi355_op_attn_bwd_prep(_stream(), _dp(o_img), _dp(o_ctx), _dp(do_img), _dp(do_ctx), _dp(lse), _dp(doh), _dp(delta), _dp(nld), B, H, S,
+                                          S_pad, n_img), "op_attn_bwd_prep")
+
+
+def op_rms_bwd_gather(q, k, dq, dk, dv, rstd_img, rstd_ctx, nw_q, nw_k, nw_cq, nw_ck, q_scale: float, out_img, out_ctx, B: int, H: int, S: int,
+                      S_pad: int, n_img: int, dw_part=None, dw_q=None, dw_k=None, dw_cq=None, dw_ck=None) -> None:
+    lib = _lib.load()
+    _lib.check(lib.mi355_op_rms_bwd_gather(_stream(), _dp(q), _dp(k), _dp(dq), _dp(dk), _dp(dv), _dp(rstd_img), _dp(rstd_ctx), _dp(nw_q), _dp(nw_k),
+                                           _dp(nw_cq), _dp(nw_ck), q_scale, _dp(out_img), _dp(out_ctx), B, H, S, S_pad, n_img, _dp(dw_part), _dp(dw_q),
+                                           _dp(dw_k), _dp(dw_cq), _dp(dw_ck)), "op_rms_bwd_gather")
+
+
 def op_attention(q: torch.Tensor, k: torch.Tensor, vT: torch.Tensor, S: int, n_img: int):
     """q,k: [B,H,S_pad,64] bf16; vT: [B,H,64,S_pad] bf16 -> (o_img [B*n_img, H*64], o_ctx [B*(S-n_img), H*64])."""
     lib = _lib.load()

@@ -233,6 +233,52 @@ int mi355_op_attention_ex(void* stream, const void* q, const void* k, const void
 int mi355_op_ln_modulate(void* stream, const void* x, const void* shift, const void* scale, void* out, int M, int D,
                          int rows_per_sample, float eps);
 
+/* ---- operators of the backward's streaming / reduction kernels (csrc/backward.hip; tests/test_gpu_backward_ops.py) ----
+ * One per launcher family.  Arguments are checked before any HIP call (non-zero return, mi355_last_error() names the operator); the launch
+ * goes to `stream`; nothing is allocated, nothing synchronises.  bf16 tensors unless a type is given; an `*_dtype` is MI355_F32 or MI355_BF16
+ * (a bf16 gradient buffer: the fp32 sum is rounded once on the way out). */
+/* dres[M][D] (+)= rstd * (g - mean(g) - xhat * mean(g * xhat)), g = dy * (1 + scale[b]) [+ dy2 * (1 + scale2[b])], b = m / rows_per_sample,
+ * scale[b] = mod[b * mod_ld + scale_off ..]; dmod (optional, fp32, same layout as mod): dshift += sum dy, dscale += sum dy * xhat per sample
+ * (and the *2 offsets for dy2).  D % 8 == 0; D <= 4096 with dmod, <= 6144 without. */
+int mi355_op_ln_mod_bwd(void* stream, const void* x, const void* dy, const void* dy2, void* dres, const void* mod, int64_t mod_ld,
+                        int shift_off, int scale_off, int shift2_off, int scale2_off, int M, int D, int rows_per_sample, float eps,
+                        int accumulate, float* dmod);
+/* dy[m][:] = gate[m / rows_per_sample][:] * dx[m][:]; with y and dgate (both or neither): dgate[b][:] (fp32, row stride dg_ld) += sum over the
+ * sample's rows of dx * y */
+int mi355_op_gate_bwd(void* stream, const void* dx, const void* gate, int64_t gate_ld, const void* y, void* dy, float* dgate, int64_t dg_ld,
+                      int64_t M, int D, int rows_per_sample);
+/* dx = dy * silu'(pre);  out = gelu_tanh(pre);  n % 8 == 0 */
+int mi355_op_silu_bwd(void* stream, const void* dy, const void* pre, void* dx, int64_t n);
+int mi355_op_gelu_fwd(void* stream, const void* pre, void* out, int64_t n);
+/* out[z][c][r] = in[z][r][c] for r < rows, 0 for rows <= r < rows_pad (row strides ld_in / ld_out, batch strides bs_in / bs_out, in elements).
+ * scratch + colsum (both or neither; batch 1; scratch: ((rows_pad + 63) / 64) * cols floats): colsum[cols] = column sums of `in` as well;
+ * finish = 0 leaves the per-row-tile partials in scratch for mi355_op_splitk_reduce and does not touch colsum */
+int mi355_op_transpose(void* stream, const void* in, int64_t ld_in, int64_t bs_in, void* out, int64_t ld_out, int64_t bs_out, int rows, int cols,
+                       int rows_pad, int batch, float* scratch, void* colsum, int colsum_dtype, int finish);
+/* out[n] (+)= sum_m dy[m][n], dy [M][ld]; scratch: 64 * N floats */
+int mi355_op_colsum(void* stream, const void* dy, int64_t ld, int64_t M, int N, float* scratch, void* out, int out_dtype, int accumulate);
+/* out[i] (+)= part[0][i] + part[1][i] + ... (fp32 partials `stride` apart, summed in that order).  cs_scratch + colsum (both or neither): the
+ * same launch also finishes colsum[cols] from `nslab` row-tile partials (accumulate must be 0); a pair that does not qualify for one launch
+ * (n % 4, stride % 4, 16-byte alignment, mixed dtypes) returns 2 and writes nothing */
+int mi355_op_splitk_reduce(void* stream, const float* part, int64_t stride, int nsplit, void* out, int out_dtype, int64_t n, int accumulate,
+                           const float* cs_scratch, int nslab, int cols, void* colsum, int colsum_dtype);
+/* out[r][c] (bf16) = r < rows ? in[r][c] (fp32) : 0 for r < rows_pad */
+int mi355_op_f32_to_bf16_pad(void* stream, const float* in, void* out, int64_t rows, int64_t rows_pad, int64_t cols);
+/* dv [Bp][C][hp*patch][wp*patch] fp32 -> out [Bp*hp*wp][patch*patch*C] bf16, feature (pp * patch + qq) * C + c */
+int mi355_op_unpatch_bwd(void* stream, const float* dv, void* out, int Bp, int C, int hp, int wp, int patch);
+/* o / dO token-major (image rows s < n_img in *_img, the others in *_ctx; do_ctx may be NULL: zeros), lse [B][H][S_pad] fp32 ->
+ * doh [B][H][S_pad][64], delta [B][H][S_pad] = rowsum(dO * O), nld [B][H][S_pad/64][2][64] = -lse | -delta.  Every row of [S, S_pad) is
+ * written as zeros, for any S_pad that is a multiple of 64.  mi355_tune_set(25, .) selects the general or the 16-byte form. */
+int mi355_op_attn_bwd_prep(void* stream, const void* o_img, const void* o_ctx, const void* do_img, const void* do_ctx, const float* lse, void* doh,
+                           float* delta, float* nld, int B, int H, int S, int S_pad, int n_img);
+/* per-head RMSNorm backward of q, k + gather of dq | dk | dv [B][H][S_pad][64] into token-major rows [.][3*H*64] of the image and the context
+ * stream; rstd_* [rows][2H], nw_* [64] fp32.  dw_part (optional, ((B*S + 31) / 32) * 256 floats): the norm-weight gradients as well, written
+ * to whichever of dw_q / dw_k / dw_cq / dw_ck [64] is not NULL (the q ones carry q_scale) */
+int mi355_op_rms_bwd_gather(void* stream, const void* q, const void* k, const void* dq, const void* dk, const void* dv, const float* rstd_img,
+                            const float* rstd_ctx, const float* nw_q, const float* nw_k, const float* nw_cq, const float* nw_ck, float q_scale,
+                            void* out_img, void* out_ctx, int B, int H, int S, int S_pad, int n_img, float* dw_part, float* dw_q, float* dw_k,
+                            float* dw_cq, float* dw_ck);
+
 /* ---- VAE decode ----------------------------------------------
  * Replaces `pipeline.vae.decode(latents / scaling_factor + shift_factor)` + `image_processor.postprocess(.., 'pt')`
  * of SD3_5Adapter.decode_latents (reference src/flow_factory/models/stable_diffusion/sd3_5.py:161-172); the decoder is
