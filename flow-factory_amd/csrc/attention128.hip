@@ -220,7 +220,15 @@ __global__ __launch_bounds__(NWAVE * 64, 2) void attn128_kernel(Attn128Params p)
         if (qi < p.S) {
             bf16_t* dst = (qi < p.n_first) ? p.o_first + ((long)b * p.n_first + qi) * p.ld_first
                                            : p.o_rest + ((long)b * (p.S - p.n_first) + (qi - p.n_first)) * p.ld_rest;
-            *(uint4*)(dst + h * HD + c * 8) = val;
+            uint4 v = val;
+            if (p.o_add) {      // optional addend (a RUNTIME branch, like lse): store bf16(bf16(o) + o_add); o_add may be the output buffer itself
+                const uint4 ad = *(const uint4*)(p.o_add + ((long)b * p.S + qi) * p.ld_first + h * HD + c * 8);      // (n_first == S: launch_attention128)
+                v.x = pack_bf16(bf_lo(v.x) + bf_lo(ad.x), bf_hi(v.x) + bf_hi(ad.x));
+                v.y = pack_bf16(bf_lo(v.y) + bf_lo(ad.y), bf_hi(v.y) + bf_hi(ad.y));
+                v.z = pack_bf16(bf_lo(v.z) + bf_lo(ad.z), bf_hi(v.z) + bf_hi(ad.z));
+                v.w = pack_bf16(bf_lo(v.w) + bf_lo(ad.w), bf_hi(v.w) + bf_hi(ad.w));
+            }
+            *(uint4*)(dst + h * HD + c * 8) = v;
         }
     }
 }
@@ -414,12 +422,15 @@ hipError_t launch_attention128(const Attn128Params& p, hipStream_t stream) {
     if (sched_trace_on()) {
         const size_t q = (size_t)p.B * p.H * p.S_pad * 256, kv = (size_t)p.B * p.H * (p.S_kv > 0 ? p.S_kv_pad : p.S_pad) * 256;
         const size_t r1 = (size_t)p.B * p.n_first, r2 = (size_t)p.B * (p.S - p.n_first);
-        sched_trace_launch("attention128", stream, {treg(p.q, q), treg(p.k, kv), treg(p.vT, kv), treg(p.kv_len, p.kv_len ? (size_t)p.B * 4 : 0)},
+        sched_trace_launch("attention128", stream, {treg(p.q, q), treg(p.k, kv), treg(p.vT, kv), treg(p.kv_len, p.kv_len ? (size_t)p.B * 4 : 0),
+                                                    treg(p.o_add, p.o_add && r1 ? ((r1 - 1) * p.ld_first + (size_t)p.H * 128) * 2 : 0)},
                            {treg(p.o_first, r1 ? ((r1 - 1) * p.ld_first + (size_t)p.H * 128) * 2 : 0),
                             treg(p.o_rest, r2 ? ((r2 - 1) * p.ld_rest + (size_t)p.H * 128) * 2 : 0)});
     }
     if (p.S <= 0 || p.S_pad < p.S || p.n_first < 0 || p.n_first > p.S) return hipErrorInvalidValue;
     if (p.S_kv > 0 ? (p.S_kv_pad % KV != 0 || p.S_kv_pad < p.S_kv) : (p.S_pad % KV != 0)) return hipErrorInvalidValue;
+    // the addend is read by the attn128_kernel epilogue only (cross-attention never takes the hand-scheduled kernel), with the output's own strides
+    if (p.o_add && (p.S_kv <= 0 || p.n_first != p.S || p.qmax2)) return hipErrorInvalidValue;
     if (g_attn128_variant == 1) return launch128<4, false>(p, stream);
     bool stat = p.score_bound > 0.f && p.score_bound <= 60.f;
     if (!stat && p.qmax2 && p.kmax2 && p.S_kv == 0 && g_attn128_variant == 0) {

@@ -76,7 +76,8 @@ __global__ __launch_bounds__(256) void ln_mod_kernel(LnModParams p) {
 }
 
 // ------------------------------------------------------------------ patchify (im2col, k = c*p*p + py*p + px)
-__global__ void patchify_kernel(const void* lat, int dt, bf16_t* out, int B, int rep, int C, int h, int w, int p) {
+// A token's C*p*p features go to columns col0 .. col0 + C*p*p of its row of `ld` elements (ld == C*p*p, col0 == 0: the dense layout).
+__global__ void patchify_kernel(const void* lat, int dt, bf16_t* out, int B, int rep, int C, int h, int w, int p, int col0, int ld) {
     const int hp = h / p, wp = w / p, K = C * p * p;
     const long total = (long)B * rep * hp * wp * K;
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
@@ -88,7 +89,7 @@ __global__ void patchify_kernel(const void* lat, int dt, bf16_t* out, int B, int
         const int b = bb % B;  // cat([latents, latents]): replica r uses sample bb - r*B
         const int c = k / (p * p), py = (k / p) % p, px = k % p;
         const long src = (((long)b * C + c) * h + ty * p + py) * w + tx * p + px;
-        out[i] = f2bf(load_as_f32(lat, src, dt));
+        out[tok * ld + col0 + k] = f2bf(load_as_f32(lat, src, dt));
     }
 }
 
@@ -125,6 +126,27 @@ __global__ void convert_kernel(const void* src, int sdt, void* dst, int ddt, lon
     }
 }
 
+// [rows][cols] of any dtype -> bf16 rows of `ld` elements, columns cols .. ld zero (a weight whose K is padded to the GEMM's multiple)
+__global__ void convert_rows_kernel(const void* src, int sdt, bf16_t* dst, long rows, int cols, int ld) {
+    const long total = rows * ld;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int c = (int)(i % ld);
+        const long r = i / ld;
+        dst[i] = c < cols ? f2bf(load_as_f32(src, r * cols + c, sdt)) : f2bf(0.f);
+    }
+}
+
+__global__ void gelu_erf_kernel(bf16_t* x, long n) {
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const float v = bf2f(x[i]);
+        x[i] = f2bf(0.5f * v * (1.0f + erff(v * 0.70710678118654752f)));
+    }
+}
+
+__global__ void add_bf16_kernel(const bf16_t* a, const bf16_t* b, bf16_t* out, long n) {
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) out[i] = f2bf(bf2f(a[i]) + bf2f(b[i]));
+}
+
 inline int grid_for(long total, int block) {
     long g = (total + block - 1) / block;
     return (int)(g > 8192 ? 8192 : (g < 1 ? 1 : g));
@@ -153,7 +175,22 @@ hipError_t launch_patchify(const void* lat, int dt, bf16_t* patches, int B, int 
         sched_trace_launch("patchify", stream, {treg(lat, (size_t)B * C * h * w * (dt == DT_F32 ? 4 : 2))}, {treg(patches, (size_t)B * rep * C * h * w * 2)});
     const long total = (long)B * rep * (h / p) * (w / p) * C * p * p;
     hipLaunchKernelGGL(patchify_kernel, dim3(grid_for(total, 256)), dim3(256), 0, stream, lat, dt, patches, B, rep, C, h,
-                       w, p);
+                       w, p, 0, C * p * p);
+    return hipGetLastError();
+}
+
+hipError_t launch_patchify_cols(const void* lat, int dt, bf16_t* patches, int B, int rep, int C, int h, int w, int p, int col0, int ld,
+                                hipStream_t stream) {
+    const int K = C * p * p;
+    if (C < 1 || col0 < 0 || col0 + K > ld || h % p || w % p) return hipErrorInvalidValue;
+    const long rows = (long)B * rep * (h / p) * (w / p);
+    // The trace region is ONE span, first to last element touched: it also covers the columns of the rows in between that this launch does not
+    // write.  Conservative: the latent-column and the condition-column launch of one patch buffer claim overlapping bytes although they write
+    // disjoint ones -- harmless while both run on one stream (they do), a false race in the checker if they ever move to different streams.
+    if (sched_trace_on())
+        sched_trace_launch("patchify_cols", stream, {treg(lat, (size_t)B * C * h * w * (dt == DT_F32 ? 4 : 2))},
+                           {treg(patches + col0, (size_t)((rows - 1) * ld + K) * 2)});
+    hipLaunchKernelGGL(patchify_kernel, dim3(grid_for(rows * K, 256)), dim3(256), 0, stream, lat, dt, patches, B, rep, C, h, w, p, col0, ld);
     return hipGetLastError();
 }
 
@@ -195,6 +232,28 @@ hipError_t launch_convert(const void* src, int src_dt, void* dst, int dst_dt, lo
         sched_trace_launch("convert", stream, {treg(src, (size_t)n * (src_dt == DT_F32 ? 4 : 2))}, {treg(dst, (size_t)n * (dst_dt == DT_F32 ? 4 : 2))});
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(convert_kernel, dim3(grid_for(n, 256)), dim3(256), 0, stream, src, src_dt, dst, dst_dt, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_gelu_erf(bf16_t* x, long n, hipStream_t stream) {
+    if (sched_trace_on()) sched_trace_launch("gelu_erf", stream, {treg(x, (size_t)n * 2)}, {treg(x, (size_t)n * 2)});
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(gelu_erf_kernel, dim3(grid_for(n, 256)), dim3(256), 0, stream, x, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_add_bf16(const bf16_t* a, const bf16_t* b, bf16_t* out, long n, hipStream_t stream) {
+    if (sched_trace_on()) sched_trace_launch("add_bf16", stream, {treg(a, (size_t)n * 2), treg(b, (size_t)n * 2)}, {treg(out, (size_t)n * 2)});
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(add_bf16_kernel, dim3(grid_for(n, 256)), dim3(256), 0, stream, a, b, out, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_convert_rows(const void* src, int src_dt, bf16_t* dst, long rows, int cols, int ld, hipStream_t stream) {
+    if (rows < 1 || cols < 1 || ld < cols) return hipErrorInvalidValue;
+    if (sched_trace_on())
+        sched_trace_launch("convert_rows", stream, {treg(src, (size_t)rows * cols * (src_dt == DT_F32 ? 4 : 2))}, {treg(dst, (size_t)rows * ld * 2)});
+    hipLaunchKernelGGL(convert_rows_kernel, dim3(grid_for(rows * ld, 256)), dim3(256), 0, stream, src, src_dt, dst, rows, cols, ld);
     return hipGetLastError();
 }
 

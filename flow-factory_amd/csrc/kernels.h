@@ -164,6 +164,8 @@ struct Attn128Params {
     int mode;           // set by launch_attention128: 0 = always run, 1 = run only where the measured bound <= 60, 2 = only where it is larger
     float* lse;         // optional [B][H][S_pad] fp32: log2-sum-exp of the scaled scores per query (training-mode forward).  A RUNTIME branch in the
                         // kernels' epilogues, not a second instantiation: rollout and training run the same binary, so their outputs agree bit for bit
+    const bf16_t* o_add; // optional addend, token-major with the output's strides (cross-attention, n_first == S): the epilogue stores bf16(bf16(o) + o_add).
+                        // A runtime branch as well; may alias the output (Wan image cross-attention added onto the text cross-attention's output)
 };
 hipError_t launch_attention128(const Attn128Params& p, hipStream_t stream);
 void set_attn128_variant(int v);   // 0 (default): 4-wave hand-scheduled kernel where it applies, else 8-wave workgroups; 1: 4-wave compiler-scheduled; 5: never hand-scheduled
@@ -251,12 +253,21 @@ hipError_t launch_ln_mod(const LnModParams& p, hipStream_t stream);
 // `rep` > 1 replicates the batch (CFG: latents_input = cat([latents, latents])).
 hipError_t launch_patchify(const void* lat, int dt, bf16_t* patches, int B, int rep, int C, int h, int w, int p,
                            hipStream_t stream);
+// the same into columns col0 .. col0 + C*p*p of rows of `ld` elements (a channel range of a wider patch row); the other columns are not written
+hipError_t launch_patchify_cols(const void* lat, int dt, bf16_t* patches, int B, int rep, int C, int h, int w, int p, int col0, int ld,
+                                hipStream_t stream);
 // pos_embed buffer [max*max][D] bf16 -> centre crop [hp*wp][D]
 hipError_t launch_pos_crop(const bf16_t* pos, bf16_t* out, int max_size, int hp, int wp, int D, hipStream_t stream);
 // sinusoidal timestep projection (cos first): out[r][dim] bf16, t rounded to `t_round_dt` first
 hipError_t launch_time_proj(const float* t, int rows, int dim, int t_round_dt, bf16_t* out, hipStream_t stream);
 // generic dtype conversion (weights binding); n elements
 hipError_t launch_convert(const void* src, int src_dt, void* dst, int dst_dt, long n, hipStream_t stream);
+// [rows][cols] (any dtype) -> bf16 [rows][ld], columns cols .. ld zero
+hipError_t launch_convert_rows(const void* src, int src_dt, bf16_t* dst, long rows, int cols, int ld, hipStream_t stream);
+// x = gelu(x), exact (erf) form, in place on bf16 (the image embedder of Wan2.1-I2V: B * 257 rows once per rollout)
+hipError_t launch_gelu_erf(bf16_t* x, long n, hipStream_t stream);
+// out = bf16(a + b): fp32 sum of two bf16 tensors, one rounding; out may alias a or b
+hipError_t launch_add_bf16(const bf16_t* a, const bf16_t* b, bf16_t* out, long n, hipStream_t stream);
 hipError_t launch_clock_probe(long long* out, int n, int sleep_iters, hipStream_t stream);   // measurement tool: {core clock, wall clock} samples
 
 // ------------------------------------------------------------------------------ VAE decode (vae.hip)

@@ -10,7 +10,20 @@
 // modulated LayerNorm -> q|k GEMM -> RMSNorm across heads + 3-D RoPE -> V^T GEMM -> head_dim-128 attention -> gated out-projection;
 // affine LayerNorm -> q GEMM -> RMSNorm -> cross-attention on the cached text K / V^T -> out-projection (+residual);
 // modulated LayerNorm -> gelu-tanh feed-forward, gated.  CFG runs as one forward over the batch [negative, positive].
+//
+// Image-to-video (mi355_wan_create_i2v, the *_i2v entry points; Wan2_I2V_Adapter.forward, reference models/wan/wan2_i2v.py:656-783, whose
+// transformer input is cat([latents (16), condition (4 mask + 16 latent)], dim = 1)): patch_embedding is Conv3d(36, D) -> the patch row holds
+// (16 + 20) * 4 = 144 features, padded to KP = 192 (GEMM K dims are multiples of 64): latents in columns 0..63, the condition in 64..143 (the
+// oracle's order c*4 + ph*2 + pw over the 36 channels), 144..191 zero in both the patch buffer (zero-filled at allocation, never written) and
+// the weight slot (zeroed at bind time).  The condition does not change with the step: its columns are written once per call, the per-step
+// patchify writes the latent columns only.  Everything downstream of the patch embedding -- scheduler-side latents, v, the SDE step, the
+// backward (the patch embedder is frozen) -- stays on the 16 latent channels.  That alone is Wan2.2-I2V-A14B (two experts, no image embeddings).
+// Wan2.1-I2V adds the image cross-attention branch (image_dim > 0, plan with n_image > 0; model body restated from the published
+// WanTransformer3DModel, parity unpinned): condition_embedder.image_embedder on the CLIP hidden states and every block's image K / V^T once
+// per call (prepare_image); per block the text cross-attention's queries attend to the image keys as well, and attn2.to_out.0 reads
+// bf16(bf16(o_text) + bf16(o_img)) -- the attention epilogue's optional addend in the rollout, separate outputs plus one add in training mode.
 #include <math.h>
+#include <algorithm>
 #include <stdio.h>
 #include <string.h>
 
@@ -32,6 +45,8 @@ struct WTrainBlk {
     bf16_t *x_in, *xn1, *o1, *x_mid1, *xn2, *o2, *x_mid2, *xn3, *pre;     // [M][D] each; pre [M][F]
     bf16_t *q, *k, *vT, *q2;                                              // [Bp][H][S_pad][128] (vT: [Bp][H][128][S_pad])
     float *lse1, *lse2, *rstd_q, *rstd_k, *rstd_q2;                       // [Bp][H][S_pad] x 2, [M] x 3
+    bf16_t *o3, *o23;                                                     // image branch: the image cross-attention's own output, and bf16(o2 + o3)
+    float* lse3;                                                          // (what attn2.to_out.0 reads); its log-sum-exp.  Null without the branch
 };
 
 struct WanBlockW {
@@ -40,6 +55,8 @@ struct WanBlockW {
     float *nq, *nk, *nq2, *nk2, *ln2_w, *ln2_b;
     float* table;          // scale_shift_table [6][D] fp32
     bf16_t* ln2_mod;       // (bias, weight - 1) rows for ln_mod, built at weights_ready time
+    bf16_t* w_kv3;         // image branch (Wan2.1-I2V): attn2.add_k_proj | attn2.add_v_proj, norm_added_k
+    float *b_kv3, *nk3;
 };
 
 }  // namespace
@@ -47,6 +64,11 @@ struct WanBlockW {
 struct mi355_wan : ParamTable {
     mi355_wan_cfg cfg;
     int D, F, L, H, KP, NO;
+    int Di = 0;                  // image_dim: width of the CLIP image embeddings; 0 = no image cross-attention branch
+    bf16_t *w_i1 = nullptr, *w_i2 = nullptr, *iln1_mod = nullptr, *iln2_mod = nullptr;     // image_embedder: ff.net.0.proj, ff.net.2, LayerNorm rows for ln_mod
+    float *b_i1 = nullptr, *b_i2 = nullptr, *iln1_w = nullptr, *iln1_b = nullptr, *iln2_w = nullptr, *iln2_b = nullptr;
+    std::vector<float> bound_img;
+    int Cc = 0, KPr = 0;         // image-to-video: condition channels appended to the latents at the patch embedding; KPr = real K, KP = padded to 64
     bf16_t *w_patch, *w_t1, *w_t2, *w_tp, *w_x1, *w_x2, *w_proj;
     float *b_patch, *b_t1, *b_t2, *b_tp, *b_x1, *b_x2, *b_proj, *table_out;
     std::vector<WanBlockW> blk;
@@ -64,13 +86,21 @@ void mi355_wan::layout() {
     const int T = cfg.freq_dim, J = cfg.text_dim;
     const int64_t DD = (int64_t)D * D;
     w_patch = a16((int64_t)D * KP); b_patch = a32(D);
-    reg("patch_embedding.weight", w_patch, DT_BF16, (int64_t)D * KP);
+    reg("patch_embedding.weight", w_patch, DT_BF16, (int64_t)D * KPr);      // (bound row by row into [D][KP] when KP > KPr)
     reg("patch_embedding.bias", b_patch, DT_F32, D);
     w_t1 = a16((int64_t)D * T); b_t1 = a32(D); lin("condition_embedder.time_embedder.linear_1", w_t1, b_t1, D, T);
     w_t2 = a16(DD); b_t2 = a32(D); lin("condition_embedder.time_embedder.linear_2", w_t2, b_t2, D, D);
     w_tp = a16(6 * DD); b_tp = a32(6 * D); lin("condition_embedder.time_proj", w_tp, b_tp, 6 * D, D);
     w_x1 = a16((int64_t)D * J); b_x1 = a32(D); lin("condition_embedder.text_embedder.linear_1", w_x1, b_x1, D, J);
     w_x2 = a16(DD); b_x2 = a32(D); lin("condition_embedder.text_embedder.linear_2", w_x2, b_x2, D, D);
+    if (Di) {          // WanImageEmbedding: norm1 -> ff (exact GELU) -> norm2; an engine without the branch lists none of these names
+        const std::string ie = "condition_embedder.image_embedder.";
+        iln1_w = a32(Di); iln1_b = a32(Di); reg(ie + "norm1.weight", iln1_w, DT_F32, Di); reg(ie + "norm1.bias", iln1_b, DT_F32, Di);
+        w_i1 = a16((int64_t)Di * Di); b_i1 = a32(Di); lin(ie + "ff.net.0.proj", w_i1, b_i1, Di, Di);
+        w_i2 = a16((int64_t)D * Di); b_i2 = a32(D); lin(ie + "ff.net.2", w_i2, b_i2, D, Di);
+        iln2_w = a32(D); iln2_b = a32(D); reg(ie + "norm2.weight", iln2_w, DT_F32, D); reg(ie + "norm2.bias", iln2_b, DT_F32, D);
+        iln1_mod = a16(2 * Di); iln2_mod = a16(2 * D);
+    }
     for (int i = 0; i < L; ++i) {
         WanBlockW& b = blk[i];
         const std::string pre = "blocks." + std::to_string(i);
@@ -90,6 +120,11 @@ void mi355_wan::layout() {
         b.ln2_w = a32(D); b.ln2_b = a32(D);
         reg(pre + ".norm2.weight", b.ln2_w, DT_F32, D); reg(pre + ".norm2.bias", b.ln2_b, DT_F32, D);
         b.ln2_mod = a16(2 * D);
+        if (Di) {
+            b.w_kv3 = a16(2 * DD); b.b_kv3 = a32(2 * D); b.nk3 = a32(D);
+            lin(pre + ".attn2.add_k_proj", b.w_kv3, b.b_kv3, D, D); lin(pre + ".attn2.add_v_proj", b.w_kv3 + DD, b.b_kv3 + D, D, D);
+            reg(pre + ".attn2.norm_added_k.weight", b.nk3, DT_F32, D);
+        }
         b.w_ff1 = a16((int64_t)F * D); b.b_ff1 = a32(F); lin(pre + ".ffn.net.0.proj", b.w_ff1, b.b_ff1, F, D);
         b.w_ff2 = a16((int64_t)D * F); b.b_ff2 = a32(D); lin(pre + ".ffn.net.2", b.w_ff2, b.b_ff2, D, F);
     }
@@ -97,24 +132,36 @@ void mi355_wan::layout() {
     w_proj = a16((int64_t)NO * D); b_proj = a32(NO); lin("proj_out", w_proj, b_proj, NO, D);
 }
 
-extern "C" int mi355_wan_create(const mi355_wan_cfg* cfg, mi355_wan** out) {
-    if (!cfg || !out) return errorf("mi355_wan_create: null argument");
-    if (cfg->head_dim != 128) return errorf("mi355_wan_create: head_dim must be 128 (got %d)", cfg->head_dim);
-    if (cfg->num_heads < 1 || cfg->num_heads > 48) return errorf("mi355_wan_create: num_heads must be 1..48");
-    if (cfg->num_layers < 1 || cfg->num_layers > 256) return errorf("mi355_wan_create: num_layers out of range");
-    if (cfg->patch_t != 1 || cfg->patch_h != 2 || cfg->patch_w != 2) return errorf("mi355_wan_create: patch_size must be (1, 2, 2)");
-    const int KP = cfg->in_channels * 4;
+static int wan_create(const char* who, const mi355_wan_cfg* cfg, int cond_channels, int image_dim, mi355_wan** out) {
+    if (!cfg || !out) return errorf("%s: null argument", who);
+    if (cfg->head_dim != 128) return errorf("%s: head_dim must be 128 (got %d)", who, cfg->head_dim);
+    if (cfg->num_heads < 1 || cfg->num_heads > 48) return errorf("%s: num_heads must be 1..48", who);
+    if (cfg->num_layers < 1 || cfg->num_layers > 256) return errorf("%s: num_layers out of range", who);
+    if (cfg->patch_t != 1 || cfg->patch_h != 2 || cfg->patch_w != 2) return errorf("%s: patch_size must be (1, 2, 2)", who);
+    const int KPr = (cfg->in_channels + cond_channels) * 4;
+    const int KP = cond_channels ? (KPr + 63) / 64 * 64 : KPr;        // the condition channels may leave K ragged: zero-padded columns
     if (KP % 64 || cfg->text_dim % 64 || cfg->freq_dim % 64 || cfg->ffn_dim % 64)
-        return errorf("mi355_wan_create: every GEMM K dim must be a multiple of 64");
+        return errorf("%s: every GEMM K dim must be a multiple of 64", who);
     mi355_wan* e = new mi355_wan();
     e->cfg = *cfg;
-    e->H = cfg->num_heads; e->D = cfg->num_heads * 128; e->F = cfg->ffn_dim; e->L = cfg->num_layers; e->KP = KP;
+    e->H = cfg->num_heads; e->D = cfg->num_heads * 128; e->F = cfg->ffn_dim; e->L = cfg->num_layers; e->KP = KP; e->KPr = KPr; e->Cc = cond_channels; e->Di = image_dim;
     e->NO = cfg->out_channels * 4;
     e->layout();
-    if (e->alloc("mi355_wan_create") != 0) { delete e; return 1; }
+    if (e->alloc(who) != 0) { delete e; return 1; }
     e->layout();
     *out = e;
     return 0;
+}
+
+extern "C" int mi355_wan_create(const mi355_wan_cfg* cfg, mi355_wan** out) { return wan_create("mi355_wan_create", cfg, 0, 0, out); }
+
+// image-to-video: cfg->in_channels stays the LATENT channel count (the scheduler's state), cond_channels (4 mask + 16 latent = 20) are the
+// channels the adapter concatenates behind it; image_dim = width of the CLIP image embeddings (Wan2.1-I2V), 0 = no image branch (Wan2.2-I2V-A14B)
+extern "C" int mi355_wan_create_i2v(const mi355_wan_cfg* cfg, int cond_channels, int image_dim, mi355_wan** out) {
+    if (cond_channels < 1 || cond_channels > 256) return errorf("mi355_wan_create_i2v: cond_channels must be 1..256 (got %d)", cond_channels);
+    if (image_dim < 0 || image_dim % 64 || image_dim > 6144)
+        return errorf("mi355_wan_create_i2v: image_dim %d must be 0 (no image branch) or a multiple of 64 up to 6144", image_dim);
+    return wan_create("mi355_wan_create_i2v", cfg, cond_channels, image_dim, out);
 }
 
 extern "C" int mi355_wan_destroy(mi355_wan* e) {
@@ -129,7 +176,24 @@ extern "C" const char* mi355_wan_param_name(mi355_wan* e, int i) { return e ? e-
 extern "C" int mi355_wan_bind_weight(mi355_wan* e, const char* name, const void* src, int dtype, int ndim, const int64_t* shape,
                                      void* stream) {
     if (!e || !name || !src) return errorf("mi355_wan_bind_weight: null argument");
-    CHK(e->bind("mi355_wan_bind_weight", name, src, dtype, ndim, shape, (hipStream_t)stream));
+    if (strstr(name, "image_embedder.pos_embed"))
+        return errorf("mi355_wan_bind_weight: '%s': the learned position embedding of the image embedder (first-and-last-frame checkpoints) is not "
+                      "implemented", name);
+    if (e->KP != e->KPr && !strcmp(name, "patch_embedding.weight")) {
+        // (D, C + Cc, 1, 2, 2) -> rows of KP elements, columns KPr .. KP zero
+        auto it = e->slots.find(name);
+        if (it == e->slots.end()) return errorf("mi355_wan_bind_weight: unknown parameter '%s'", name);
+        int64_t n = 1;
+        for (int i = 0; i < ndim; ++i) n *= shape[i];
+        if (n != it->second.numel || ndim < 2 || shape[0] != e->D)
+            return errorf("mi355_wan_bind_weight: '%s' has %lld elements in %d dimensions, expected (%d, %d, 1, 2, 2)", name, (long long)n, ndim, e->D,
+                          e->KPr / 4);
+        if (dtype < 0 || dtype > 2) return errorf("mi355_wan_bind_weight: bad dtype %d", dtype);
+        HIPCHK(launch_convert_rows(src, dtype, e->w_patch, e->D, e->KPr, e->KP, (hipStream_t)stream));
+        it->second.bound = true;
+    } else {
+        CHK(e->bind("mi355_wan_bind_weight", name, src, dtype, ndim, shape, (hipStream_t)stream));
+    }
     e->derived_dirty = true;
     engine_train_mark_dirty(e->train); // the transposed copies the backward's dgrad GEMMs read are stale
     return 0;
@@ -154,11 +218,32 @@ struct mi355_wan_plan {
     float* max2_part;          // scratch of the kernel that measures them
     std::vector<float> host_t, host_sc;
     int mod_cols;
+    int Ni = 0, Ni_pad = 0;             // image branch: CLIP image tokens per sample (0 = none), padded to 64
+    bf16_t *ie_n = nullptr, *ie_h = nullptr, *ie_o = nullptr, *ictx = nullptr, *kvbuf3 = nullptr, *ki = nullptr, *vTi = nullptr;
     PlanTrain* train = nullptr;         // training workspace (wan_train.inc: mi355_wan_train), created by the first training-mode forward
 };
 
+static int wan_plan_create(mi355_wan* e, int batch, int n_cfg, int latent_t, int latent_h, int latent_w, int n_text, int n_image, int max_steps,
+                           mi355_wan_plan** out);
+
 extern "C" int mi355_wan_plan_create(mi355_wan* e, int batch, int n_cfg, int latent_t, int latent_h, int latent_w, int n_text,
                                      int max_steps, mi355_wan_plan** out) {
+    if (e && e->Cc) return errorf("mi355_wan_plan_create: image-to-video engine (mi355_wan_create_i2v): use mi355_wan_plan_create_i2v");
+    return wan_plan_create(e, batch, n_cfg, latent_t, latent_h, latent_w, n_text, 0, max_steps, out);
+}
+
+// n_image: CLIP image tokens per sample of the image cross-attention branch (257); 0 = none (the only value on an engine with image_dim == 0)
+extern "C" int mi355_wan_plan_create_i2v(mi355_wan* e, int batch, int n_cfg, int latent_t, int latent_h, int latent_w, int n_text, int n_image,
+                                         int max_steps, mi355_wan_plan** out) {
+    if (e && !e->Cc) return errorf("mi355_wan_plan_create_i2v: text-to-video engine (mi355_wan_create): use mi355_wan_plan_create");
+    if (n_image < 0 || n_image > 65536) return errorf("mi355_wan_plan_create_i2v: bad n_image %d", n_image);
+    if (e && n_image != 0 && !e->Di)
+        return errorf("mi355_wan_plan_create_i2v: n_image %d: the engine has no image cross-attention branch (image_dim == 0)", n_image);
+    return wan_plan_create(e, batch, n_cfg, latent_t, latent_h, latent_w, n_text, n_image, max_steps, out);
+}
+
+static int wan_plan_create(mi355_wan* e, int batch, int n_cfg, int latent_t, int latent_h, int latent_w, int n_text, int n_image, int max_steps,
+                           mi355_wan_plan** out) {
     if (!e || !out) return errorf("mi355_wan_plan_create: null argument");
     if (batch < 1 || (n_cfg != 1 && n_cfg != 2) || latent_t < 1 || latent_h < 2 || latent_w < 2 || ((latent_h | latent_w) & 1) ||
         n_text < 1 || max_steps < 1)
@@ -168,6 +253,7 @@ extern "C" int mi355_wan_plan_create(mi355_wan* e, int batch, int n_cfg, int lat
     p->hp = latent_h / 2; p->wp = latent_w / 2; p->S = latent_t * p->hp * p->wp; p->S_pad = (p->S + 63) / 64 * 64;
     p->Nt = n_text; p->Nt_pad = (n_text + 63) / 64 * 64; p->M = p->Bp * p->S; p->Mc = p->Bp * n_text; p->max_steps = max_steps;
     p->n_lat = (int64_t)e->cfg.in_channels * latent_t * latent_h * latent_w;
+    p->Ni = n_image; p->Ni_pad = (n_image + 63) / 64 * 64;
     if ((int64_t)p->Bp * p->S > 0x7fffffffLL / 2) { delete p; return errorf("mi355_wan_plan_create: too many tokens"); }
     const int D = e->D, F = e->F;
     p->mod_cols = e->L * 6 * D + 2 * D;
@@ -187,8 +273,13 @@ extern "C" int mi355_wan_plan_create(mi355_wan* e, int batch, int n_cfg, int lat
     c.take(p->io_init, nl * 4); c.take(p->io_traj, (int64_t)(max_steps + 1) * nl * 4); c.take(p->io_noise, (int64_t)max_steps * nl);
     c.take(p->io_lp, (int64_t)max_steps * batch);
     c.take(p->io_pe, (int64_t)batch * n_text * e->cfg.text_dim); c.take(p->io_ne, (int64_t)batch * n_text * e->cfg.text_dim);
+    if (p->Ni) {       // image embedder activations for the B samples; every block's image K / V^T for the whole forward batch (both CFG halves)
+        const int64_t ri = (int64_t)batch * p->Ni, ki_el = (int64_t)p->Bp * e->H * p->Ni_pad * 128;
+        c.take(p->ie_n, ri * e->Di); c.take(p->ie_h, ri * e->Di); c.take(p->ie_o, ri * D); c.take(p->ictx, ri * D); c.take(p->kvbuf3, ri * D);
+        c.take(p->ki, ki_el * e->L); c.take(p->vTi, ki_el * e->L);
+    }
     c.take(p->max2, (int64_t)2 * p->Bp * e->H); c.take(p->max2_part, (int64_t)p->Bp * norm_rope_parts(p->S) * e->H);
-    // zeroed: the padded key rows / columns of q, k, vT, kx, vTx must stay finite
+    // zeroed: the padded key rows / columns of q, k, vT, kx, vTx must stay finite; image-to-video: the padding columns KPr .. KP of `patches` stay zero
     if (c.alloc(&p->ws, &p->ws_bytes, true, "mi355_wan_plan_create") != 0) { delete p; return 1; }
     // rotary table (WanRotaryPosEmbed): head_dim 128 -> t / h / w axes of 44 / 42 / 42 features, float64 angles, adjacent pairs
     {
@@ -240,6 +331,10 @@ int g_wan_data_bound = 1;
 int refresh_derived(mi355_wan* e, hipStream_t st) {
     if (!e->derived_dirty) return 0;
     for (auto& b : e->blk) HIPCHK(launch_affine_to_mod(b.ln2_w, b.ln2_b, b.ln2_mod, e->D, st));
+    if (e->Di) {
+        HIPCHK(launch_affine_to_mod(e->iln1_w, e->iln1_b, e->iln1_mod, e->Di, st));
+        HIPCHK(launch_affine_to_mod(e->iln2_w, e->iln2_b, e->iln2_mod, e->D, st));
+    }
     std::vector<float> host(e->used32 / 4);
     HIPCHK(hipMemcpyAsync(host.data(), e->arena32, e->used32, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
@@ -249,11 +344,12 @@ int refresh_derived(mi355_wan* e, hipStream_t st) {
         for (int i = 0; i < e->D; ++i) m = fmaxf(m, fabsf(hh[i]));
         return m;
     };
-    e->bound_self.assign(e->L, 0.f); e->bound_cross.assign(e->L, 0.f);
+    e->bound_self.assign(e->L, 0.f); e->bound_cross.assign(e->L, 0.f); e->bound_img.assign(e->L, 0.f);
     const float c = (float)e->D * kScale * 1.02f;
     for (int i = 0; i < e->L; ++i) {
         e->bound_self[i] = c * amax(e->blk[i].nq) * amax(e->blk[i].nk);
         e->bound_cross[i] = c * amax(e->blk[i].nq2) * amax(e->blk[i].nk2);
+        if (e->Di) e->bound_img[i] = c * amax(e->blk[i].nq2) * amax(e->blk[i].nk3);      // the same normalised query against the image keys
     }
     e->derived_dirty = false;
     ++e->derived_ver;
@@ -322,6 +418,40 @@ int prepare_prompt(mi355_wan_plan* p, hipStream_t st, const void* enc_a, const v
     return 0;
 }
 
+// step-invariant image work (Wan2.1-I2V; next to prepare_prompt): the image embedder on the CLIP penultimate hidden states [B][Ni][Di] -- norm1
+// (LayerNorm with affine, eps 1e-5) -> ff.net.0.proj -> exact (erf) GELU -> ff.net.2 -> norm2 -- then every block's image keys
+// RMSNorm_across_heads(add_k_proj(img); norm_added_k) (no RoPE) and values add_v_proj(img)^T, in the text keys' layout [Bp][H][Ni_pad][128].
+// The image embeddings are the same in both CFG halves: computed for the B samples, the second half is a copy.
+int prepare_image(mi355_wan_plan* p, hipStream_t st, const void* image_embeds) {
+    mi355_wan* e = p->e;
+    const int D = e->D, Di = e->Di, R = p->B * p->Ni;
+    LnModParams l;
+    memset(&l, 0, sizeof(l));
+    l.x = (const bf16_t*)image_embeds; l.out = p->ie_n; l.mod = e->iln1_mod; l.mod_ld = 0; l.shift_off = 0; l.scale_off = Di;
+    l.M = R; l.D = Di; l.rows_per_sample = R; l.eps = 1e-5f;
+    HIPCHK(launch_ln_mod(l, st));
+    GemmParams g1 = make_gemm(p->ie_n, Di, e->w_i1, Di, R, Di, Di, EPI_BIAS, e->b_i1, p->ie_h, Di);
+    HIPCHK(launch_gemm(g1, st));
+    HIPCHK(launch_gelu_erf(p->ie_h, (long)R * Di, st));
+    GemmParams g2 = make_gemm(p->ie_h, Di, e->w_i2, Di, R, D, Di, EPI_BIAS, e->b_i2, p->ie_o, D);
+    HIPCHK(launch_gemm(g2, st));
+    l.x = p->ie_o; l.out = p->ictx; l.mod = e->iln2_mod; l.scale_off = D; l.D = D;
+    HIPCHK(launch_ln_mod(l, st));
+    const int64_t ki_el = (int64_t)p->Bp * e->H * p->Ni_pad * 128, half = (int64_t)p->B * e->H * p->Ni_pad * 128;
+    for (int i = 0; i < e->L; ++i) {
+        const WanBlockW& b = e->blk[i];
+        GemmParams gk = make_gemm(p->ictx, D, b.w_kv3, D, R, D, D, EPI_BIAS, b.b_kv3, p->kvbuf3, D);     // add_k_proj
+        HIPCHK(launch_gemm(gk, st));
+        CHK(norm_rope(p, st, p->kvbuf3, D, 0, b.nk3, false, p->ki + i * ki_el, R, p->Ni, p->Ni_pad, 1.0f));
+        CHK(vt_proj(p, st, b.w_kv3 + (int64_t)D * D, b.b_kv3 + D, p->ictx, R, p->Ni, p->vTi + i * ki_el, p->Ni_pad));
+        if (p->ncfg == 2) {
+            HIPCHK(copy_d2d(p->ki + i * ki_el + half, p->ki + i * ki_el, (size_t)half * 2, st));
+            HIPCHK(copy_d2d(p->vTi + i * ki_el + half, p->vTi + i * ki_el, (size_t)half * 2, st));
+        }
+    }
+    return 0;
+}
+
 // conditioning of `nsteps` steps: temb, time_proj(silu(temb)), modulation tables = scale_shift_table + time_proj
 int prepare_conditioning(mi355_wan_plan* p, hipStream_t st, int nsteps) {
     mi355_wan* e = p->e;
@@ -347,13 +477,19 @@ int prepare_conditioning(mi355_wan_plan* p, hipStream_t st, int nsteps) {
 // per-block buffers (+ the residual stream copied aside at the three sub-layer boundaries, the log-sum-exp / 1/rms side outputs switched on,
 // the FFN pre-activation stashed by the GEMM epilogue); `kx` / `vTx` = the cross-attention keys / values to read (the training state's copy).
 int forward_core(mi355_wan_plan* p, hipStream_t st, const void* latents, int lat_dt, const bf16_t* mod, bf16_t* v_out, const WTrainBlk* tb = nullptr,
-                 bf16_t* x_final = nullptr, const bf16_t* kx = nullptr, const bf16_t* vTx = nullptr) {
+                 bf16_t* x_final = nullptr, const bf16_t* kx = nullptr, const bf16_t* vTx = nullptr, const bf16_t* ki = nullptr,
+                 const bf16_t* vTi = nullptr) {
     mi355_wan* e = p->e;
     const int D = e->D, F = e->F, M = p->M, S = p->S;
     const int64_t kx_el = (int64_t)p->Bp * e->H * p->Nt_pad * 128;
     const size_t x_b = (size_t)M * D * 2;
     if (!kx) { kx = p->kx; vTx = p->vTx; }
-    HIPCHK(launch_patchify(latents, lat_dt, p->patches, p->B, p->ncfg, e->cfg.in_channels, p->T * p->h, p->w, 2, st));
+    if (!ki) { ki = p->ki; vTi = p->vTi; }
+    const int64_t ki_el = (int64_t)p->Bp * e->H * p->Ni_pad * 128;
+    if (e->Cc)       // image-to-video: the latent columns of the wider row; the condition columns were written once for this call (write_i2v_inputs)
+        HIPCHK(launch_patchify_cols(latents, lat_dt, p->patches, p->B, p->ncfg, e->cfg.in_channels, p->T * p->h, p->w, 2, 0, e->KP, st));
+    else
+        HIPCHK(launch_patchify(latents, lat_dt, p->patches, p->B, p->ncfg, e->cfg.in_channels, p->T * p->h, p->w, 2, st));
     GemmParams g0 = make_gemm(p->patches, e->KP, e->w_patch, e->KP, M, D, e->KP, EPI_BIAS, e->b_patch, p->x, D);
     HIPCHK(launch_gemm(g0, st));
     for (int i = 0; i < e->L; ++i) {
@@ -404,6 +540,19 @@ int forward_core(mi355_wan_plan* p, hipStream_t st, const void* latents, int lat
             a.lse = k ? k->lse2 : nullptr;
             HIPCHK(launch_attention128(a, st));
         }
+        if (p->Ni) {
+            // image cross-attention: the SAME normalised queries over the cached image keys, its output added to the text cross-attention's
+            // before attn2.to_out.0: bf16(bf16(o_img) + o_text).  Rollout: the attention epilogue adds onto o2 in place.  Training mode keeps both
+            // outputs and both log-sum-exps (delta = rowsum(dO . O) is per softmax) and forms the same sum with one add kernel: bit-identical.
+            Attn128Params a;
+            memset(&a, 0, sizeof(a));
+            a.q = q2; a.k = ki + i * ki_el; a.vT = vTi + i * ki_el; a.o_first = k ? k->o3 : o2; a.ld_first = D; a.n_first = S;
+            a.o_rest = a.o_first; a.ld_rest = D; a.B = p->Bp; a.H = e->H; a.S = S; a.S_pad = p->S_pad; a.q_prescaled = 1;
+            a.S_kv = p->Ni; a.S_kv_pad = p->Ni_pad; a.score_bound = e->bound_img[i];
+            a.lse = k ? k->lse3 : nullptr; a.o_add = k ? nullptr : o2;
+            HIPCHK(launch_attention128(a, st));
+            if (k) { HIPCHK(launch_add_bf16(k->o3, k->o2, k->o23, (long)M * D, st)); o2 = k->o23; }
+        }
         GemmParams go2 = make_gemm(o2, D, b.w_o2, D, M, D, D, EPI_POSADD, b.b_o2, p->x, D);
         go2.aux = p->x; go2.ld_aux = D; go2.rows_per_sample = M;
         HIPCHK(launch_gemm(go2, st));
@@ -425,23 +574,61 @@ int forward_core(mi355_wan_plan* p, hipStream_t st, const void* latents, int lat
     return 0;
 }
 
+// which entry points serve which plan, and the image-to-video arguments: checks only, nothing is launched
+int check_kind(mi355_wan_plan* p, const char* who, bool i2v, const void* condition, int cond_dt, const void* image_embeds) {
+    mi355_wan* e = p->e;
+    if (!i2v) {
+        if (e->Cc) return errorf("%s: image-to-video plan: use %s_i2v (the transformer input has %d condition channels)", who, who, e->Cc);
+        return 0;
+    }
+    if (!e->Cc) return errorf("%s_i2v: text-to-video plan: use %s", who, who);
+    if (image_embeds && !e->Di) return errorf("%s_i2v: image_embeds given, but the engine has no image cross-attention branch (image_dim == 0)", who);
+    if (image_embeds && !p->Ni) return errorf("%s_i2v: image_embeds given, but the plan was created with n_image == 0", who);
+    if (!image_embeds && p->Ni) return errorf("%s_i2v: the plan was created with n_image == %d: image_embeds is NULL", who, p->Ni);
+    if (!condition) return errorf("%s_i2v: condition is NULL", who);
+    if (cond_dt < 0 || cond_dt > 2) return errorf("%s_i2v: bad condition dtype %d", who, cond_dt);
+    return 0;
+}
+
+// the step-invariant image-to-video inputs, once per call: condition [B][Cc][T][h][w] (both CFG halves read it) -> columns C*4 .. (C + Cc)*4 of
+// every patch row; image_embeds -> the image context and every block's image K / V^T
+int write_i2v_inputs(mi355_wan_plan* p, hipStream_t st, const void* condition, int cond_dt, const void* image_embeds) {
+    mi355_wan* e = p->e;
+    if (!e->Cc) return 0;
+    HIPCHK(launch_patchify_cols(condition, cond_dt, p->patches, p->B, p->ncfg, e->Cc, p->T * p->h, p->w, 2, e->cfg.in_channels * 4, e->KP, st));
+    if (p->Ni) CHK(prepare_image(p, st, image_embeds));
+    return 0;
+}
+
 }  // namespace
 
 namespace mi355 { void set_wan_data_bound(int v) { g_wan_data_bound = v != 0; } }
 
 // transformer only (tests / replay): t[Bp] device fp32 = the timestep values the network embeds; enc_b == NULL when n_cfg == 1.
 // With n_cfg == 2 the forward batch is [enc_a (negative), enc_b (positive)] on replicated latents, v_out holds both halves.
-extern "C" int mi355_wan_forward(mi355_wan_plan* p, void* stream, const void* latents, int lat_dtype, const float* t, const void* enc_a,
-                                 const void* enc_b, void* v_out) {
+static int wan_forward(mi355_wan_plan* p, void* stream, const void* latents, int lat_dtype, const float* t, const void* enc_a, const void* enc_b,
+                       void* v_out, bool i2v, const void* condition, int cond_dtype, const void* image_embeds) {
     if (!p || !latents || !t || !enc_a || !v_out) return errorf("mi355_wan_forward: null argument");
     if (lat_dtype < 0 || lat_dtype > 2) return errorf("mi355_wan_forward: bad latent dtype %d", lat_dtype);
-    CHK(mi355_wan_weights_ready(p->e));
     hipStream_t st = (hipStream_t)stream;
+    CHK(check_kind(p, "mi355_wan_forward", i2v, condition, cond_dtype, image_embeds));
+    CHK(mi355_wan_weights_ready(p->e));
     CHK(refresh_derived(p->e, st));
+    CHK(write_i2v_inputs(p, st, condition, cond_dtype, image_embeds));
     HIPCHK(hipMemcpyAsync(p->t_dev, t, (size_t)p->Bp * 4, hipMemcpyDeviceToDevice, st));
     CHK(prepare_prompt(p, st, enc_a, enc_b));
     CHK(prepare_conditioning(p, st, 1));
     return forward_core(p, st, latents, lat_dtype, p->mod_all, (bf16_t*)v_out);
+}
+
+extern "C" int mi355_wan_forward(mi355_wan_plan* p, void* stream, const void* latents, int lat_dtype, const float* t, const void* enc_a,
+                                 const void* enc_b, void* v_out) {
+    return wan_forward(p, stream, latents, lat_dtype, t, enc_a, enc_b, v_out, false, nullptr, 0, nullptr);
+}
+// image-to-video: + condition [batch][cond_channels][T][h][w] (cond_dtype: MI355_F32 / BF16 / F16), image_embeds [batch][n_image][image_dim] bf16 or NULL
+extern "C" int mi355_wan_forward_i2v(mi355_wan_plan* p, void* stream, const void* latents, int lat_dtype, const float* t, const void* enc_a,
+                                     const void* enc_b, const void* condition, int cond_dtype, const void* image_embeds, void* v_out) {
+    return wan_forward(p, stream, latents, lat_dtype, t, enc_a, enc_b, v_out, true, condition, cond_dtype, image_embeds);
 }
 
 // The loop runs as eager launches: replaying it as ONE hipGraph (the SD3.5 / FLUX.1 / Qwen-Image engines do) was measured in round 3 at the
@@ -450,21 +637,23 @@ extern "C" int mi355_wan_forward(mi355_wan_plan* p, void* stream, const void* la
 // ~10 launches each).  Removed rather than kept as a dead option.
 // the whole N-step loop; timesteps_host: the scheduler's (integer-valued) timesteps; sigma of a step = t / 1000
 // (scheduler/unipc_multistep.py:288-291); neg_embeds == NULL <=> the plan has n_cfg == 1.
-extern "C" int mi355_wan_rollout(mi355_wan_plan* p, void* stream, int n_steps, const float* timesteps_host, const float* sigmas_host,
-                                 const float* noise_levels_host, int dynamics, float guidance, const void* init_latents, int init_dtype,
-                                 int storage_dtype, const float* step_noise, const void* prompt_embeds, const void* neg_embeds,
-                                 const int32_t* keep_slot_host, void* out_latents, float* out_log_probs, void* out_final,
-                                 int compute_log_prob) {
+static int wan_rollout(mi355_wan_plan* p, void* stream, int n_steps, const float* timesteps_host, const float* sigmas_host,
+                       const float* noise_levels_host, int dynamics, float guidance, const void* init_latents, int init_dtype,
+                       int storage_dtype, const float* step_noise, const void* prompt_embeds, const void* neg_embeds,
+                       const int32_t* keep_slot_host, void* out_latents, float* out_log_probs, void* out_final,
+                       int compute_log_prob, bool i2v, const void* condition, int cond_dtype, const void* image_embeds) {
     if (!p || !timesteps_host || !sigmas_host || !noise_levels_host || !init_latents || !prompt_embeds)
         return errorf("mi355_wan_rollout: null argument");
+    CHK(check_kind(p, "mi355_wan_rollout", i2v, condition, cond_dtype, image_embeds));
     if (n_steps < 1 || n_steps > p->max_steps) return errorf("mi355_wan_rollout: n_steps %d exceeds the plan's max_steps %d", n_steps, p->max_steps);
     if (storage_dtype < 0 || storage_dtype > 2 || init_dtype < 0 || init_dtype > 2) return errorf("mi355_wan_rollout: bad dtype");
     if (p->ncfg == 2 && !neg_embeds) return errorf("mi355_wan_rollout: plan has n_cfg == 2 but no negative prompt embeddings");
     if (!step_noise && dynamics != MI355_ODE) return errorf("mi355_wan_rollout: step_noise is NULL");
     if (dynamics < 0 || dynamics > 3) return errorf("mi355_wan_rollout: unknown dynamics %d", dynamics);
-    CHK(mi355_wan_weights_ready(p->e));
     hipStream_t st = (hipStream_t)stream;
+    CHK(mi355_wan_weights_ready(p->e));
     CHK(refresh_derived(p->e, st));
+    CHK(write_i2v_inputs(p, st, condition, cond_dtype, image_embeds));      // once per rollout, not once per step
     const int B = p->B, Bp = p->Bp;
     std::vector<float>& tt = p->host_t;
     std::vector<float>& sc = p->host_sc;
@@ -527,6 +716,25 @@ extern "C" int mi355_wan_rollout(mi355_wan_plan* p, void* stream, int n_steps, c
     if (out_final)
         HIPCHK(hipMemcpyAsync(out_final, p->io_traj + (size_t)n_steps * lat_bytes, lat_bytes, hipMemcpyDeviceToDevice, st));
     return 0;
+}
+
+extern "C" int mi355_wan_rollout(mi355_wan_plan* p, void* stream, int n_steps, const float* timesteps_host, const float* sigmas_host,
+                                 const float* noise_levels_host, int dynamics, float guidance, const void* init_latents, int init_dtype,
+                                 int storage_dtype, const float* step_noise, const void* prompt_embeds, const void* neg_embeds,
+                                 const int32_t* keep_slot_host, void* out_latents, float* out_log_probs, void* out_final,
+                                 int compute_log_prob) {
+    return wan_rollout(p, stream, n_steps, timesteps_host, sigmas_host, noise_levels_host, dynamics, guidance, init_latents, init_dtype, storage_dtype,
+                       step_noise, prompt_embeds, neg_embeds, keep_slot_host, out_latents, out_log_probs, out_final, compute_log_prob, false, nullptr, 0,
+                       nullptr);
+}
+extern "C" int mi355_wan_rollout_i2v(mi355_wan_plan* p, void* stream, int n_steps, const float* timesteps_host, const float* sigmas_host,
+                                     const float* noise_levels_host, int dynamics, float guidance, const void* init_latents, int init_dtype,
+                                     int storage_dtype, const float* step_noise, const void* prompt_embeds, const void* neg_embeds,
+                                     const int32_t* keep_slot_host, void* out_latents, float* out_log_probs, void* out_final,
+                                     int compute_log_prob, const void* condition, int cond_dtype, const void* image_embeds) {
+    return wan_rollout(p, stream, n_steps, timesteps_host, sigmas_host, noise_levels_host, dynamics, guidance, init_latents, init_dtype, storage_dtype,
+                       step_noise, prompt_embeds, neg_embeds, keep_slot_host, out_latents, out_log_probs, out_final, compute_log_prob, true, condition,
+                       cond_dtype, image_embeds);
 }
 
 #include "wan_train.inc"

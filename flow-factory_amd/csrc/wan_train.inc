@@ -27,6 +27,8 @@ struct mi355_wan_train : PlanTrain {       // per plan
     bf16_t *x_final, *mod, *kx, *vTx, *ctx;     // this step's modulation rows, cross-attention k / v and text context (the plan's own copies may be
     float* rstd_kx;                             // overwritten by a no-grad forward -- the KL reference pass -- before the backward runs); [L][Mc]
     bf16_t *dx, *dproj, *widec;
+    bf16_t *ki = nullptr, *vTi = nullptr;       // image branch: this step's image K / V^T (own copies, for the reason kx / vTx are)
+    bf16_t* dq_img = nullptr;                   // head-major dq~ of the image cross-attention, added to the text cross-attention's
     int M_pad, Mc_pad;
 };
 
@@ -91,6 +93,7 @@ static int wan_train_of(mi355_wan_plan* p, mi355_wan_train** out) {
     const int M = p->M, Mc = p->Mc;
     const int64_t qk_el = (int64_t)p->Bp * H * p->S_pad * 128, kx_el = (int64_t)p->Bp * H * p->Nt_pad * 128;
     const int64_t bhs = (int64_t)p->Bp * H * p->S_pad;
+    const int64_t ki_el = (int64_t)p->Bp * H * p->Ni_pad * 128;
     mi355_wan_train* t = new mi355_wan_train();
     t->M_pad = (M + 63) / 64 * 64; t->Mc_pad = (Mc + 63) / 64 * 64;
     TrainScratch& sc = t->sc;
@@ -102,7 +105,10 @@ static int wan_train_of(mi355_wan_plan* p, mi355_wan_train** out) {
         c.take(k.pre, (int64_t)M * F);
         c.take(k.q, qk_el); c.take(k.k, qk_el); c.take(k.vT, qk_el); c.take(k.q2, qk_el);
         c.take(k.lse1, bhs); c.take(k.lse2, bhs); c.take(k.rstd_q, M); c.take(k.rstd_k, M); c.take(k.rstd_q2, M);
+        k.o3 = k.o23 = nullptr; k.lse3 = nullptr;
+        if (p->Ni) { c.take(k.o3, (int64_t)M * D); c.take(k.o23, (int64_t)M * D); c.take(k.lse3, bhs); }
     }
+    if (p->Ni) { c.take(t->ki, ki_el * L); c.take(t->vTi, ki_el * L); c.take(t->dq_img, qk_el); }
     c.take(t->x_final, (int64_t)M * D); c.take(t->mod, (int64_t)p->Bp * p->mod_cols);
     c.take(t->kx, kx_el * L); c.take(t->vTx, kx_el * L); c.take(t->ctx, (int64_t)Mc * D); c.take(t->rstd_kx, (int64_t)L * Mc);
     c.take(t->dx, (int64_t)M * D); c.take(t->dproj, (int64_t)M * NO); c.take(t->widec, (int64_t)Mc * 2 * D);
@@ -113,7 +119,7 @@ static int wan_train_of(mi355_wan_plan* p, mi355_wan_train** out) {
     // Nt_pad > S_pad (ADVICE r4).
     // Mmax_pad: operand slots and column-sum partials serve the text-side weight gradients too: rows = the LONGER of the two token counts -- a clip
     // shorter than its prompt overflowed slots sized by the video rows in the first GPU run of this file, profiles/r04t_wan_bwd_diag.txt.
-    const int64_t kv_el = qk_el > kx_el ? qk_el : kx_el;
+    const int64_t kv_el = std::max(std::max(qk_el, kx_el), ki_el);
     const int Mmax_pad = t->M_pad > t->Mc_pad ? t->M_pad : t->Mc_pad;
     const int rows_T = F > 3 * D ? F : 3 * D;
     CHK(t_train_alloc(c, t, "wan training", ScratchSizes{D, F, qk_el, kv_el, bhs, rows_T, F, Mmax_pad, rows_T, 0}));
@@ -125,18 +131,23 @@ static int wan_train_of(mi355_wan_plan* p, mi355_wan_train** out) {
 }
 
 // arguments as mi355_wan_forward; v_out [Bp][C][T][h][w] bf16 (both CFG halves)
-extern "C" int mi355_wan_forward_train(mi355_wan_plan* p, void* stream, const void* latents, int lat_dtype, const float* t_in, const void* enc_a,
-                                       const void* enc_b, void* v_out) {
+static int wan_forward_train(mi355_wan_plan* p, void* stream, const void* latents, int lat_dtype, const float* t_in, const void* enc_a,
+                             const void* enc_b, void* v_out, bool i2v, const void* condition, int cond_dtype, const void* image_embeds) {
     if (!p || !latents || !t_in || !enc_a || !v_out) return errorf("mi355_wan_forward_train: null argument");
     if (lat_dtype < 0 || lat_dtype > 2) return errorf("mi355_wan_forward_train: bad latent dtype %d", lat_dtype);
-    CHK(mi355_wan_weights_ready(p->e));
     hipStream_t st = (hipStream_t)stream;
+    // (image-to-video: the backward reads nothing below blocks.0 -- the patch embedder is frozen and block 0's input is stashed -- so the
+    //  condition columns of the plan's patch buffer need no copy in the training stash, a deliberate difference from the image K / V^T below,
+    //  which the backward does read: a later no-grad forward may overwrite the plan's patch buffer freely)
+    CHK(check_kind(p, "mi355_wan_forward_train", i2v, condition, cond_dtype, image_embeds));
+    CHK(mi355_wan_weights_ready(p->e));
     CHK(refresh_derived(p->e, st));
     mi355_wan_train* t = nullptr;
     CHK(wan_train_of(p, &t));
     mi355_wan* e = p->e;
     const int64_t kx_el = (int64_t)p->Bp * e->H * p->Nt_pad * 128;
     HIPCHK(hipMemcpyAsync(p->t_dev, t_in, (size_t)p->Bp * 4, hipMemcpyDeviceToDevice, st));
+    CHK(write_i2v_inputs(p, st, condition, cond_dtype, image_embeds));
     CHK(prepare_prompt(p, st, enc_a, enc_b, t->rstd_kx));
     CHK(prepare_conditioning(p, st, 1));
     // this step's cross-attention k / v, text context and modulation rows: the plan's own copies may be overwritten by a no-grad forward on other
@@ -145,9 +156,24 @@ extern "C" int mi355_wan_forward_train(mi355_wan_plan* p, void* stream, const vo
     HIPCHK(copy_d2d(t->vTx, p->vTx, (size_t)kx_el * e->L * 2, st));
     HIPCHK(copy_d2d(t->ctx, p->ctx, (size_t)p->Mc * e->D * 2, st));
     HIPCHK(copy_d2d(t->mod, p->mod_all, (size_t)p->Bp * p->mod_cols * 2, st));
-    CHK(forward_core(p, st, latents, lat_dtype, p->mod_all, (bf16_t*)v_out, t->blk.data(), t->x_final, t->kx, t->vTx));
+    if (p->Ni) {
+        const size_t ki_b = (size_t)p->Bp * e->H * p->Ni_pad * 128 * e->L * 2;
+        HIPCHK(copy_d2d(t->ki, p->ki, ki_b, st));
+        HIPCHK(copy_d2d(t->vTi, p->vTi, ki_b, st));
+    }
+    CHK(forward_core(p, st, latents, lat_dtype, p->mod_all, (bf16_t*)v_out, t->blk.data(), t->x_final, t->kx, t->vTx, t->ki, t->vTi));
     t->have_forward = true;
     return 0;
+}
+
+extern "C" int mi355_wan_forward_train(mi355_wan_plan* p, void* stream, const void* latents, int lat_dtype, const float* t_in, const void* enc_a,
+                                       const void* enc_b, void* v_out) {
+    return wan_forward_train(p, stream, latents, lat_dtype, t_in, enc_a, enc_b, v_out, false, nullptr, 0, nullptr);
+}
+// arguments as mi355_wan_forward_i2v; mi355_wan_backward serves both plan kinds (no gradient flows to the condition)
+extern "C" int mi355_wan_forward_train_i2v(mi355_wan_plan* p, void* stream, const void* latents, int lat_dtype, const float* t_in, const void* enc_a,
+                                           const void* enc_b, const void* condition, int cond_dtype, const void* image_embeds, void* v_out) {
+    return wan_forward_train(p, stream, latents, lat_dtype, t_in, enc_a, enc_b, v_out, true, condition, cond_dtype, image_embeds);
 }
 
 // d loss / d weights from dv = d loss / d v_out [Bp][C][T][h][w] fp32 (v_out = the prediction of the LAST mi355_wan_forward_train on this plan)
@@ -166,6 +192,8 @@ extern "C" int mi355_wan_backward(mi355_wan_plan* p, void* stream, const float* 
     TrainScratch& sc = t->sc;
     const AttnGeom ag_self{p->Bp, e->H, D, S, p->S_pad, p->cs, nullptr, 0, 0};
     const AttnGeom ag_cross{p->Bp, e->H, D, S, p->S_pad, nullptr, nullptr, p->Nt, p->Nt_pad};
+    const AttnGeom ag_img{p->Bp, e->H, D, S, p->S_pad, nullptr, nullptr, p->Ni, p->Ni_pad};
+    const int64_t ki_el = (int64_t)p->Bp * e->H * p->Ni_pad * 128, qk_el = (int64_t)p->Bp * e->H * p->S_pad * 128;
     const ModRows mr{mod, mld, e->cfg.eps};
     const TrainChain ch{st, M, t->M_pad, S, sc.g1, sc.g2, sc.g3, sc.wide, sc.hid, false};
     auto G = [&](int i, const char* layer) { return ts->grads.linear("blocks." + std::to_string(i) + layer); };
@@ -187,8 +215,15 @@ extern "C" int mi355_wan_backward(mi355_wan_plan* p, void* stream, const float* 
         // ---- feed-forward (gated residual)
         CHK(t_mlp_back(sc, ch, mr, m0, D, F, t->dx, k.x_mid2, k.xn3, k.pre, w.ff1, w.ff2, G(i, ".ffn.net.0.proj"), G(i, ".ffn.net.2")));
         // ---- cross-attention (x += attn2(norm2(x), text): no gate): d (projection output) = d x
-        CHK(t_linear_back(sc, ch, t->dx, D, D, k.o2, D, D, w.o2, G(i, ".attn2.to_out.0"), sc.g2, D));
+        CHK(t_linear_back(sc, ch, t->dx, D, D, p->Ni ? k.o23 : k.o2, D, D, w.o2, G(i, ".attn2.to_out.0"), sc.g2, D));
+        if (p->Ni) {
+            // image branch: the same dO through the image softmax first (its own o and log-sum-exp: delta is per softmax); its dK / dV have no
+            // consumer (add_k_proj / add_v_proj / norm_added_k are frozen) and are overwritten by the text pass, its dq~ is kept aside
+            CHK(t_attention128_backward(sc, ag_img, st, k.q2, t->ki + i * ki_el, t->vTi + i * ki_el, k.lse3, k.o3, nullptr, sc.g2, nullptr, S));
+            HIPCHK(copy_d2d(t->dq_img, sc.dq, (size_t)qk_el * 2, st));
+        }
         CHK(t_attention128_backward(sc, ag_cross, st, k.q2, t->kx + i * kx_el, t->vTx + i * kx_el, k.lse2, k.o2, nullptr, sc.g2, nullptr, S));
+        if (p->Ni) HIPCHK(launch_add_bf16(sc.dq, t->dq_img, sc.dq, (long)qk_el, st));      // dq~ = dq~_text + dq~_img: fp32 sum, one bf16 rounding
         // queries: full-row RMSNorm backward (no RoPE) -> d (to_q output) [M][D]
         HIPCHK(norm_back(k.q2, sc.dq, b.nq2, k.rstd_q2, false, kScale, sc.wide, D, 0, M, S, p->S_pad));
         CHK(t_linear_back(sc, ch, sc.wide, D, D, k.xn2, D, D, w.q2, G(i, ".attn2.to_q"), sc.g3, D));

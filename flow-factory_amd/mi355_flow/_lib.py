@@ -189,6 +189,12 @@ SIGNATURES = {
     "mi355_wan_forward_train": (_I, [_P, _P, _P, _I, _P, _P, _P, _P]),
     "mi355_wan_backward": (_I, [_P, _P, _P]),
     "mi355_op_norm_rope_full_fwd_bwd": (_I, [_P, _P, _L, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F]),
+    "mi355_wan_create_i2v": (_I, [C.POINTER(WanCfg), _I, _I, C.POINTER(_P)]),
+    "mi355_wan_plan_create_i2v": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_P)]),
+    "mi355_wan_forward_i2v": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P]),
+    "mi355_wan_rollout_i2v": (_I, [_P, _P, _I, C.POINTER(_F), C.POINTER(_F), C.POINTER(_F), _I, _F, _P, _I, _I, _P, _P, _P,
+                                   C.POINTER(C.c_int32), _P, _P, _P, _I, _P, _I, _P]),
+    "mi355_wan_forward_train_i2v": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P]),
     "mi355_qwen_create": (_I, [C.POINTER(QwenCfg), C.POINTER(_P)]),
     "mi355_qwen_destroy": (_I, [_P]),
     "mi355_qwen_bind_weight": (_I, [_P, C.c_char_p, _P, _I, _I, C.POINTER(_L), _P]),

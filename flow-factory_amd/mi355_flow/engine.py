@@ -168,9 +168,13 @@ class EngineBase(WeightHolder):
         self.cfg = cfg
         h = C.c_void_p()
         c = cfg.to_c()
-        _lib.check(self._fn("create")(C.byref(c), C.byref(h)), f"{self._ABI}_create")
+        self._create(c, h)
         self._h = h
         self._plans: Dict[tuple, "PlanBase"] = {}
+
+    def _create(self, c, h) -> None:
+        """The C constructor of this engine (hook: a family with more than one constructor chooses here)."""
+        _lib.check(self._fn("create")(C.byref(c), C.byref(h)), f"{self._ABI}_create")
 
     def plan(self, *shape_and_max_steps: int):
         """`plan(*shape, max_steps)`: the cached workspace for one shape (the positional arguments of the family's plan class), replaced by a

@@ -1,5 +1,6 @@
 """The binding a Flow-Factory installation uses:  `model.model_type: mi355_flow.flow_factory_plugin.SD3_5NativeAdapter`
-(also `...Flux1NativeAdapter`, `...Flux1KontextNativeAdapter`, `...Wan2T2VNativeAdapter`, `...QwenImageNativeAdapter`).
+(also `...Flux1NativeAdapter`, `...Flux1KontextNativeAdapter`, `...Wan2T2VNativeAdapter`, `...Wan2I2VNativeAdapter`,
+`...QwenImageNativeAdapter`).
 
 Flow-Factory resolves an unknown `model_type` as a python path (reference src/flow_factory/models/registry.py:69-82) and
 constructs `cls(config=config, accelerator=accelerator)` (models/loader.py:61-64).  Each class below IS the reference's own
@@ -350,6 +351,22 @@ if _RefAdapter is not None:
     if _RefWan is not None:
         from .wan import WanConfig, WanEngine, WanRolloutMixin
 
+        def _wan_bind_experts(self, wcfg) -> None:
+            """One engine for a single-transformer pipeline; Wan2.2: the high-noise and the low-noise expert, or the low-noise one alone."""
+            ratio = getattr(self.pipeline.config, "boundary_ratio", None)
+            second = getattr(self.pipeline, "transformer_2", None)
+            if second is not None and ratio is not None and 0 < ratio <= 1:     # (ratio == 1: t == 1000 still picks the high-noise expert)
+                self._init_live(WanEngine(wcfg(self.pipeline.transformer.config)))
+                self.engine_2 = WanEngine(wcfg(second.config))
+                self._live_weights_2 = LiveWeights(self.engine_2, lambda: self.transformer_2)
+                self.boundary_ratio = float(ratio)
+            elif second is not None and ratio is not None and ratio > 1:         # every t is below the boundary: only the low-noise expert,
+                self._init_live(WanEngine(wcfg(second.config)))                  # with ITS guidance scale (wan2_t2v.py:482-485)
+                self._live_weights = LiveWeights(self.engine, lambda: self.transformer_2)
+                self.low_noise_only = True
+            else:
+                self._init_live(WanEngine(wcfg(self.pipeline.transformer.config)))
+
         class Wan2T2VNativeAdapter(_LiveBinding, WanRolloutMixin, _RefWan):
             """`Wan2_T2V_Adapter` (reference models/wan/wan2_t2v.py) with the rollout on the MI355X engine: single-transformer Wan2.1, and
             two-expert Wan2.2 pipelines (`transformer` while t >= boundary_ratio * 1000, `transformer_2` below, each with its own
@@ -378,19 +395,7 @@ if _RefAdapter is not None:
                     return WanConfig(in_channels=tc.in_channels, out_channels=tc.out_channels, num_layers=tc.num_layers,
                                      num_attention_heads=tc.num_attention_heads, attention_head_dim=tc.attention_head_dim, ffn_dim=tc.ffn_dim,
                                      text_dim=tc.text_dim, freq_dim=tc.freq_dim, patch_size=tuple(tc.patch_size), eps=tc.eps)
-                ratio = getattr(self.pipeline.config, "boundary_ratio", None)
-                second = getattr(self.pipeline, "transformer_2", None)
-                if second is not None and ratio is not None and 0 < ratio <= 1:     # (ratio == 1: t == 1000 still picks the high-noise expert)
-                    self._init_live(WanEngine(wcfg(self.pipeline.transformer.config)))
-                    self.engine_2 = WanEngine(wcfg(second.config))
-                    self._live_weights_2 = LiveWeights(self.engine_2, lambda: self.transformer_2)
-                    self.boundary_ratio = float(ratio)
-                elif second is not None and ratio is not None and ratio > 1:         # every t is below the boundary: only the low-noise expert,
-                    self._init_live(WanEngine(wcfg(second.config)))                  # with ITS guidance scale (wan2_t2v.py:482-485)
-                    self._live_weights = LiveWeights(self.engine, lambda: self.transformer_2)
-                    self.low_noise_only = True
-                else:
-                    self._init_live(WanEngine(wcfg(self.pipeline.transformer.config)))
+                _wan_bind_experts(self, wcfg)
 
             def _eval_inference(self, **kwargs):          # MI355_WAN_EVAL_REFERENCE=1 only: the reference's own evaluation loop
                 return _RefWan.inference(self, **kwargs)
@@ -423,6 +428,70 @@ if _RefAdapter is not None:
                     logger.warning("mi355_flow: grad-mode forward() differentiates through the reference path (%s); values stay the engine's", why)
                     self._warned_ref_grad = True
                 return self._replay_on_reference(_RefWan.forward, WanRolloutMixin._forward_nograd, (), kwargs)
+
+    try:
+        from flow_factory.models.wan.wan2_i2v import Wan2_I2V_Adapter as _RefWanI2V, WanI2VSample as _RefWanI2VSample
+    except Exception:  # noqa: BLE001
+        _RefWanI2V = None
+
+    if _RefWan is not None and _RefWanI2V is not None:
+        from .wan import WanI2VRolloutMixin
+
+        class Wan2I2VNativeAdapter(_LiveBinding, WanI2VRolloutMixin, _RefWanI2V):
+            """`Wan2_I2V_Adapter` (reference models/wan/wan2_i2v.py) with the rollout on image-to-video engine(s): the condition channels
+            (Wan2.2-I2V-A14B: two experts, no image embeddings).  The reference's own `encode_image`, `preprocess_func` and `prepare_latents`
+            (VAE encode of the conditioning clip, the mask) produce the condition on the pipeline's torch modules, once per rollout; the
+            samples are the reference's `WanI2VSample`.  A Wan2.1-I2V transformer (`image_dim` set) gets the image cross-attention branch; its
+            `image_embeds` come from the reference's own `encode_image` (CLIP on the pipeline's torch modules).  Refused at construction:
+            `expand_timesteps` pipelines (Wan2.2-TI2V-5B: one timestep per token)."""
+
+            _sample_cls = _RefWanI2VSample
+            _output_cls = _RefOutput
+
+            def __init__(self, config, accelerator):
+                _RefWanI2V.__init__(self, config, accelerator)
+                self.expand_timesteps = bool(getattr(self.pipeline.config, "expand_timesteps", False))
+                self._refuse_expand_timesteps()
+                self.vae_scale_temporal = int(getattr(self.pipeline, "vae_scale_factor_temporal", 4))
+                self.vae_scale_spatial = int(getattr(self.pipeline, "vae_scale_factor_spatial", 8))
+                _wan_bind_experts(self, WanConfig.from_hf)
+
+            def _prepare_i2v(self, images, last_image, image_embeds, B, T, h, w, height, width, num_frames, generator):
+                # wan2_i2v.py:484, :514-546 -- the reference's own steps, in its order: `prepare_latents` draws the fp32 latents, then encodes
+                device = self.device
+                images = self._standardize_image_input(images, output_type="pil")
+                if self.engine.cfg.image_dim and image_embeds is None:          # only the Wan2.1-I2V transformer takes them (wan2_i2v.py:514-522)
+                    image_embeds = self.encode_image(images if last_image is None else [images, last_image], device)["image_embeds"]
+                if image_embeds is not None:
+                    image_embeds = image_embeds.to(device=device, dtype=self.transformer_dtype)
+                pre = lambda im: self.pipeline.video_processor.preprocess(im, height=height, width=width).to(device, dtype=torch.float32)    # noqa: E731
+                images = pre(images)
+                last = pre(last_image) if last_image is not None else None
+                latents, condition = self.prepare_latents(image=images, batch_size=B, num_channels_latents=self.pipeline.vae.config.z_dim, height=height,
+                                                          width=width, num_frames=num_frames, dtype=torch.float32, device=device, generator=generator,
+                                                          latents=None, last_image=last)
+                return latents, condition, image_embeds, lambda b: dict(condition=condition[b], first_frame_mask=None, condition_images=images[b],
+                                                                        image_embeds=image_embeds[b] if image_embeds is not None else None)
+
+            def _eval_inference(self, **kwargs):          # MI355_WAN_EVAL_REFERENCE=1 only: the reference's own evaluation loop
+                return _RefWanI2V.inference(self, **kwargs)
+
+            decode_latents = Wan2T2VNativeAdapter.decode_latents
+
+            @functools.wraps(WanI2VRolloutMixin.forward)
+            def forward(self, *args, **kwargs):
+                if bool(getattr(self.scheduler, "is_eval", False)):
+                    return _RefWanI2V.forward(self, *args, **kwargs)
+                if torch.is_grad_enabled() and not WanEngine.native_backward_enabled:
+                    return self._replay_on_reference(_RefWanI2V.forward, WanI2VRolloutMixin.forward, args, kwargs)     # (called under no_grad)
+                return WanI2VRolloutMixin.forward(self, *args, **kwargs)
+
+            def _grad_fallback(self, why, kwargs):
+                _require_reference_autograd("Wan I2V", why)
+                if not getattr(self, "_warned_ref_grad", False):
+                    logger.warning("mi355_flow: grad-mode forward() differentiates through the reference path (%s); values stay the engine's", why)
+                    self._warned_ref_grad = True
+                return self._replay_on_reference(_RefWanI2V.forward, WanI2VRolloutMixin._forward_nograd, (), kwargs)
 
     try:
         from flow_factory.models.qwen_image.qwen_image import QwenImageAdapter as _RefQwen, QwenImageSample as _RefQwenSample
@@ -490,4 +559,5 @@ else:
     Flux1NativeAdapter = _unavailable("Flux1NativeAdapter", "mi355_flow.flux.Flux1NativeAdapter")
     Flux1KontextNativeAdapter = _unavailable("Flux1KontextNativeAdapter", "mi355_flow.flux.Flux1KontextNativeAdapter")
     Wan2T2VNativeAdapter = _unavailable("Wan2T2VNativeAdapter", "mi355_flow.wan.Wan2T2VNativeAdapter")
+    Wan2I2VNativeAdapter = _unavailable("Wan2I2VNativeAdapter", "mi355_flow.wan.Wan2I2VNativeAdapter")
     QwenImageNativeAdapter = _unavailable("QwenImageNativeAdapter", "mi355_flow.qwen.QwenImageNativeAdapter")

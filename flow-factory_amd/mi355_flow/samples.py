@@ -273,3 +273,14 @@ class QwenImageSample(BaseSample):
 class WanT2VSample(BaseSample):
     """reference wan2_t2v.py:49-51: video latents `(P, 16, T, h, w)` in `all_latents`, the decoded clip in `video`."""
     _shared_fields: ClassVar[frozenset] = frozenset()
+
+
+@dataclass
+class WanI2VSample(ImageConditionSample):
+    """reference wan2_i2v.py:56-63 (`I2VSample` adds nothing to `ImageConditionSample`): the T2V trajectory, the sample's condition
+    `(4 mask + 16 latent, T, h, w)`, its CLIP image embeddings `(Ni, image_dim)` (Wan2.1-I2V) and the timestep mask of the
+    `expand_timesteps` pipelines, shared by the batch."""
+    _shared_fields: ClassVar[frozenset] = frozenset({"first_frame_mask"})
+    image_embeds: Optional[torch.Tensor] = None
+    condition: Optional[torch.Tensor] = None
+    first_frame_mask: Optional[torch.Tensor] = None

@@ -4,7 +4,10 @@
 Kept from the reference: latents `(B, 16, T, h, w)` drawn in fp32 (`prepare_latents(dtype=float32)`), `timestep = t.expand(B)` with
 the scheduler's integer timesteps, classifier-free guidance as `u + g (c - u)` (here one forward over the batch [negative, positive]
 instead of two passes), `UniPCMultistepSDEScheduler.step` in rollout mode = the four SDE / ODE dynamics with sigma = t / 1000.
-Not covered (raise): `attention_kwargs`; image-conditioned TI2V (per-token timesteps that DIFFER: the text-to-video use of Wan2.2-TI2V-5B, whose
+Image-to-video with condition channels (Wan2.2-I2V-A14B; `Wan2_I2V_Adapter`, reference models/wan/wan2_i2v.py): `WanI2VRolloutMixin`,
+`Wan2I2VNativeAdapter`, `wan_i2v_condition` below, on an engine created with `WanConfig.cond_channels`; Wan2.1-I2V's CLIP image
+cross-attention branch with `WanConfig.image_dim` and `image_embeds=`.
+Not covered (raise): `attention_kwargs`; the image embedder's `pos_embed` (first-and-last-frame checkpoints); image-conditioned TI2V (per-token timesteps that DIFFER: the text-to-video use of Wan2.2-TI2V-5B, whose
 `expand_timesteps` mask is all ones, runs as the scalar-timestep forward).  The causal 3-D video VAE decode is native too
 (`mi355_flow.vae.WanVAEDecoder`, csrc/wan_vae_engine.hip): pass `vae_state_dict` to the standalone adapter (or a `video_decode` callable).
 """
@@ -20,7 +23,7 @@ import torch
 from ._lib import WanCfg
 from .engine import EngineBase, PlanBase, _bf16c, _ptr, _stream, dtype_code, sde_step
 from .host import RolloutMixinBase, StandaloneAdapterBase
-from .samples import WanT2VSample
+from .samples import WanI2VSample, WanT2VSample
 from .scheduler import FlowMatchEulerDiscreteSDEScheduler, SDESchedulerOutput, randn_tensor
 from .trajectory import TrajectoryIndicesType
 
@@ -29,7 +32,9 @@ VAE_SCALE_SPATIAL, VAE_SCALE_TEMPORAL = 8, 4
 
 @dataclass
 class WanConfig:
-    """diffusers WanTransformer3DModel config fields the engine needs (Wan2.1-T2V-1.3B defaults)."""
+    """diffusers WanTransformer3DModel config fields the engine needs (Wan2.1-T2V-1.3B defaults).  `in_channels` is the LATENT channel count
+    (the scheduler's state); an image-to-video transformer takes `cond_channels` more at its patch embedding (4 mask + 16 latent = 20:
+    `cat([latents, condition], 1)`, reference wan2_i2v.py:744) and, for Wan2.1-I2V, CLIP image embeddings of width `image_dim`."""
     in_channels: int = 16
     out_channels: int = 16
     num_layers: int = 30
@@ -40,10 +45,28 @@ class WanConfig:
     freq_dim: int = 256
     patch_size: Tuple[int, int, int] = (1, 2, 2)
     eps: float = 1e-6
+    cond_channels: int = 0
+    image_dim: Optional[int] = None
 
     @property
     def dim(self) -> int:
         return self.num_attention_heads * self.attention_head_dim
+
+    @classmethod
+    def from_hf(cls, config) -> "WanConfig":
+        """From a diffusers `WanTransformer3DModel.config` (object or dict).  The HF `in_channels` counts what the patch embedding sees:
+        latent channels = `out_channels`, `cond_channels = in_channels - out_channels` (36 - 16 = 20 for the I2V transformers, 0 for T2V and
+        for Wan2.2-TI2V-5B's 48 / 48), and the image branch exists iff `image_dim` is set (Wan2.1-I2V; Wan2.2-I2V-A14B has none)."""
+        g = (lambda k, d=None: config.get(k, d)) if isinstance(config, dict) else (lambda k, d=None: getattr(config, k, d))
+        inc = int(g("in_channels", 16))
+        out = int(g("out_channels", None) or inc)
+        if inc < out:
+            raise ValueError(f"mi355_flow: Wan transformer with in_channels {inc} < out_channels {out}")
+        image_dim = g("image_dim", None)
+        return cls(in_channels=out, out_channels=out, num_layers=int(g("num_layers", 30)), num_attention_heads=int(g("num_attention_heads", 12)),
+                   attention_head_dim=int(g("attention_head_dim", 128)), ffn_dim=int(g("ffn_dim", 8960)), text_dim=int(g("text_dim", 4096)),
+                   freq_dim=int(g("freq_dim", 256)), patch_size=tuple(g("patch_size", (1, 2, 2))), eps=float(g("eps", 1e-6)),
+                   cond_channels=inc - out, image_dim=int(image_dim) if image_dim else None)
 
     def to_c(self) -> WanCfg:
         return WanCfg(self.in_channels, self.out_channels, self.num_layers, self.num_attention_heads, self.attention_head_dim, self.ffn_dim,
@@ -76,13 +99,39 @@ class UniPCMultistepSDEScheduler(FlowMatchEulerDiscreteSDEScheduler):
 class WanPlan(PlanBase):
     _PRE = "wan_"
 
-    def __init__(self, engine: WanEngine, batch: int, n_cfg: int, T: int, h: int, w: int, n_text: int, max_steps: int):
-        self.batch, self.n_cfg, self.T, self.h, self.w, self.n_text = batch, n_cfg, T, h, w, n_text
-        super().__init__(engine, (batch, n_cfg, T, h, w, n_text), max_steps)
+    def __init__(self, engine: WanEngine, batch: int, n_cfg: int, T: int, h: int, w: int, n_text: int, max_steps: int, n_image: int = 0):
+        self.batch, self.n_cfg, self.T, self.h, self.w, self.n_text, self.n_image = batch, n_cfg, T, h, w, n_text, n_image
+        self.cond_channels = engine.cfg.cond_channels          # > 0: an image-to-video plan, served by the `_i2v` entry points only
+        shape = (batch, n_cfg, T, h, w, n_text)
+        if self.cond_channels:
+            self._CREATE, shape = "plan_create_i2v", shape + (n_image,)
+        elif n_image:
+            raise ValueError("mi355_flow: n_image needs an image-to-video Wan engine (WanConfig.cond_channels > 0)")
+        super().__init__(engine, shape, max_steps)
         # d loss / d v arrives as [uncond | text], as `engine.sde_step_bwd` returns it
         self.dv_shape = (batch * n_cfg, engine.cfg.out_channels, T, h, w)
 
-    def _forward(self, symbol: str, latents, t, enc_a, enc_b) -> torch.Tensor:
+    def _i2v_args(self, condition, image_embeds) -> Optional[tuple]:
+        """(condition, its dtype code, image_embeds) as the `_i2v` entry points take them; None = a plain call.  A plain plan handed a
+        condition still goes to the `_i2v` symbol, which refuses it (and the other way round): the C side owns that rule."""
+        if condition is None and image_embeds is None and not self.cond_channels:
+            return None
+        if self.cond_channels:
+            if condition is None:
+                raise ValueError("mi355_flow: an image-to-video Wan plan needs `condition` (cat([mask (4), latent condition (16)], 1): wan_i2v_condition)")
+            want = (self.batch, self.cond_channels, self.T, self.h, self.w)
+            if tuple(condition.shape) != want:
+                raise ValueError(f"mi355_flow: condition has shape {tuple(condition.shape)}, expected {want}")
+            if self.n_image:
+                want = (self.batch, self.n_image, self.engine.cfg.image_dim)
+                if image_embeds is None or tuple(image_embeds.shape) != want:
+                    raise ValueError(f"mi355_flow: this plan was created with n_image={self.n_image}: image_embeds "
+                                     f"{None if image_embeds is None else tuple(image_embeds.shape)}, expected {want}")
+        condition = condition.contiguous() if condition is not None else None
+        image_embeds = _bf16c(image_embeds) if image_embeds is not None else None
+        return condition, dtype_code(condition.dtype) if condition is not None else 0, image_embeds
+
+    def _forward(self, symbol: str, latents, t, enc_a, enc_b, condition=None, image_embeds=None) -> torch.Tensor:
         B, Bp = self.batch, self.batch * self.n_cfg
         assert tuple(latents.shape) == (B, self.C, self.T, self.h, self.w), latents.shape
         dev = latents.device
@@ -93,34 +142,48 @@ class WanPlan(PlanBase):
         latents = latents.contiguous()
         ea = _bf16c(enc_a)
         eb = _bf16c(enc_b) if enc_b is not None else None
-        self._call(symbol, self._h, _stream(), _ptr(latents), dtype_code(latents.dtype), _ptr(t), _ptr(ea), _ptr(eb), _ptr(out))
+        i2v = self._i2v_args(condition, image_embeds)
+        if i2v is None:
+            self._call(symbol, self._h, _stream(), _ptr(latents), dtype_code(latents.dtype), _ptr(t), _ptr(ea), _ptr(eb), _ptr(out))
+        else:
+            self._call(symbol + "_i2v", self._h, _stream(), _ptr(latents), dtype_code(latents.dtype), _ptr(t), _ptr(ea), _ptr(eb), _ptr(i2v[0]), i2v[1],
+                       _ptr(i2v[2]), _ptr(out))
         return out
 
-    def transformer_forward(self, latents: torch.Tensor, t: torch.Tensor, enc_a: torch.Tensor, enc_b: Optional[torch.Tensor] = None):
-        """latents (B, 16, T, h, w); t (B*n_cfg,) or scalar; n_cfg == 2: enc_a = negative, enc_b = positive, output (2B, ...)."""
-        return self._forward("forward", latents, t, enc_a, enc_b)
+    def transformer_forward(self, latents: torch.Tensor, t: torch.Tensor, enc_a: torch.Tensor, enc_b: Optional[torch.Tensor] = None,
+                            condition: Optional[torch.Tensor] = None, image_embeds: Optional[torch.Tensor] = None):
+        """latents (B, 16, T, h, w); t (B*n_cfg,) or scalar; n_cfg == 2: enc_a = negative, enc_b = positive, output (2B, ...).
+        Image-to-video plan: + condition (B, cond_channels, T, h, w), read by both CFG halves."""
+        return self._forward("forward", latents, t, enc_a, enc_b, condition, image_embeds)
 
     # ---------------------------------------------------------------- differentiable forward (optimize() replay)
-    def forward_train(self, latents: torch.Tensor, t: torch.Tensor, enc_a: torch.Tensor, enc_b: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def forward_train(self, latents: torch.Tensor, t: torch.Tensor, enc_a: torch.Tensor, enc_b: Optional[torch.Tensor] = None,
+                      condition: Optional[torch.Tensor] = None, image_embeds: Optional[torch.Tensor] = None) -> torch.Tensor:
         """mi355_wan_forward_train: `transformer_forward` on per-block activation buffers -- the same kernel binaries, so the prediction is
         bit-identical -- keeping what `backward` needs in the plan's training stash (ONE per plan; every call takes a serial number)."""
-        out = self._forward("forward_train", latents, t, enc_a, enc_b)
+        out = self._forward("forward_train", latents, t, enc_a, enc_b, condition, image_embeds)
         self._train_serial += 1
         return out
 
     def rollout(self, timesteps: Sequence[float], sigmas: Sequence[float], noise_levels: Sequence[float], dynamics: str, guidance: float,
                 init_latents: torch.Tensor, storage_dtype: torch.dtype, step_noise: Optional[torch.Tensor], prompt_embeds: torch.Tensor,
-                neg_embeds: Optional[torch.Tensor] = None, keep_positions: Optional[Sequence[int]] = None, compute_log_prob: bool = True):
+                neg_embeds: Optional[torch.Tensor] = None, condition: Optional[torch.Tensor] = None, image_embeds: Optional[torch.Tensor] = None,
+                keep_positions: Optional[Sequence[int]] = None, compute_log_prob: bool = True):
         shape = (self.batch, self.C, self.T, self.h, self.w)
         assert tuple(init_latents.shape) == shape, init_latents.shape
         pe = _bf16c(prompt_embeds)
         ne = _bf16c(neg_embeds) if neg_embeds is not None else None
+        i2v = self._i2v_args(condition, image_embeds)
+        if i2v is None:
+            return self._rollout(shape, timesteps, sigmas, noise_levels, dynamics, guidance, init_latents, storage_dtype, step_noise,
+                                 (_ptr(pe), _ptr(ne)), keep_positions, compute_log_prob)
         return self._rollout(shape, timesteps, sigmas, noise_levels, dynamics, guidance, init_latents, storage_dtype, step_noise,
-                             (_ptr(pe), _ptr(ne)), keep_positions, compute_log_prob)
+                             (_ptr(pe), _ptr(ne)), keep_positions, compute_log_prob, symbol="rollout_i2v", tail=(_ptr(i2v[0]), i2v[1], _ptr(i2v[2])))
 
 
 class WanEngine(EngineBase):
-    """Owns the packed bf16 copy of one Wan transformer (mi355_wan).  `plan(batch, n_cfg, T, h, w, n_text, max_steps)`."""
+    """Owns the packed bf16 copy of one Wan transformer (mi355_wan).  `plan(batch, n_cfg, T, h, w, n_text, max_steps)`.
+    `cfg.cond_channels > 0`: an image-to-video transformer (mi355_wan_create_i2v); its plans take `condition=`."""
 
     _ABI, _WHAT, _PLAN = "wan", "Wan transformer", WanPlan
 
@@ -131,8 +194,50 @@ class WanEngine(EngineBase):
     def __init__(self, cfg: WanConfig = WanConfig()):
         super().__init__(cfg)
 
+    def _create(self, c, h) -> None:
+        cfg = self.cfg
+        if cfg.image_dim and not cfg.cond_channels:
+            raise ValueError("mi355_flow: image_dim needs an image-to-video Wan transformer (cond_channels > 0)")
+        if not cfg.cond_channels:
+            return super()._create(c, h)
+        import ctypes as C
+        from . import _lib
+        _lib.check(self.lib.mi355_wan_create_i2v(C.byref(c), int(cfg.cond_channels), int(cfg.image_dim or 0), C.byref(h)), "wan_create_i2v")
+
+    def plan(self, *shape_and_max_steps: int, n_image: int = 0):
+        """`plan(batch, n_cfg, T, h, w, n_text, max_steps, n_image=0)`; n_image = CLIP image tokens per sample of the image cross-attention
+        branch (Wan2.1-I2V: 257), 0 = a plan without it."""
+        if not n_image:
+            return super().plan(*shape_and_max_steps)
+        *shape, max_steps = shape_and_max_steps
+        key = tuple(shape) + ("n_image", int(n_image))
+        p = self._plans.get(key)
+        if p is None or p.max_steps < max_steps:
+            if p is not None:
+                p.close()
+            p = self._plans[key] = WanPlan(self, *shape, max_steps, n_image=int(n_image))
+        return p
+
+    def bind_state_dict(self, state_dict, *a, **k) -> None:
+        bad = [n for n in state_dict if "image_embedder.pos_embed" in n]
+        if bad:
+            raise NotImplementedError(f"mi355_flow: '{bad[0]}': the learned position embedding of the image embedder (first-and-last-frame "
+                                      "Wan checkpoints) is not implemented natively")
+        super().bind_state_dict(state_dict, *a, **k)
+
     def grad_supported(self, name: str) -> int:
         return super().grad_supported(name) if type(self).native_backward_enabled else 0
+
+
+def _i2v_kw(condition, image_embeds) -> Dict[str, Any]:
+    """The image-to-video inputs as keywords of `transformer_forward` / `forward_train` / `rollout`; empty for text-to-video."""
+    return {} if condition is None and image_embeds is None else dict(condition=condition, image_embeds=image_embeds)
+
+
+def _n_image_kw(image_embeds=None, plan=None) -> Dict[str, int]:
+    """`n_image=` for `WanEngine.plan` from the image embeddings of this call (or from the plan a smaller one replaces); empty without."""
+    n = image_embeds.shape[1] if image_embeds is not None else int(getattr(plan, "n_image", 0) or 0)
+    return dict(n_image=n) if n else {}
 
 
 class WanRolloutMixin(RolloutMixinBase):
@@ -209,6 +314,16 @@ class WanRolloutMixin(RolloutMixinBase):
                 negative_prompt_embeds=negative_prompt_embeds, compute_log_prob=compute_log_prob, attention_kwargs=attention_kwargs,
                 max_sequence_length=max_sequence_length, extra_call_back_kwargs=extra_call_back_kwargs,
                 trajectory_indices=trajectory_indices)
+        return self._wan_inference(prompt, negative_prompt, height, width, num_frames, num_inference_steps, guidance_scale, guidance_scale_2, generator,
+                                   prompt_ids, prompt_embeds, negative_prompt_ids, negative_prompt_embeds, compute_log_prob, attention_kwargs,
+                                   extra_call_back_kwargs, trajectory_indices, eval_mode)
+
+    def _wan_inference(self, prompt, negative_prompt, height, width, num_frames, num_inference_steps, guidance_scale, guidance_scale_2, generator,
+                       prompt_ids, prompt_embeds, negative_prompt_ids, negative_prompt_embeds, compute_log_prob, attention_kwargs,
+                       extra_call_back_kwargs, trajectory_indices, eval_mode, i2v=None):
+        """Body of `inference()`.  `i2v` (image-to-video, `WanI2VRolloutMixin`): callable (B, T, h, w, height, width, num_frames, generator) ->
+        (latents, condition, image_embeds, per-sample fields of the sample class), run where the reference calls `prepare_latents`."""
+        device = self.device
         self._before_engine_call()
         if attention_kwargs:
             raise NotImplementedError("mi355_flow: attention_kwargs are not supported by the native engine")
@@ -245,15 +360,21 @@ class WanRolloutMixin(RolloutMixinBase):
         T, h, w = (num_frames - 1) // vst + 1, height // vss, width // vss
         # RNG in the reference's order: prepare_latents in fp32, then one fp32 draw per step
         # (none of the step draws under ODE dynamics: the reference's ODE branch draws nothing)
-        latents = randn_tensor((B, Cl, T, h, w), generator=generator, device=device, dtype=torch.float32)
+        condition = image_embeds = None
+        sample_fields = lambda b: {}          # noqa: E731
+        if i2v is not None:          # (prepare_latents: the reference draws the latents there, before it encodes the condition)
+            latents, condition, image_embeds, sample_fields = i2v(B, T, h, w, height, width, num_frames, generator)
+        else:
+            latents = randn_tensor((B, Cl, T, h, w), generator=generator, device=device, dtype=torch.float32)
         step_noise = None
         if self.scheduler.dynamics_type != "ODE" and not eval_mode:      # (the evaluation-mode solver is deterministic: the reference draws nothing)
             step_noise = torch.empty((N, B, Cl, T, h, w), device=device, dtype=torch.float32)
             for i in range(N):
                 step_noise[i] = randn_tensor((B, Cl, T, h, w), generator=None, device=device, dtype=torch.float32)
         storage = self.latent_storage_dtype or torch.float32       # cast_latents(latents) with no default: fp32 stays fp32
-        plan = self.engine.plan(B, 2 if do_cfg else 1, T, h, w, prompt_embeds.shape[1], N)
-        plan_2 = self.engine_2.plan(B, 2 if do_cfg else 1, T, h, w, prompt_embeds.shape[1], N) if two else None
+        nimg = _n_image_kw(image_embeds)
+        plan = self.engine.plan(B, 2 if do_cfg else 1, T, h, w, prompt_embeds.shape[1], N, **nimg)
+        plan_2 = self.engine_2.plan(B, 2 if do_cfg else 1, T, h, w, prompt_embeds.shape[1], N, **nimg) if two else None
         sampler = None
         if eval_mode:
             if compute_log_prob or any(k != "noise_level" for k in extra_call_back_kwargs):
@@ -263,9 +384,18 @@ class WanRolloutMixin(RolloutMixinBase):
         elif two:
             # two experts: per-step engine calls (each step picks its expert and guidance by the boundary rule; still all-HIP)
             sampler = self._rollout_stepwise
-        traj, final = self._rollout_and_collect(plan, timesteps, N, guidance_scale, latents, storage, step_noise,
-                                                (prompt_embeds, negative_prompt_embeds if do_cfg else None), compute_log_prob,
-                                                extra_call_back_kwargs, trajectory_indices, sampler=sampler, plan_2=plan_2, guidance_2=g2)
+        elif any(k != "noise_level" for k in extra_call_back_kwargs):
+            # per-step callback tensors.  The SAME rule as `RolloutMixinBase._rollout_and_collect` applies itself (host.py: keep the two in
+            # step); it is decided here as well only because the image-to-video inputs go positionally into the fused rollout and as keywords
+            # into a sampler, so which of the two runs must be known before the call
+            sampler = self._rollout_stepwise
+        # the image-to-video inputs travel with the prompt embeddings: positionally into the fused `plan.rollout`, as keywords into a sampler
+        cond = (prompt_embeds, negative_prompt_embeds if do_cfg else None)
+        ikw = _i2v_kw(condition, image_embeds)
+        if sampler is None and ikw:
+            cond, ikw = cond + (condition, image_embeds), {}
+        traj, final = self._rollout_and_collect(plan, timesteps, N, guidance_scale, latents, storage, step_noise, cond, compute_log_prob,
+                                                extra_call_back_kwargs, trajectory_indices, sampler=sampler, plan_2=plan_2, guidance_2=g2, **ikw)
         videos = self.decode_latents(final, output_type="pt")
         return [
             self._sample_cls(
@@ -279,17 +409,19 @@ class WanRolloutMixin(RolloutMixinBase):
                 negative_prompt=negative_prompt[b] if isinstance(negative_prompt, list) else negative_prompt,
                 negative_prompt_ids=negative_prompt_ids[b] if negative_prompt_ids is not None else None,
                 negative_prompt_embeds=negative_prompt_embeds[b] if negative_prompt_embeds is not None else None,
+                **sample_fields(b),
             )
             for b in range(B)
         ]
 
     def _rollout_eval_stepwise(self, plan, ts, sig, eta, guidance, latents, storage, step_noise, pe, ne, compute_log_prob, extra_keys,
-                               plan_2=None, guidance_2=None):
+                               plan_2=None, guidance_2=None, condition=None, image_embeds=None):
         """`_rollout_eval` as a sampler of `_rollout_stepwise`'s signature: no log-probs, no per-step outputs."""
-        all_lat = self._rollout_eval(plan, ts, sig, guidance, latents, storage, pe, ne, plan_2=plan_2, guidance_2=guidance_2)
+        all_lat = self._rollout_eval(plan, ts, sig, guidance, latents, storage, pe, ne, plan_2=plan_2, guidance_2=guidance_2, condition=condition,
+                                     image_embeds=image_embeds)
         return all_lat, torch.full((len(ts), latents.shape[0]), float("nan"), device=latents.device), None
 
-    def _rollout_eval(self, plan, ts, sig, guidance, latents, storage, pe, ne, plan_2=None, guidance_2=None):
+    def _rollout_eval(self, plan, ts, sig, guidance, latents, storage, pe, ne, plan_2=None, guidance_2=None, condition=None, image_embeds=None):
         """Evaluation-mode sampling (reference: the loop of wan2_t2v.py:346-375 with `scheduler.step` in its `is_eval` branch,
         unipc_multistep.py:282-285 = diffusers' UniPC multistep predictor-corrector): one engine forward per step (per expert and guidance by
         the boundary rule, like the rollout), then the solver step on the GPU -- `mi355_unipc_convert` + `mi355_op_lincomb` with host-side
@@ -314,8 +446,8 @@ class WanRolloutMixin(RolloutMixinBase):
             pl, gd = (plan_2, guidance_2) if low else (plan, guidance)
             cfg_i = ne is not None and gd > 1.0
             if not cfg_i and pl.n_cfg == 2:
-                pl = pl.engine.plan(B, 1, pl.T, pl.h, pl.w, pl.n_text, 1)
-            v = pl.transformer_forward(cur, f32(ts[i]).reshape(1), ne if cfg_i else pe, pe if cfg_i else None)
+                pl = pl.engine.plan(B, 1, pl.T, pl.h, pl.w, pl.n_text, 1, **_n_image_kw(plan=pl))
+            v = pl.transformer_forward(cur, f32(ts[i]).reshape(1), ne if cfg_i else pe, pe if cfg_i else None, **_i2v_kw(condition, image_embeds))
             vu, vt = (v[:B], v[B:]) if cfg_i else (None, v)
             nxt = solver.step(i, vt.reshape(cur.shape), vu.reshape(cur.shape) if vu is not None else None, gd, cur)
             cur = self.cast_latents(nxt, storage)
@@ -323,7 +455,7 @@ class WanRolloutMixin(RolloutMixinBase):
         return all_lat
 
     def _rollout_stepwise(self, plan, ts, sig, eta, guidance, latents, storage, step_noise, pe, ne, compute_log_prob, extra_keys, plan_2=None,
-                          guidance_2=None):
+                          guidance_2=None, condition=None, image_embeds=None):
         """Per-step engine calls (still all-HIP) for rollouts that ask for per-step callback tensors, and for two-expert pipelines."""
         B = latents.shape[0]
 
@@ -333,8 +465,9 @@ class WanRolloutMixin(RolloutMixinBase):
             pl, gd = (plan_2, guidance_2) if low else (plan, guidance)
             cfg_i = ne is not None and gd > 1.0          # the reference decides CFG per expert (wan2_t2v.py:489-498)
             if not cfg_i and pl.n_cfg == 2:
-                pl = pl.engine.plan(B, 1, pl.T, pl.h, pl.w, pl.n_text, 1)
-            v = pl.transformer_forward(cur, torch.tensor(float(ts[i]), dtype=torch.float32).reshape(1), ne if cfg_i else pe, pe if cfg_i else None)
+                pl = pl.engine.plan(B, 1, pl.T, pl.h, pl.w, pl.n_text, 1, **_n_image_kw(plan=pl))
+            v = pl.transformer_forward(cur, torch.tensor(float(ts[i]), dtype=torch.float32).reshape(1), ne if cfg_i else pe, pe if cfg_i else None,
+                                       **_i2v_kw(condition, image_embeds))
             return (v[B:], v[:B], gd) if cfg_i else (v, None, gd)
 
         return self._stepwise(ts, sig, eta, latents, storage, step_noise, compute_log_prob, extra_keys, predict)
@@ -377,7 +510,8 @@ class WanRolloutMixin(RolloutMixinBase):
                                      _sync_weights=getattr(self, "_sync_weights", None))
 
     def _forward_impl(self, t, latents, prompt_embeds, negative_prompt_embeds, guidance_scale, guidance_scale_2, t_next, next_latents, noise_level,
-                      attention_kwargs, compute_log_prob, return_kwargs, boundary_timestep, grad: bool, host=None) -> SDESchedulerOutput:
+                      attention_kwargs, compute_log_prob, return_kwargs, boundary_timestep, grad: bool, host=None, condition=None,
+                      image_embeds=None) -> SDESchedulerOutput:
         self._before_engine_call()
         if attention_kwargs:
             raise NotImplementedError("mi355_flow: attention_kwargs are not supported by the native engine")
@@ -391,8 +525,9 @@ class WanRolloutMixin(RolloutMixinBase):
             t_next = torch.as_tensor(t_next, device=dev, dtype=torch.float32).reshape(-1)[0]
         eng, guidance_scale = self._expert(float(t0), guidance_scale, guidance_scale_2, boundary_timestep)
         do_cfg = negative_prompt_embeds is not None and guidance_scale > 1.0
-        plan = eng.plan(B, 2 if do_cfg else 1, T, h, w, prompt_embeds.shape[1], 1)
+        plan = eng.plan(B, 2 if do_cfg else 1, T, h, w, prompt_embeds.shape[1], 1, **_n_image_kw(image_embeds))
         enc_a, enc_b = (negative_prompt_embeds, prompt_embeds) if do_cfg else (prompt_embeds, None)
+        extra = (condition, image_embeds) if condition is not None or image_embeds is not None else ()
         sched = self.scheduler
         if noise_level is None and not (sched.is_eval or sched.dynamics_type == "ODE"):
             noise_level = sched.get_noise_level_for_timestep(float(t0))          # Wan's schedulers look the level up by timestep
@@ -400,10 +535,135 @@ class WanRolloutMixin(RolloutMixinBase):
             from .autograd import wan_replay
             return self._scheduler_step(t0, latents, t_next, next_latents, noise_level, compute_log_prob, return_kwargs, replay=(
                 wan_replay, host if host is not None else self, plan,
-                dict(train_args=(latents, t0.reshape(1), enc_a, enc_b), cfg_guidance=float(guidance_scale) if do_cfg else None)))
-        v = plan.transformer_forward(latents, t0.reshape(1), enc_a, enc_b)
+                dict(train_args=(latents, t0.reshape(1), enc_a, enc_b) + extra, cfg_guidance=float(guidance_scale) if do_cfg else None)))
+        v = plan.transformer_forward(latents, t0.reshape(1), enc_a, enc_b, **_i2v_kw(condition, image_embeds))
         return self._scheduler_step(t0, latents, t_next, next_latents, noise_level, compute_log_prob, return_kwargs,
                                     v=(v[B:], v[:B], guidance_scale) if do_cfg else (v, None, guidance_scale))
+
+
+def wan_i2v_condition(latent_condition: torch.Tensor, num_frames: int, vae_scale_temporal: int = VAE_SCALE_TEMPORAL,
+                      last_frame: bool = False) -> torch.Tensor:
+    """The transformer-side condition of the I2V pipelines from the normalised VAE latents of the conditioning clip (first frame [+ last
+    frame], zeros between): `cat([mask (vae_scale_temporal), latent_condition], 1)` -- the mask arithmetic of the reference's
+    `prepare_latents` (wan2_i2v.py:409-422).  The pixel-frame mask (1 on the given frames) has its first frame repeated `vae_scale_temporal`
+    times, so that `num_frames + vae_scale_temporal - 1` frames fold into T latent frames of `vae_scale_temporal` mask channels."""
+    B, _, T, h, w = latent_condition.shape
+    mask = torch.ones(B, 1, num_frames, h, w)
+    if last_frame:
+        mask[:, :, 1:-1] = 0
+    else:
+        mask[:, :, 1:] = 0
+    first = torch.repeat_interleave(mask[:, :, 0:1], dim=2, repeats=vae_scale_temporal)
+    mask = torch.concat([first, mask[:, :, 1:]], dim=2)
+    if mask.shape[2] != T * vae_scale_temporal:
+        raise ValueError(f"mi355_flow: {num_frames} frames do not fold into {T} latent frames at temporal scale {vae_scale_temporal}")
+    mask = mask.view(B, -1, vae_scale_temporal, h, w).transpose(1, 2).to(latent_condition.device)
+    return torch.concat([mask, latent_condition], dim=1)
+
+
+class WanI2VRolloutMixin(WanRolloutMixin):
+    """`inference()` / `forward()` of `Wan2_I2V_Adapter` (reference models/wan/wan2_i2v.py:425-652, :656-783) on an image-to-video engine
+    (`WanConfig.cond_channels > 0`): the T2V loop whose transformer input is `cat([latents, condition], 1)`.  `condition` (and, once the image
+    branch exists natively, `image_embeds`) travel with the prompt embeddings through the fused rollout, the step-wise and evaluation-mode
+    loops, the replay and its native backward; the two-expert rule and the per-expert CFG are inherited (Wan2.2-I2V-A14B).
+    `image_embeds` (B, Ni, image_dim) drive the image cross-attention branch of a Wan2.1-I2V engine (`WanConfig.image_dim`).
+    Refused: `expand_timesteps` pipelines (Wan2.2-TI2V-5B in I2V use: one timestep per token, wan2_i2v.py:736-741 -- the engine's modulation
+    is per sample) and `first_frame_mask`."""
+
+    _sample_cls = WanI2VSample
+    expand_timesteps = False
+
+    def _refuse_expand_timesteps(self, first_frame_mask=None) -> None:
+        if self.expand_timesteps or first_frame_mask is not None:
+            raise NotImplementedError("mi355_flow: `expand_timesteps` image-to-video pipelines (Wan2.2-TI2V-5B) pass one timestep per token "
+                                      "(first_frame_mask * t); the native engine modulates per sample")
+
+    def _prepare_i2v(self, images, last_image, image_embeds, B, T, h, w, height, width, num_frames, generator):
+        """-> (fp32 latents, condition, image_embeds, condition_images) from raw images: needs a VAE encoder (and CLIP for Wan2.1-I2V).
+        Hook of the host class; standalone there is neither."""
+        raise NotImplementedError("mi355_flow: the native Wan I2V adapter has no VAE encoder / CLIP image encoder: pass `condition=` "
+                                  "(wan_i2v_condition of the normalised first-frame latents) instead of `images`")
+
+    @torch.no_grad()
+    def inference(
+        self,
+        images: Any = None,
+        prompt: Optional[Union[str, List[str]]] = None,
+        negative_prompt: Optional[Union[str, List[str]]] = None,
+        height: int = 480,
+        width: int = 832,
+        num_frames: int = 81,
+        num_inference_steps: int = 50,
+        guidance_scale: float = 5.0,
+        guidance_scale_2: Optional[float] = None,
+        generator: Optional[torch.Generator] = None,
+        prompt_ids: Optional[torch.Tensor] = None,
+        prompt_embeds: Optional[torch.Tensor] = None,
+        negative_prompt_ids: Optional[torch.Tensor] = None,
+        negative_prompt_embeds: Optional[torch.Tensor] = None,
+        image_embeds: Optional[torch.Tensor] = None,
+        condition_images: Optional[Any] = None,
+        last_image: Optional[torch.Tensor] = None,
+        compute_log_prob: bool = False,
+        attention_kwargs: Optional[Dict[str, Any]] = None,
+        max_sequence_length: int = 512,
+        extra_call_back_kwargs: List[str] = [],
+        trajectory_indices: TrajectoryIndicesType = "all",
+        condition: Optional[torch.Tensor] = None,
+    ) -> List[WanI2VSample]:
+        """The reference's signature plus `condition=` (B, 20, T, h, w): given, nothing is encoded (the standalone adapter's only way)."""
+        self._refuse_expand_timesteps()
+        eval_mode = bool(getattr(self.scheduler, "is_eval", False))
+        device = self.device
+
+        def i2v(B, T, h, w, height_, width_, frames, gen):
+            if condition is None:
+                return self._prepare_i2v(images, last_image, image_embeds, B, T, h, w, height_, width_, frames, gen)
+            # RNG in the reference's order: prepare_latents draws the fp32 latents first (then one fp32 draw per SDE step)
+            lat = randn_tensor((B, self.engine.cfg.in_channels, T, h, w), generator=gen, device=device, dtype=torch.float32)
+            cond = condition.to(device)
+            emb = image_embeds.to(device=device, dtype=self.transformer_dtype) if image_embeds is not None else None
+            want = (B, self.engine.cfg.cond_channels, T, h, w)
+            if tuple(cond.shape) != want:
+                raise ValueError(f"mi355_flow: condition has shape {tuple(cond.shape)}, expected {want}")
+            imgs = condition_images if condition_images is not None else images
+            return lat, cond, emb, lambda b: dict(condition=cond[b], image_embeds=emb[b] if emb is not None else None, first_frame_mask=None,
+                                                  condition_images=imgs[b] if imgs is not None else None)
+
+        return self._wan_inference(prompt, negative_prompt, height, width, num_frames, num_inference_steps, guidance_scale, guidance_scale_2, generator,
+                                   prompt_ids, prompt_embeds, negative_prompt_ids, negative_prompt_embeds, compute_log_prob, attention_kwargs,
+                                   extra_call_back_kwargs, trajectory_indices, eval_mode, i2v=i2v)
+
+    def forward(
+        self,
+        t: torch.Tensor,
+        latents: torch.Tensor,
+        prompt_embeds: torch.Tensor,
+        negative_prompt_embeds: Optional[torch.Tensor] = None,
+        guidance_scale: float = 5.0,
+        guidance_scale_2: Optional[float] = None,
+        image_embeds: Optional[torch.Tensor] = None,
+        condition: Optional[torch.Tensor] = None,
+        first_frame_mask: Optional[torch.Tensor] = None,
+        boundary_timestep: Optional[float] = None,
+        t_next: Optional[torch.Tensor] = None,
+        next_latents: Optional[torch.Tensor] = None,
+        noise_level: Optional[float] = None,
+        attention_kwargs: Optional[Dict[str, Any]] = None,
+        compute_log_prob: bool = True,
+        return_kwargs: List[str] = ["noise_pred", "next_latents", "next_latents_mean", "std_dev_t", "dt", "log_prob"],
+    ) -> SDESchedulerOutput:
+        self._refuse_expand_timesteps(first_frame_mask)
+        if condition is None:
+            raise ValueError("mi355_flow: Wan I2V forward() needs `condition`")
+        kw = dict(t=t, latents=latents, prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds, guidance_scale=guidance_scale,
+                  guidance_scale_2=guidance_scale_2, t_next=t_next, next_latents=next_latents, noise_level=noise_level,
+                  attention_kwargs=attention_kwargs, compute_log_prob=compute_log_prob, return_kwargs=return_kwargs, boundary_timestep=boundary_timestep,
+                  condition=condition.to(latents.device), image_embeds=image_embeds)
+        if not WanEngine.native_backward_enabled:
+            return self._forward_nograd(**kw)
+        return self._forward_dispatch(kw, replay_host=lambda: self._replay_host(self._expert(
+            float(torch.as_tensor(t, dtype=torch.float32).reshape(-1)[0]), guidance_scale, guidance_scale_2, boundary_timestep)[0]))
 
 
 class Wan2T2VNativeAdapter(StandaloneAdapterBase, WanRolloutMixin):
@@ -441,3 +701,17 @@ class Wan2T2VNativeAdapter(StandaloneAdapterBase, WanRolloutMixin):
             vid = self.vae_decoder.decode(latents, postprocess=True, out_dtype=torch.float32, max_batch=self.vae_max_batch)
             return vid if output_type == "pt" else vid.permute(0, 1, 3, 4, 2).cpu().numpy()
         return self._video_decode(latents) if self._video_decode is not None else None
+
+
+class Wan2I2VNativeAdapter(WanI2VRolloutMixin, Wan2T2VNativeAdapter):
+    """Standalone Wan image-to-video adapter (no Flow-Factory import): `Wan2T2VNativeAdapter` on image-to-video engine(s) -- Wan2.2-I2V-A14B
+    with `state_dict_2` / `boundary_ratio`.  `config` carries `cond_channels` (`WanConfig.from_hf` of the transformer's config).  There is no
+    VAE encoder and no CLIP here: `inference(condition=..., prompt_embeds=...)` takes the condition ready-made (`wan_i2v_condition`)."""
+
+    def __init__(self, state_dict: Dict[str, torch.Tensor], config: Optional[WanConfig] = None, *args, expand_timesteps: bool = False, **kw):
+        config = config or WanConfig(cond_channels=20)
+        if not config.cond_channels:
+            raise ValueError("mi355_flow: Wan2I2VNativeAdapter needs an image-to-video config (WanConfig.cond_channels > 0)")
+        self.expand_timesteps = bool(expand_timesteps)
+        self._refuse_expand_timesteps()
+        super().__init__(state_dict, config, *args, **kw)

@@ -207,12 +207,20 @@ def expected_wan_shapes(cfg) -> Dict[str, Tuple[int, ...]]:
     def lin(n, o, i):
         out[n + ".weight"], out[n + ".bias"] = (o, i), (o,)
 
-    out["patch_embedding.weight"], out["patch_embedding.bias"] = (D, cfg.in_channels) + tuple(cfg.patch_size), (D,)
+    # (image-to-video: the patch embedding sees the latent channels and the condition channels)
+    out["patch_embedding.weight"], out["patch_embedding.bias"] = (D, cfg.in_channels + getattr(cfg, "cond_channels", 0)) + tuple(cfg.patch_size), (D,)
     lin("condition_embedder.time_embedder.linear_1", D, cfg.freq_dim)
     lin("condition_embedder.time_embedder.linear_2", D, D)
     lin("condition_embedder.time_proj", 6 * D, D)
     lin("condition_embedder.text_embedder.linear_1", D, cfg.text_dim)
     lin("condition_embedder.text_embedder.linear_2", D, D)
+    Di = getattr(cfg, "image_dim", None) or 0          # Wan2.1-I2V: the image embedder and every block's image key / value projections
+    if Di:
+        ie = "condition_embedder.image_embedder."
+        out[ie + "norm1.weight"], out[ie + "norm1.bias"] = (Di,), (Di,)
+        lin(ie + "ff.net.0.proj", Di, Di)
+        lin(ie + "ff.net.2", D, Di)
+        out[ie + "norm2.weight"], out[ie + "norm2.bias"] = (D,), (D,)
     for i in range(cfg.num_layers):
         b = f"blocks.{i}"
         out[f"{b}.scale_shift_table"] = (1, 6, D)
@@ -224,6 +232,10 @@ def expected_wan_shapes(cfg) -> Dict[str, Tuple[int, ...]]:
         out[f"{b}.norm2.weight"], out[f"{b}.norm2.bias"] = (D,), (D,)
         lin(f"{b}.ffn.net.0.proj", cfg.ffn_dim, D)
         lin(f"{b}.ffn.net.2", D, cfg.ffn_dim)
+        if Di:
+            lin(f"{b}.attn2.add_k_proj", D, D)
+            lin(f"{b}.attn2.add_v_proj", D, D)
+            out[f"{b}.attn2.norm_added_k.weight"] = (D,)
     out["scale_shift_table"] = (1, 2, D)
     lin("proj_out", cfg.out_channels * math.prod(cfg.patch_size), D)
     return out
@@ -234,7 +246,7 @@ def synthetic_wan_state_dict(cfg, device="cuda", seed: int = 1357, std: float = 
     sd = {}
     for name, shape in expected_wan_shapes(cfg).items():
         t = torch.randn(shape, generator=g, device=device, dtype=torch.float32) * std
-        if ".norm_q." in name or ".norm_k." in name or name.endswith("norm2.weight"):
+        if ".norm_q." in name or ".norm_k." in name or ".norm_added_k." in name or name.endswith(("norm2.weight", "norm1.weight")):
             t = t + 1.0
         if "scale_shift_table" in name:
             t = t * (0.3 / std)
@@ -246,7 +258,7 @@ def wan_forward_flops(cfg, S: int, Nt: int) -> float:
     """Algorithmic matmul FLOPs of one Wan forward for one sample (2 FLOP/MAC; conditioning MLPs excluded)."""
     D, Fd = cfg.dim, cfg.ffn_dim
     per_layer = S * (4 * D * D) + 2 * S * S * D + S * 2 * D * D + Nt * 2 * D * D + 2 * S * Nt * D + S * 2 * D * Fd
-    emb = S * cfg.in_channels * 4 * D + S * D * cfg.out_channels * 4 + Nt * cfg.text_dim * D + Nt * D * D
+    emb = S * (cfg.in_channels + getattr(cfg, "cond_channels", 0)) * 4 * D + S * D * cfg.out_channels * 4 + Nt * cfg.text_dim * D + Nt * D * D
     return 2.0 * (cfg.num_layers * per_layer + emb)
 
 

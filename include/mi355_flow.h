@@ -456,6 +456,33 @@ int mi355_wan_rollout(mi355_wan_plan* plan, void* stream, int n_steps, const flo
                       int storage_dtype, const float* step_noise, const void* prompt_embeds, const void* neg_embeds,
                       const int32_t* keep_slot_host, void* out_latents, float* out_log_probs, void* out_final, int compute_log_prob);
 
+/* ---- Wan image-to-video: condition channels (Wan2.2-I2V-A14B) and CLIP image keys (Wan2.1-I2V) -------------------------------------
+ * Replaces the same passes inside Wan2_I2V_Adapter.inference / .forward (reference models/wan/wan2_i2v.py:425-652, :656-783), whose transformer
+ * input is cat([latents (16), condition (4 mask + 16 latent)], dim = 1): patch_embedding is Conv3d(in_channels + cond_channels, D), proj_out still
+ * emits out_channels.  cfg->in_channels stays the LATENT channel count; patch_embedding.weight binds as (D, in_channels + cond_channels, 1, 2, 2).
+ * image_dim: width of the CLIP image embeddings of Wan2.1-I2V's image cross-attention branch (1280; a multiple of 64), 0 = no branch.  With it
+ * the engine also lists condition_embedder.image_embedder.{norm1,norm2}.{weight,bias}, .ff.net.0.proj / .ff.net.2 and per block
+ * attn2.{add_k_proj,add_v_proj}.{weight,bias}, attn2.norm_added_k.weight (all frozen: mi355_wan_grad_supported reports 1); the image
+ * embedder's pos_embed (first-and-last-frame checkpoints) is refused by mi355_wan_bind_weight.  A plan created with n_image > 0 (CLIP tokens
+ * per sample, 257) needs image_embeds [batch][n_image][image_dim] bf16 in every call; a plan with n_image == 0 refuses them.  The condition
+ * [batch][cond_channels][T][h][w] (cond_dtype: MI355_F32 / BF16 / F16) and the image embeddings are step-invariant: patchified / embedded and
+ * projected to every block's image K / V^T once per call, both CFG halves read them, no gradient flows to them.  Per block the image
+ * cross-attention runs the text cross-attention's queries over the image keys and attn2.to_out.0 reads bf16(bf16(o_text) + bf16(o_img)).  A plan
+ * of an image-to-video engine is created by mi355_wan_plan_create_i2v and served by the _i2v entry points only (and a text-to-video plan by
+ * the plain ones only: the other kind returns an error and runs nothing); mi355_wan_backward, the set_grad family and the destructors serve both. */
+int mi355_wan_create_i2v(const mi355_wan_cfg* cfg, int cond_channels, int image_dim, mi355_wan** out);
+int mi355_wan_plan_create_i2v(mi355_wan* e, int batch, int n_cfg, int latent_t, int latent_h, int latent_w, int n_text, int n_image,
+                              int max_steps, mi355_wan_plan** out);
+int mi355_wan_forward_i2v(mi355_wan_plan* plan, void* stream, const void* latents, int lat_dtype, const float* t, const void* enc_a,
+                          const void* enc_b, const void* condition, int cond_dtype, const void* image_embeds, void* v_out);
+int mi355_wan_rollout_i2v(mi355_wan_plan* plan, void* stream, int n_steps, const float* timesteps_host, const float* sigmas_host,
+                          const float* noise_levels_host, int dynamics, float guidance, const void* init_latents, int init_dtype,
+                          int storage_dtype, const float* step_noise, const void* prompt_embeds, const void* neg_embeds,
+                          const int32_t* keep_slot_host, void* out_latents, float* out_log_probs, void* out_final, int compute_log_prob,
+                          const void* condition, int cond_dtype, const void* image_embeds);
+int mi355_wan_forward_train_i2v(mi355_wan_plan* plan, void* stream, const void* latents, int lat_dtype, const float* t, const void* enc_a,
+                                const void* enc_b, const void* condition, int cond_dtype, const void* image_embeds, void* v_out);
+
 /* ---- Wan2.1 / Wan2.2 T2V `optimize()` replay with gradients (SURVEY.md 8(f) N1 over N4) ----------------------------------------
  * Replaces the grad-mode `Wan2_T2V_Adapter.forward(...)` + `accelerator.backward(loss)` (trainers/grpo.py:263, :326-330 over
  * models/wan/wan2_t2v.py:426-543).  Same contract as mi355_flux_forward_train / _backward: the training-mode forward is mi355_wan_forward's own
