@@ -42,11 +42,15 @@ __device__ __forceinline__ float gelu_tanh_f(float x) {
 }
 
 // d/dx of gelu_tanh_f: s + x s (1 - s) 2u'(x), s = sigmoid(2u), 2u = x (k0 + k1 x^2), (2u)' = k0 + 3 k1 x^2
+// The guard-free and the guarded EPI_DGELU epilogues of gemm.hip are different instantiations and must agree bit for bit whichever kernel a grid
+// selects: every multiply-add is an explicit fma and contraction is off, so that hipcc cannot fuse in one of them what it leaves unfused in the
+// other (tests/test_gpu_gemm_epilogues.py found the ping-pong kernel's dpre an ulp off the 128x128 kernel's; the q/k epilogue has the same rule).
 __device__ __forceinline__ float gelu_tanh_grad_f(float x) {
+#pragma clang fp contract(off)
     const float k0 = 2.0f * 0.7978845608028654f, k1 = k0 * 0.044715f;
     const float x2 = x * x;
-    const float s = fast_rcp(1.0f + __expf(-x * (k0 + k1 * x2)));
-    return s + x * s * (1.0f - s) * (k0 + 3.0f * k1 * x2);
+    const float s = fast_rcp(1.0f + __expf(-x * __builtin_fmaf(k1, x2, k0)));
+    return __builtin_fmaf(x * s * (1.0f - s), __builtin_fmaf(3.0f * k1, x2, k0), s);
 }
 
 __device__ __forceinline__ float wave_sum(float v) {

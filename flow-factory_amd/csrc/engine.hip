@@ -1059,6 +1059,80 @@ extern "C" int mi355_op_linear_gate_res(void* stream, const void* A, const void*
     return 0;
 }
 
+// Every fused epilogue of launch_epi as an operator (tests/test_gpu_gemm_epilogues.py): fills a GemmParams from plain arguments and calls
+// launch_gemm, nothing else.  Every argument is checked before any HIP call; the message names the operator and the argument.
+extern "C" int mi355_op_gemm_epi(void* stream, const void* A, int64_t lda, const void* W, int64_t ldw, int M, int N, int K, int epi, const float* bias,
+                                 void* out, int64_t ldo, const void* aux, int64_t ld_aux, int rows_per_sample, void* q, void* k, const float* nw_q,
+                                 const float* nw_k, int H, int S_pad, int s_off, float eps, int hd_shift, float q_scale, int hp, int wp, int patch,
+                                 int out_ch, void* stash, int64_t ld_stash, float* rstd_out) {
+#define GE_FAIL(...) return errorf("mi355_op_gemm_epi: " __VA_ARGS__)
+    static_assert(EPI_GATE_RES == 5 && EPI_UNPATCH == 8 && EPI_DGELU == 12, "the MI355_EPI_* values of include/mi355_flow.h are GemmEpi's");
+    const bool is_qk = epi == EPI_QK_NORM, is_vt = epi == EPI_VT, is_unp = epi == EPI_UNPATCH;
+    const bool uses_aux = epi == EPI_POSADD || epi == EPI_ADDSRC_SILU || epi == EPI_GATE_RES || epi == EPI_DGELU;
+    const bool uses_out = !is_qk && !is_vt;
+    auto misaligned = [](const void* p) { return ((uintptr_t)p & 15) != 0; };
+    if (!(epi == EPI_BIAS || epi == EPI_BIAS_SILU || epi == EPI_BIAS_GELU || uses_aux || is_qk || is_vt || is_unp))
+        GE_FAIL("epi = %d is not one of the fused epilogues of launch_epi (the convolution / VAE kinds have their own operators)", epi);
+    if (!A || !W || !bias) GE_FAIL("null argument (A, W, bias)");
+    if (M <= 0 || N <= 0 || K <= 0) GE_FAIL("bad shape M = %d, N = %d, K = %d", M, N, K);
+    if (K % 64) GE_FAIL("K = %d is not a multiple of 64", K);
+    if (N % 4) GE_FAIL("N = %d is not a multiple of 4 (the bias is read four columns at a time)", N);
+    if (lda % 8 || lda < K) GE_FAIL("lda = %lld must be a multiple of 8 and at least K", (long long)lda);
+    if (ldw % 8 || ldw < K) GE_FAIL("ldw = %lld must be a multiple of 8 and at least K", (long long)ldw);
+    if (misaligned(A) || misaligned(W)) GE_FAIL("A and W must be 16-byte aligned");
+    if (rows_per_sample < 1) GE_FAIL("rows_per_sample %d is below 1", rows_per_sample);
+    if (uses_out) {
+        if (!out) GE_FAIL("null argument (out)");
+        if (!is_unp && ldo < N) GE_FAIL("ldo = %lld is below N", (long long)ldo);
+        if (!is_unp && ldo % 8 == 0 && misaligned(out)) GE_FAIL("out must be 16-byte aligned when ldo is a multiple of 8");
+    }
+    if (uses_aux) {
+        if (!aux) GE_FAIL("null argument (aux)");
+        if (ld_aux % 8 || ld_aux < N || misaligned(aux)) GE_FAIL("ld_aux = %lld must be a multiple of 8 and at least N, aux 16-byte aligned", (long long)ld_aux);
+    }
+    if (epi == EPI_GATE_RES && N % 8) GE_FAIL("N = %d is not a multiple of 8 (gated residual)", N);
+    if (stash) {
+        if (epi != EPI_BIAS_GELU && epi != EPI_GATE_RES) GE_FAIL("stash is written by the GELU and the gated-residual epilogues only");
+        if (ld_stash < N) GE_FAIL("ld_stash = %lld is below N", (long long)ld_stash);
+        if (ld_stash % 8 == 0 && misaligned(stash)) GE_FAIL("stash must be 16-byte aligned when ld_stash is a multiple of 8");
+    }
+    if (rstd_out && !is_qk) GE_FAIL("rstd_out is written by the q/k-norm epilogue only");
+    if (is_qk || is_vt) {
+        if (H < 1) GE_FAIL("H = %d is below 1", H);
+        if (s_off < 0 || (long)S_pad < (long)s_off + rows_per_sample)
+            GE_FAIL("S_pad = %d is below s_off + rows_per_sample = %d + %d", S_pad, s_off, rows_per_sample);
+    }
+    if (is_qk) {
+        if (!q || !k || !nw_q || !nw_k) GE_FAIL("null argument (q, k, nw_q, nw_k)");
+        if (misaligned(q) || misaligned(k) || misaligned(nw_q) || misaligned(nw_k)) GE_FAIL("q, k, nw_q, nw_k must be 16-byte aligned");
+        if ((long)N != 2L * H * 64) GE_FAIL("N = %d is not 2 * H * 64 = %ld (q | k, head_dim 64)", N, 2L * H * 64);
+    }
+    if (is_vt) {
+        if (!q) GE_FAIL("null argument (q = vT)");
+        if (hd_shift != 0 && hd_shift != 6 && hd_shift != 7) GE_FAIL("hd_shift = %d: 0 or 6 (head_dim 64) or 7 (head_dim 128)", hd_shift);
+        const int hs = hd_shift ? hd_shift : 6;
+        if ((long)M != ((long)H << hs)) GE_FAIL("M = %d is not H << hd = %ld (rows are the features)", M, (long)H << hs);
+        if (S_pad % 8 || misaligned(q)) GE_FAIL("S_pad = %d must be a multiple of 8 and vT 16-byte aligned", S_pad);
+    }
+    if (is_unp) {
+        if (hp < 1 || wp < 1 || patch < 1 || out_ch < 1) GE_FAIL("bad shape hp = %d, wp = %d, patch = %d, out_ch = %d", hp, wp, patch, out_ch);
+        if (M % (hp * wp)) GE_FAIL("M = %d is not a multiple of hp * wp = %d", M, hp * wp);
+        if (N != patch * patch * out_ch) GE_FAIL("N = %d is not patch * patch * out_ch = %d", N, patch * patch * out_ch);
+    }
+#undef GE_FAIL
+    GemmParams g = gp((const bf16_t*)A, (long)lda, (const bf16_t*)W, (long)ldw, M, N, K, epi, bias, (bf16_t*)out, (long)ldo);
+    g.aux = (const bf16_t*)aux; g.ld_aux = (long)ld_aux; g.rows_per_sample = rows_per_sample;
+    g.q = (bf16_t*)q; g.k = (bf16_t*)k; g.nw_q = nw_q; g.nw_k = nw_k; g.H = H; g.S_pad = S_pad; g.s_off = s_off; g.eps = eps;
+    g.hd_shift = hd_shift; g.q_scale = q_scale;
+    g.hp = hp; g.wp = wp; g.patch = patch; g.out_ch = out_ch;
+    g.stash = (bf16_t*)stash; g.ld_stash = (long)ld_stash; g.rstd_out = rstd_out;
+    HIPCHK(launch_gemm(g, (hipStream_t)stream));
+    return 0;
+}
+
+// the kernel family the calling thread's last GEMM launch went to (GemmKernelId of kernels.h; MI355_GEMM_* of the public header)
+extern "C" int mi355_gemm_last_kernel(void) { return gemm_last_kernel(); }
+
 // weight-gradient product as an operator (unit tests / A/B scripts): variant 1 = gemm_tn.hip on the row-major operands, variant 0 = the
 // transposed-copy path (launch_transpose x 2 + the K-contiguous EPI_F32 GEMM).  Output: k_split fp32 partial slabs [N][K].
 extern "C" int mi355_op_wgrad(void* stream, const void* dY, int64_t ld_dy, const void* X, int64_t ld_x, float* out, int M, int N, int K, int k_split,

@@ -25,6 +25,7 @@ constexpr bool is_qk_epi(int e) { return e == EPI_QK_NORM || e == EPI_QK_NORM_RS
 
 
 constexpr int BK = 64;
+thread_local int g_last_kernel = GEMM_KERNEL_NONE;      // family of this thread's last launch (gemm_last_kernel(): the operator tests assert the dispatch)
 int g_raster_gm = 6;          // tile rows per raster band (0 = plain row-major order); mi355_tune_set(7, v)
 int g_pp_min_tiles = 128;     // smallest 256x256-tile grid for gemm_pp_kernel
 int g_w4_min_tiles = 512;     // smallest 256x256-tile grid the DEFAULT dispatch (key 0 = 1) gives to the 4-wave kernel; mi355_tune_set(31, v)
@@ -756,6 +757,7 @@ hipError_t launch_mid(const GemmParams& p, hipStream_t stream) {
         attr_set = true;
     }
     const int ntm = (p.M + BM - 1) / BM, ntn = (p.N + BN - 1) / BN;
+    g_last_kernel = MI == 4 ? GEMM_KERNEL_MID_128x192 : GEMM_KERNEL_MID_192x128;
     hipLaunchKernelGGL(kern, dim3(ntm * ntn), dim3(256), smem, stream, p);
     return hipGetLastError();
 }
@@ -1022,6 +1024,7 @@ hipError_t launch_pp(const GemmParams& p, hipStream_t stream) {
     int grid = ntm * ntn;
     if (grid > 256) grid = 256;            // one 512-thread workgroup (128 KiB LDS) per CU, persistent
     grid = (grid + 7) / 8 * 8;             // whole XCD rounds (surplus workgroups exit at once)
+    g_last_kernel = GEMM_KERNEL_PP;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), smem, stream, p);
     return hipGetLastError();
 }
@@ -1167,6 +1170,7 @@ hipError_t launch_w4(const GemmParams& p, hipStream_t stream) {
     int grid = (p.M / 256) * (p.N / 256);
     if (grid > 256) grid = 256;
     grid = (grid + 7) / 8 * 8;
+    g_last_kernel = GEMM_KERNEL_W4;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, stream, p);
     return hipGetLastError();
 }
@@ -1300,6 +1304,7 @@ hipError_t launch_w6(const GemmParams& p, hipStream_t stream) {
     int grid = (p.M / 256) * (p.N / 192);
     if (grid > 256) grid = 256;
     grid = (grid + 7) / 8 * 8;
+    g_last_kernel = GEMM_KERNEL_W6;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, stream, p);
     return hipGetLastError();
 }
@@ -1322,6 +1327,7 @@ hipError_t launch_cfg(const GemmParams& p, hipStream_t stream) {
     }
     const int ntm = (p.M + BM - 1) / BM, ntn = (p.N + BN - 1) / BN;
     const int nsplit = (EPI == EPI_F32 && p.k_split > 1) ? p.k_split : 1;
+    g_last_kernel = (BM == 128 && BN == 128) ? GEMM_KERNEL_SIMPLE_128 : (BM == 256 && BN == 256) ? GEMM_KERNEL_SIMPLE_256 : GEMM_KERNEL_SIMPLE_OTHER;
     hipLaunchKernelGGL(kern, dim3(ntm * ntn * nsplit), dim3(C::NT), smem, stream, p);
     return hipGetLastError();
 }
@@ -1332,8 +1338,13 @@ hipError_t launch_epi(const GemmParams& p, hipStream_t stream) {
     // else 128x128 tiles with 2 workgroups per CU (a 128x256 ping-pong variant for mid-size grids measured slower than
     // this on every text-stream / small-batch shape: profiles/r01_gemm_variants.txt)
     const long big = (long)((p.M + 255) / 256) * ((p.N + 255) / 256);
+    // The q / k scatter has no column guard (a head is one whole 64-column chunk of one wave, and the epilogue sits at its register limit in the
+    // ping-pong kernel): a 256-wide tile that ends 128 columns behind N = 128 H (odd H) would normalise and scatter two heads that do not exist --
+    // into the next sample's rows, and behind the buffers for the last sample (found by tests/test_gpu_gemm_epilogues.py; no shipped model has
+    // an odd H).  Such a grid never goes to a kernel with 256-wide tiles; the 128x128 kernel's tiles N always fills.
+    const bool n256_ok = !is_qk_epi(EPI) || p.N % 256 == 0;
     if (g_gemm_variant == 0) {
-        if (big >= 200 && EPI != EPI_UNPATCH) return launch_cfg<256, 256, 2, 4, EPI>(p, stream);
+        if (big >= 200 && EPI != EPI_UNPATCH && n256_ok) return launch_cfg<256, 256, 2, 4, EPI>(p, stream);
         return launch_cfg<128, 128, 2, 2, EPI>(p, stream);
     }
     // the ping-pong kernel addresses its operands with 32-bit byte offsets from the base pointers
@@ -1387,7 +1398,7 @@ hipError_t launch_epi(const GemmParams& p, hipStream_t stream) {
             }
             return launch_w4<EPI>(p, stream);
         }
-        if (big >= g_pp_min_tiles && fits32 && cost_pp <= cost_128) {
+        if (big >= g_pp_min_tiles && fits32 && cost_pp <= cost_128 && n256_ok) {
             if constexpr (EPI == EPI_BIAS) {      // ablation builds (scripts/gemm_ablate.py)
                 switch (p.dbg_skip_prefetch) {
                     case 0: break;
@@ -1403,7 +1414,7 @@ hipError_t launch_epi(const GemmParams& p, hipStream_t stream) {
             }
             return launch_pp<EPI>(p, stream);
         }
-        if (big >= 200 && !fits32) return launch_cfg<256, 256, 2, 4, EPI>(p, stream);    // > 4 GiB operand (FLUX modulation table)
+        if (big >= 200 && !fits32 && n256_ok) return launch_cfg<256, 256, 2, 4, EPI>(p, stream);    // > 4 GiB operand (FLUX modulation table)
     }
     return launch_cfg<128, 128, 2, 2, EPI>(p, stream);
 }
@@ -1427,6 +1438,7 @@ hipError_t launch_simple(const GemmParams& p, hipStream_t stream) {
 
 }  // namespace
 
+int gemm_last_kernel() { return g_last_kernel; }
 void set_conv_cfg(int v) { g_conv_cfg = v; }
 void set_gemm_variant(int v) { g_gemm_variant = v; }
 void set_w4_max_k(int v) { g_w4_max_k = v; }
@@ -1495,6 +1507,7 @@ hipError_t launch_gemm(const GemmParams& p_in, hipStream_t stream) {
     p.raster_gm = g_raster_gm;
     if (sched_trace_on()) trace_gemm(p, stream);
     if (p.K % BK != 0 || p.M <= 0 || p.N <= 0) return hipErrorInvalidValue;
+    if (p.epi == EPI_QK_NORM && (p.H < 1 || p.N != 2 * p.H * 64)) return hipErrorInvalidValue;      // q | k, whole heads: the scatter relies on it
     if (p.conv_cin > 0) {
         const int ks = p.conv_ks ? p.conv_ks : 3, kt3 = p.conv_kt ? p.conv_kt : 1;
         if (p.conv_cin % BK != 0 || p.K != kt3 * ks * ks * p.conv_cin || !p.zero_page || p.M % (p.conv_h * p.conv_w) != 0 ||

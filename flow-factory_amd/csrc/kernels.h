@@ -12,21 +12,24 @@ namespace mi355 {
 // C[m][n] = sum_k A[m][k] * W[n][k]   (both operands K-contiguous bf16, fp32 accumulate on
 // v_mfma_f32_16x16x32_bf16); the epilogue decides what is written.  K % 64 == 0.
 enum GemmEpi : int {
-    EPI_BIAS = 0,       // out[m][n] = bf16(acc + bias[n])
-    EPI_BIAS_SILU,      // out = bf16(silu(bf16(acc + bias)))
-    EPI_BIAS_GELU,      // out = bf16(gelu_tanh(acc + bias))
-    EPI_POSADD,         // out = bf16(acc + bias[n] + aux[(m % rows_per_sample)][n])   (patch-embed + pos-embed)
-    EPI_ADDSRC_SILU,    // out = bf16(silu(bf16(acc + bias[n] + aux[m % rows_per_sample][n])))  (temb = t_emb + pooled_emb)
-    EPI_GATE_RES,       // out[m][n] = bf16(out[m][n] + gate[m / rows_per_sample][n] * (acc + bias[n]))  (in place)
-    EPI_QK_NORM,        // per-head RMSNorm of (acc + bias) then scatter to q/k [b][h][s][64]
-    EPI_VT,             // rows = features, cols = tokens: vT[b][h][d][s] = bf16(acc + bias[m])
-    EPI_UNPATCH,        // proj_out: scatter (token, (p,q,c)) -> latent [b][c][y][x] (bf16)
+    // pre = acc + bias[n] in fp32.  Every epilogue that goes on after the bias stages bf16(pre) through LDS first and works on THAT value: one
+    // rounding per bf16 op of the PyTorch module it fuses (tests/test_gpu_gemm_epilogues.py pins each line per element)
+    EPI_BIAS = 0,       // out[m][n] = bf16(pre)
+    EPI_BIAS_SILU,      // out = bf16(silu(bf16(pre)))
+    EPI_BIAS_GELU,      // out = bf16(gelu_tanh(pre))   (the activation on the fp32 sum: one rounding); with `stash`: stash = bf16(pre)
+    EPI_POSADD,         // out = bf16(bf16(pre) + aux[m % rows_per_sample][n])   (patch-embed + pos-embed)
+    EPI_ADDSRC_SILU,    // out = bf16(silu(bf16(bf16(pre) + aux[m % rows_per_sample][n])))  (temb = t_emb + pooled_emb)
+    EPI_GATE_RES,       // out[m][n] = bf16(fma(gate[m / rows_per_sample][n], bf16(pre), out[m][n]))  (in place); with `stash`: stash = bf16(pre)
+    EPI_QK_NORM,        // per (row, 64-column head): rstd = 1/sqrt(mean(pre^2) + eps), y = bf16(pre * rstd * nw[d] (* q_scale for q, if non-zero)),
+                        // scattered to q/k [b][h][s_off + m % rows_per_sample][64], b = m / rows_per_sample (columns [0, 64 H) = q, the rest = k)
+    EPI_VT,             // rows = features, cols = tokens: vT[b][h][d][s_off + n % rows_per_sample] = bf16(acc + bias[m]), m = (h << hd) + d, b = n / rows_per_sample
+    EPI_UNPATCH,        // proj_out: latent[b][c][ty*p + pp][tx*p + qq] = bf16(pre[m][n]), m = (b, ty, tx), n = (pp*p + qq)*out_ch + c
     // ---- VAE decode (vae_engine.hip); these three always run on the simple 2-stage kernel
     EPI_BIAS_ROW,       // out[m][n] = bf16(acc + bias[m])              (row-major; swapped-operand V^T of the mid attention)
     EPI_F32,            // out_f32[m][n] = acc * q_scale                (attention scores, no bias)
     EPI_IMG,            // conv_out: image[b][n][y][x] = post(acc + bias[n]), n < N <= 4, fp32 or bf16 NCHW
     // ---- backward (engine_train.inc)
-    EPI_DGELU,          // out[m][n] = bf16((acc + bias[n]) * gelu_tanh'(aux[m][n]))   (aux = stashed pre-activation, row stride ld_aux)
+    EPI_DGELU,          // out[m][n] = bf16(bf16(pre) * gelu_tanh'(aux[m][n]))   (aux = stashed pre-activation, row stride ld_aux)
     EPI_QK_NORM_RSTD,   // EPI_QK_NORM that also stores the per-(row, head) 1/rms to rstd_out (training-mode forward; selected by launch_gemm)
     EPI_COUNT
 };
@@ -111,6 +114,19 @@ inline hipError_t copy_d2d(void* dst, const void* src, size_t bytes, hipStream_t
 // captured under the previous kernel selection (engine.hip)
 int tune_epoch();
 hipError_t launch_gemm(const GemmParams& p, hipStream_t stream);
+// which kernel family this thread's last launch_gemm launched (host-side record; mi355_gemm_last_kernel() of the C ABI returns it)
+enum GemmKernelId : int {
+    GEMM_KERNEL_NONE = 0,
+    GEMM_KERNEL_SIMPLE_128,      // 2-stage kernel, 128x128 tiles
+    GEMM_KERNEL_SIMPLE_256,      // 2-stage kernel, 256x256 tiles
+    GEMM_KERNEL_PP,              // persistent 256x256 ping-pong kernel
+    GEMM_KERNEL_W4,              // hand-scheduled 4-wave kernel, 256x256 tiles
+    GEMM_KERNEL_W6,              // 256x192 kernel
+    GEMM_KERNEL_MID_128x192,     // mid-size kernel
+    GEMM_KERNEL_MID_192x128,     // mid-size kernel, transposed form (EPI_VT)
+    GEMM_KERNEL_SIMPLE_OTHER,    // 2-stage kernel, the convolutions' 256x128 / 512x128 tiles
+};
+int gemm_last_kernel();
 void set_gemm_variant(int v);
 void set_w4_max_k(int k);      // largest K that the default dispatch gives to the 4-wave hand-scheduled kernel (mi355_tune_set(19, k))
 int get_gemm_variant();

@@ -547,6 +547,23 @@ def op_linear_gate_res(x: torch.Tensor, a: torch.Tensor, w: torch.Tensor, bias: 
     return x
 
 
+EPI_BIAS, EPI_BIAS_SILU, EPI_BIAS_GELU, EPI_POSADD, EPI_ADDSRC_SILU, EPI_GATE_RES, EPI_QK_NORM, EPI_VT, EPI_UNPATCH, EPI_DGELU = 0, 1, 2, 3, 4, 5, 6, 7, 8, 12
+GEMM_KERNELS = {0: "none", 1: "simple128", 2: "simple256", 3: "pingpong", 4: "w4", 5: "256x192", 6: "mid128x192", 7: "mid192x128", 8: "simple-other"}
+
+
+def op_gemm_epi(epi: int, a, lda: int, w, ldw: int, M: int, N: int, K: int, bias, out=None, ldo: int = 0, aux=None, ld_aux: int = 0,
+                rows_per_sample: int = 1, q=None, k=None, nw_q=None, nw_k=None, H: int = 0, S_pad: int = 0, s_off: int = 0, eps: float = 1e-6,
+                hd_shift: int = 0, q_scale: float = 0.0, hp: int = 0, wp: int = 0, patch: int = 0, out_ch: int = 0, stash=None, ld_stash: int = 0,
+                rstd_out=None) -> str:
+    """One GEMM with the fused epilogue `epi` (mi355_op_gemm_epi of include/mi355_flow.h has the formulas) on caller-owned buffers: nothing is
+    allocated, copied or made contiguous, the strides are arguments.  Returns the name of the kernel family the dispatch launched."""
+    lib = _lib.load()
+    _lib.check(lib.mi355_op_gemm_epi(_stream(), _dp(a), lda, _dp(w), ldw, M, N, K, epi, _dp(bias), _dp(out), ldo, _dp(aux), ld_aux, rows_per_sample,
+                                     _dp(q), _dp(k), _dp(nw_q), _dp(nw_k), H, S_pad, s_off, eps, hd_shift, q_scale, hp, wp, patch, out_ch,
+                                     _dp(stash), ld_stash, _dp(rstd_out)), "op_gemm_epi")
+    return GEMM_KERNELS[lib.mi355_gemm_last_kernel()]
+
+
 def op_wgrad(dy: torch.Tensor, x: torch.Tensor, k_split: int = 1, variant: int = 1, want_colsum: bool = False):
     """Weight-gradient partial sums [k_split, N, K] (fp32) of dW = dy^T @ x over `k_split` slices of the M rows; dy [M, N] and x [M, K] bf16
     row-major (rows may be strided views: the row stride is passed; any M: a ragged last 64-row tile reads zeros).  variant 1 = the

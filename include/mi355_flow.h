@@ -203,6 +203,36 @@ int mi355_op_linear(void* stream, const void* A, const void* W, const float* bia
  * JointTransformerBlock.forward, reached from models/stable_diffusion/sd3_5.py:421-428) as an operator */
 int mi355_op_linear_gate_res(void* stream, const void* A, const void* W, const float* bias, const void* gate, void* x, int M, int N, int K,
                              int rows_per_sample);
+/* Every fused GEMM epilogue as an operator (tests/test_gpu_gemm_epilogues.py): C = A[M][K] (row stride lda) . W[N][K]^T (row stride ldw), fp32
+ * accumulation, pre = C + bias[n] (fp32), then by `epi`, in the order of the engine's epilogue enumeration:
+ *   MI355_EPI_BIAS         out[m][n] = bf16(pre)                                              (row stride ldo)
+ *   MI355_EPI_BIAS_SILU    out = bf16(silu(bf16(pre)))
+ *   MI355_EPI_BIAS_GELU    out = bf16(gelu_tanh(pre));  with stash: stash[m][n] = bf16(pre)   (row stride ld_stash)
+ *   MI355_EPI_POSADD       out = bf16(bf16(pre) + aux[m % rows_per_sample][n])                (aux row stride ld_aux)
+ *   MI355_EPI_ADDSRC_SILU  out = bf16(silu(bf16(bf16(pre) + aux[m % rows_per_sample][n])))
+ *   MI355_EPI_GATE_RES     out = bf16(fma(aux[m / rows_per_sample][n], bf16(pre), out)), in place;  with stash: stash = bf16(pre)
+ *   MI355_EPI_QK_NORM      N = 2 * H * 64: per row and 64-column head rstd = 1/sqrt(mean(pre^2) + eps), y = bf16(pre * rstd * nw[d]) (nw_q for the
+ *                          first H heads, times q_scale if that is non-zero; nw_k for the rest), to q / k [b][h][s_off + m % rows_per_sample][64]
+ *                          ([B][H][S_pad][64], b = m / rows_per_sample); with rstd_out: rstd_out[m][2 H] = rstd as well, q / k bits unchanged
+ *   MI355_EPI_VT           rows are features (M = H << hd, hd = 6, or 7 with hd_shift = 7; bias[m]), columns tokens:
+ *                          q[b][h][d][s_off + n % rows_per_sample] = bf16(C + bias[m])          ([B][H][1 << hd][S_pad], b = n / rows_per_sample)
+ *   MI355_EPI_UNPATCH      N = patch * patch * out_ch, M = B * hp * wp: out[b][c][ty * patch + pp][tx * patch + qq] = bf16(pre[m][n]),
+ *                          m = (b * hp + ty) * wp + tx, n = (pp * patch + qq) * out_ch + c
+ *   MI355_EPI_DGELU        out = bf16(bf16(pre) * gelu_tanh'(aux[m][n]))
+ * bf16 tensors, fp32 bias / nw / rstd_out.  K % 64 == 0, N % 4 == 0 (N % 8 for GATE_RES), lda / ldw / ld_aux multiples of 8; ldo and ld_stash
+ * may be any value >= N (rows that are not 16-byte aligned take the element-wise store path).  Arguments an epilogue does not use are
+ * ignored (NULL / 0).  Everything is checked before any HIP call. */
+enum { MI355_EPI_BIAS = 0, MI355_EPI_BIAS_SILU = 1, MI355_EPI_BIAS_GELU = 2, MI355_EPI_POSADD = 3, MI355_EPI_ADDSRC_SILU = 4, MI355_EPI_GATE_RES = 5,
+       MI355_EPI_QK_NORM = 6, MI355_EPI_VT = 7, MI355_EPI_UNPATCH = 8, MI355_EPI_DGELU = 12 };
+int mi355_op_gemm_epi(void* stream, const void* A, int64_t lda, const void* W, int64_t ldw, int M, int N, int K, int epi, const float* bias,
+                      void* out, int64_t ldo, const void* aux, int64_t ld_aux, int rows_per_sample, void* q, void* k, const float* nw_q,
+                      const float* nw_k, int H, int S_pad, int s_off, float eps, int hd_shift, float q_scale, int hp, int wp, int patch,
+                      int out_ch, void* stash, int64_t ld_stash, float* rstd_out);
+/* The kernel family that the calling thread's last GEMM launch went to (a host-side record; the dispatch picks by grid size and the
+ * mi355_tune_set keys 0, 3, 19, 31, 32, 34, 37, 40) */
+enum { MI355_GEMM_NONE = 0, MI355_GEMM_SIMPLE_128 = 1, MI355_GEMM_SIMPLE_256 = 2, MI355_GEMM_PINGPONG = 3, MI355_GEMM_W4 = 4, MI355_GEMM_256x192 = 5,
+       MI355_GEMM_MID_128x192 = 6, MI355_GEMM_MID_192x128 = 7, MI355_GEMM_SIMPLE_OTHER = 8 };
+int mi355_gemm_last_kernel(void);
 /* Weight-gradient product on ROW-MAJOR operands (round 6, csrc/gemm_tn.hip): out[s][n][k] (fp32, [k_split][N][K]) = sum over the s-th slice of
  * the M rows of dY[m][n] * X[m][k]; dY [M][ld_dy] and X [M][ld_x] bf16 as the backward leaves them in HBM -- no transposed copies (reference: the
  * weight gradients `accelerator.backward(loss)` produces for the trainable linear layers, trainers/grpo.py:326-330).  N % 128, K % 128 must be

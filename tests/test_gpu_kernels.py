@@ -47,6 +47,16 @@ def test_linear(eng, M, N, K, act):
     # asymmetric operands: a transposed / mis-mapped fragment gives rel error ~1.4, not 1e-3
     assert _rel(y, ref) < 4e-3, (M, N, K, act, _rel(y, ref))
     assert float((y.float() - ref).abs().max()) < 0.06 * max(1.0, float(ref.abs().max()))
+    if M * N * K <= 300 * 260 * 128:
+        # the three smallest shapes, PER ELEMENT against fp64 (the bounds of tests/test_gpu_gemm_epilogues.py): one wrong element, row or
+        # 8-column strip at a tile edge passes the two norms above
+        from test_gpu_gemm_epilogues import _direct, _gelu, _silu, _staged
+        pre64 = x.double() @ w.double().t() + b.double()
+        pre32 = x.float() @ w.float().t() + b
+        if act == 2:
+            _direct(y, _gelu(pre64), _gelu(pre32), f"linear gelu {M}x{N}x{K}")
+        else:
+            _staged(y, pre64, pre32, _silu if act == 1 else None, f"linear act={act} {M}x{N}x{K}")
 
 
 @pytest.mark.parametrize("key,M,N,K", [(40, 8192, 1536, 1536), (40, 8192, 3072, 1536), (40, 8192, 1536, 6144), (40, 4608, 3072, 3072), (40, 256, 192, 128),
