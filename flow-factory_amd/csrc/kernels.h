@@ -143,6 +143,7 @@ void set_mid_plan_hint(int v);      // engine.hip forward_core: whether this pla
 void set_raster_gm(int v);      // GEMM tile raster: tile rows per band (0 = row-major)
 void set_conv_cfg(int v);       // VAE conv tile shape A/B knob (0 auto)
 void set_attn_variant(int v);  // 0 = plain online softmax, 1 = deferred-rescale (default)
+void set_attn64_w4(int v);     // 1 (default) = static-softmax launches with a pre-scaled q take the 4-wave hand-scheduled kernel, 0 = never
 int get_attn_variant();  // tuning / A-B knob: 0 = simple 2-stage 256x256 kernel, 1 = ping-pong (default)
 
 // ------------------------------------------------------------------------------- attention

@@ -716,6 +716,10 @@ int mi355_profile_enable(int on);
  *         form (64 keys / queries per wave, one wave per SIMD: bit-identical, measured equal -- csrc/gen_attn_bwd.py 64x2).
  *  44     head_dim-128 attention backward (FLUX.1 / Qwen-Image / Wan): 1 (default) = the software-pipelined passes (csrc/gen_attn_bwd.py 128),
  *         0 = the round-4 kernels (bit-identical).
+ *  45     head_dim-64 attention forward: 1 (default) = every launch with a proven |score| bound <= 60 and a pre-scaled q (the rollout and the
+ *         training-mode forward of the SD3.5 engine) runs the 4-wave kernel with the hand-scheduled two-chain key loop (csrc/gen_attn64_w4.py),
+ *         whatever key 1 says; 0 = the compiler-scheduled kernels as before; 2 = as 1 at one workgroup per CU (A/B).  Row sums are fp32 sums
+ *         of the exponentials there: results agree with key 45 = 0 to the operator bounds, not bit for bit.
  * The environment variable MI355_TUNE="key=value,..." applies these settings when the Python binding loads the library. */
 int mi355_tune_set(int key, int value);
 int mi355_profile_collect(double* ms_out, int64_t* count_out);

@@ -18,7 +18,8 @@ def short(name):
                      ("splitk_reduce_kernel", "splitk_reduce_kernel"), ("colsum_partial_kernel", "colsum_partial_kernel"),
                      ("colsum_finish_kernel", "colsum_finish_kernel"), ("transpose_kernel", "transpose_kernel"), ("ln_mod_bwd_kernel", "ln_mod_bwd_kernel"),
                      ("rms_bwd_gather", "rms_bwd_gather_kernel"), ("attn_bwd_prep", "attn_bwd_prep_kernel"), ("gate_mul_kernel", "gate_mul_kernel"),
-                     ("attn_bwd_dkv_tr_kernel", "attn_bwd_dkv_tr_kernel"), ("attn_bwd_dq_tr_kernel", "attn_bwd_dq_tr_kernel"), ("attn_kernel", "attn_kernel"),
+                     ("attn_bwd_dkv_tr_kernel", "attn_bwd_dkv_tr_kernel"), ("attn_bwd_dq_tr_kernel", "attn_bwd_dq_tr_kernel"), ("attn64_w4_kernel", "attn64_w4_kernel"),
+                     ("attn_kernel", "attn_kernel"),
                      ("gemm_mid_kernel", None), ("gemm_w6_kernel", None), ("gemm_w4_kernel", None), ("gemm_pp_kernel", None), ("gemm_kernel", None), ("ln_mod_kernel", "ln_mod_kernel"),
                      ("sde_step_kernel", "sde_step_kernel"), ("patchify", "patchify_kernel"), ("time_proj", "time_proj_kernel"),
                      ("convert_kernel", "convert_kernel"), ("pos_crop", "pos_crop_kernel"), ("gn_partial", "gn_partial_kernel"),
@@ -98,7 +99,9 @@ json.dump(summary, open(os.path.join(out, "pmc_per_launch.json"), "w"), indent=1
 
 # the dominant kernel's HBM traffic per launch, as bench.py's roofline.traffic reads it (MI355X_MICROARCH.md: FETCH_SIZE / WRITE_SIZE are in
 # KiB; on gfx950 FETCH_SIZE reports half of the bytes of wide coalesced reads -> doubled; WRITE_SIZE as is)
-a = summary.get("attn_kernel", {})
+# (since tune key 45 the static-softmax launches of the forward run attn64_w4_kernel; attn_kernel where key 45 = 0 or no bound is proven)
+a_name = "attn64_w4_kernel" if "FETCH_SIZE" in summary.get("attn64_w4_kernel", {}) else "attn_kernel"
+a = summary.get(a_name, {})
 if "FETCH_SIZE" in a and "WRITE_SIZE" in a:
     import subprocess
     try:
@@ -114,9 +117,9 @@ if "FETCH_SIZE" in a and "WRITE_SIZE" in a:
     for k, v in summary.items():
         if v.get("SQ_VALU_MFMA_BUSY_CYCLES") and v.get("GRBM_GUI_ACTIVE") and ("gemm" in k or "attn" in k):
             by_kernel[k] = round(v["SQ_VALU_MFMA_BUSY_CYCLES"] / (v["GRBM_GUI_ACTIVE"] / 8.0 * 1024.0), 4)
-    json.dump({"round": int(os.environ.get("MI355_ROUND", "4")), "commit": sha, "mfma_busy": mfma_busy,
+    json.dump({"round": int(os.environ.get("MI355_ROUND", "7")), "commit": sha, "mfma_busy": mfma_busy,
                "mfma_busy_formula": "SQ_VALU_MFMA_BUSY_CYCLES (summed over 1024 SIMDs) / (GRBM_GUI_ACTIVE (summed over 8 XCDs) / 8 * 1024), per launch",
-               "mfma_busy_by_kernel": by_kernel, "kernel": "mi355::attn_kernel (mean over the joint S=4429 and dual S=4096 launches of a forward, forward batch 8)",
+               "mfma_busy_by_kernel": by_kernel, "kernel": "mi355::" + a_name + " (mean over the joint S=4429 and dual S=4096 launches of a forward, forward batch 8)",
                "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) of bench.py --steps 1 --warmup 0 --denoise-steps 2",
                "FETCH_SIZE_kb_per_launch": a["FETCH_SIZE"], "WRITE_SIZE_kb_per_launch": a["WRITE_SIZE"],
                "correction": "gfx950: FETCH_SIZE reports 1/2 of the bytes of wide coalesced reads -> doubled; WRITE_SIZE as is",
