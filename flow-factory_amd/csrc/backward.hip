@@ -16,8 +16,11 @@ namespace {
 // dx is ADDED to dres (the residual-stream gradient arriving from later layers) when accumulate != 0.
 // DMOD = false drops the modulation-gradient partials (4 x LN_MAXC x 8 registers) from the instantiation: the D = 5120 form (Wan2.1-14B,
 // both Wan2.2-A14B experts; their modulation table is not trained through this kernel) would not fit its registers otherwise.
-template <int LN_MAXC, bool DMOD = true>
+// SPLIT (two-group modulation, head_rows > 0; DMOD = false only): the scale row of token row m is 2 b + (m % rows_per_sample >= head_rows).  A
+// compile-time flag, so that the unsplit instantiations keep their code.
+template <int LN_MAXC, bool DMOD = true, bool SPLIT = false>
 __global__ __launch_bounds__(256) void ln_mod_bwd_kernel(LnModBwdParams p, int rows_per_wave) {
+    static_assert(!(SPLIT && DMOD), "modulation gradients of a split table are not implemented");
     const int lane = threadIdx.x & 63;
     const int first = (blockIdx.x * 4 + (threadIdx.x >> 6)) * rows_per_wave;
     if (first >= p.M) return;
@@ -56,7 +59,9 @@ __global__ __launch_bounds__(256) void ln_mod_bwd_kernel(LnModBwdParams p, int r
     for (int row = first; row < last; ++row) {
         const int b = row / p.rows_per_sample;
         if (DMOD && p.dmod && b != cur_b) { flush(cur_b); zero_acc(); cur_b = b; }
-        const bf16_t* mod = p.mod + (long)b * p.mod_ld;
+        long mrow = b;
+        if constexpr (SPLIT) mrow = 2L * b + ((row - b * p.rows_per_sample) >= p.head_rows ? 1 : 0);
+        const bf16_t* mod = p.mod + mrow * p.mod_ld;
         float v[LN_MAXC][8], g[LN_MAXC][8];
         float sum = 0.f;
         const long ro = (long)row * p.D;
@@ -142,6 +147,25 @@ __global__ __launch_bounds__(256) void gate_mul_kernel(const bf16_t* dx, const b
         float a[8], gt[8];
         unpack8(*(const uint4*)(dx + m * D + ch * 8), a);
         unpack8(*(const uint4*)(gate + (m / rps) * gate_ld + ch * 8), gt);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) a[e] *= gt[e];
+        *(uint4*)(dy + m * D + ch * 8) = pack8(a);
+    }
+}
+
+// the same with two gate rows per sample (two-group modulation): the first head_rows rows of sample b read gate row 2 b, the others row 2 b + 1
+__global__ __launch_bounds__(256) void gate_mul_split_kernel(const bf16_t* dx, const bf16_t* gate, long gate_ld, bf16_t* dy, long M, int D, int rps,
+                                                             int head_rows) {
+    const int chunks = D >> 3;
+    const long total = M * chunks;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const long m = i / chunks;
+        const int ch = (int)(i - m * chunks);
+        const long b = m / rps;
+        const long grow = 2 * b + ((m - b * rps) >= head_rows ? 1 : 0);
+        float a[8], gt[8];
+        unpack8(*(const uint4*)(dx + m * D + ch * 8), a);
+        unpack8(*(const uint4*)(gate + grow * gate_ld + ch * 8), gt);
 #pragma unroll
         for (int e = 0; e < 8; ++e) a[e] *= gt[e];
         *(uint4*)(dy + m * D + ch * 8) = pack8(a);
@@ -851,7 +875,8 @@ int wgrad_split(int N, int K, int M_pad, size_t part_floats, bool overlapped) {
 hipError_t launch_ln_mod_bwd(const LnModBwdParams& p, hipStream_t st) {
     if (sched_trace_on()) {
         const size_t xb = (size_t)p.M * p.D * 2, nb = (size_t)((p.M + p.rows_per_sample - 1) / p.rows_per_sample);
-        const TraceRegion mod = treg(p.mod, ((nb - 1) * p.mod_ld + (size_t)(p.scale_off > p.scale2_off ? p.scale_off : p.scale2_off) + p.D) * 2);
+        const size_t mrows = nb * (p.head_rows > 0 ? 2 : 1);      // two modulation rows per sample with the two-group split
+        const TraceRegion mod = treg(p.mod, ((mrows - 1) * p.mod_ld + (size_t)(p.scale_off > p.scale2_off ? p.scale_off : p.scale2_off) + p.D) * 2);
         sched_trace_launch("ln_mod_bwd", st, {treg(p.x, xb), treg(p.dy, xb), treg(p.dy2, p.dy2 ? xb : 0), mod, treg(p.dres, p.accumulate ? xb : 0)},
                            {treg(p.dres, xb), treg(p.dmod, p.dmod ? (nb * p.mod_ld) * 4 : 0)});
     }
@@ -859,6 +884,13 @@ hipError_t launch_ln_mod_bwd(const LnModBwdParams& p, hipStream_t st) {
     if (p.D % 8 != 0 || p.D > (p.dmod ? 8 : 12) * 64 * 8 || p.M <= 0) return hipErrorInvalidValue;
     const int rpw = p.dmod ? 16 : 1;         // rows per wave: 16 with the modulation-gradient partials in registers
     const int grid = (p.M + 4 * rpw - 1) / (4 * rpw);
+    if (p.head_rows < 0 || (p.head_rows > 0 && (p.dmod || p.rows_per_sample <= 0 || p.head_rows > p.rows_per_sample))) return hipErrorInvalidValue;
+    if (p.head_rows > 0) {      // two-group modulation: its own instantiations (no modulation gradients)
+        if (p.D <= 2048) hipLaunchKernelGGL((ln_mod_bwd_kernel<4, false, true>), dim3(grid), dim3(256), 0, st, p, rpw);
+        else if (p.D <= 4096) hipLaunchKernelGGL((ln_mod_bwd_kernel<8, false, true>), dim3(grid), dim3(256), 0, st, p, rpw);
+        else hipLaunchKernelGGL((ln_mod_bwd_kernel<12, false, true>), dim3(grid), dim3(256), 0, st, p, rpw);
+        return hipGetLastError();
+    }
     // Without modulation gradients (the reference's default target sets: no trainable tensor upstream of the modulation table) the
     // DMOD = false instantiation: the 4 x LN_MAXC x 8 partial-sum registers of the other form cost it its occupancy even when unused
     // (round 6: one wave per row, 8192 latency-bound waves per launch -- resident waves per SIMD are what hides their four reductions)
@@ -894,9 +926,16 @@ hipError_t launch_f32_to_bf16_pad(const float* in, bf16_t* out, long rows, long 
     return hipGetLastError();
 }
 
-hipError_t launch_gate_mul(const bf16_t* dx, const bf16_t* gate, long gate_ld, bf16_t* dy, long M, int D, int rps, hipStream_t st) {
-    if (sched_trace_on()) sched_trace_launch("gate_mul", st, {treg(dx, (size_t)M * D * 2), treg(gate, ((size_t)((M + rps - 1) / rps - 1) * gate_ld + D) * 2)}, {treg(dy, (size_t)M * D * 2)});
-    if (D % 8 || M <= 0) return hipErrorInvalidValue;
+hipError_t launch_gate_mul(const bf16_t* dx, const bf16_t* gate, long gate_ld, bf16_t* dy, long M, int D, int rps, hipStream_t st, int head_rows) {
+    if (sched_trace_on()) {
+        const size_t grows = (size_t)((M + rps - 1) / rps) * (head_rows > 0 ? 2 : 1);
+        sched_trace_launch("gate_mul", st, {treg(dx, (size_t)M * D * 2), treg(gate, ((grows - 1) * gate_ld + D) * 2)}, {treg(dy, (size_t)M * D * 2)});
+    }
+    if (D % 8 || M <= 0 || head_rows < 0 || head_rows > rps) return hipErrorInvalidValue;
+    if (head_rows > 0) {
+        hipLaunchKernelGGL(gate_mul_split_kernel, dim3(grid_for(M * (D >> 3), 256)), dim3(256), 0, st, dx, gate, gate_ld, dy, M, D, rps, head_rows);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(gate_mul_kernel, dim3(grid_for(M * (D >> 3), 256)), dim3(256), 0, st, dx, gate, gate_ld, dy, M, D, rps);
     return hipGetLastError();
 }

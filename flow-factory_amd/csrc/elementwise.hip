@@ -11,7 +11,9 @@ namespace {
 // One wave per row; the row (D <= 8*64*MAXC) stays in registers: exact two-pass mean/variance.
 // LN_MAXC 16-byte chunks per lane: 4 -> D <= 2048 (SD3.5, D = 1536), 8 -> D <= 4096 (FLUX.1, D = 3072), 12 -> D <= 6144 (the 40-head Wan
 // transformers, D = 5120: Wan2.1-14B and both Wan2.2-A14B experts)
-template <int LN_MAXC>
+// SPLIT (two-group modulation, head_rows > 0): the first head_rows rows of sample b read modulation row 2 b, the others row 2 b + 1.  A compile-time
+// flag: the unsplit instantiations keep their code.
+template <int LN_MAXC, bool SPLIT = false>
 __global__ __launch_bounds__(256) void ln_mod_kernel(LnModParams p) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -43,7 +45,9 @@ __global__ __launch_bounds__(256) void ln_mod_kernel(LnModParams p) {
     }
     const float rstd = rsqrtf(wave_sum(sq) / (float)p.D + p.eps);
     const int b = row / p.rows_per_sample;
-    const bf16_t* mod = p.mod + (long)b * p.mod_ld;
+    long mrow = b;
+    if constexpr (SPLIT) mrow = 2L * b + ((row - b * p.rows_per_sample) >= p.head_rows ? 1 : 0);
+    const bf16_t* mod = p.mod + mrow * p.mod_ld;
 #pragma unroll
     for (int c = 0; c < LN_MAXC; ++c) {
         const int ch = lane + c * 64;
@@ -90,6 +94,24 @@ __global__ void patchify_kernel(const void* lat, int dt, bf16_t* out, int B, int
         const int c = k / (p * p), py = (k / p) % p, px = k % p;
         const long src = (((long)b * C + c) * h + ty * p + py) * w + tx * p + px;
         out[tok * ld + col0 + k] = f2bf(load_as_f32(lat, src, dt));
+    }
+}
+
+// first-frame merge (Wan2.2-TI2V image-to-video): the patches of ONE frame ff [B][C][h][w] go to rows [0, hp*wp) of every sample's `rps` rows of the
+// dense patch matrix (both CFG replicas) -- the same element-wise conversion as patchify_kernel, so the rows equal those of a patchified merged tensor
+__global__ void patchify_head_kernel(const void* ff, int dt, bf16_t* out, int B, int rep, int C, int h, int w, int p, int rps) {
+    const int hp = h / p, wp = w / p, K = C * p * p;
+    const long total = (long)B * rep * hp * wp * K;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int k = (int)(i % K);
+        const long tok = i / K;
+        const int tx = (int)(tok % wp);
+        const int ty = (int)((tok / wp) % hp);
+        const int bb = (int)(tok / ((long)wp * hp));
+        const int b = bb % B;
+        const int c = k / (p * p), py = (k / p) % p, px = k % p;
+        const long src = (((long)b * C + c) * h + ty * p + py) * w + tx * p + px;
+        out[((long)bb * rps + ty * wp + tx) * K + k] = f2bf(load_as_f32(ff, src, dt));
     }
 }
 
@@ -157,12 +179,20 @@ inline int grid_for(long total, int block) {
 hipError_t launch_ln_mod(const LnModParams& p, hipStream_t stream) {
     if (sched_trace_on()) {
         const size_t xb = (size_t)p.M * p.D * 2, nb = (size_t)((p.M + p.rows_per_sample - 1) / (p.rows_per_sample > 0 ? p.rows_per_sample : 1));
-        const size_t mb = nb ? ((nb - 1) * p.mod_ld + p.D) * 2 : 0;
+        const size_t mrows = nb * (p.head_rows > 0 ? 2 : 1);      // two modulation rows per sample with the two-group split
+        const size_t mb = mrows ? ((mrows - 1) * p.mod_ld + p.D) * 2 : 0;
         sched_trace_launch("ln_mod", stream, {treg(p.x, xb), treg(p.mod + p.shift_off, mb), treg(p.mod + p.scale_off, mb),
                                               treg(p.out2 ? p.mod + p.shift2_off : nullptr, mb), treg(p.out2 ? p.mod + p.scale2_off : nullptr, mb)},
                            {treg(p.out, xb), treg(p.out2, p.out2 ? xb : 0)});
     }
     if (p.D % 8 != 0 || p.D > 12 * 64 * 8 || p.M <= 0) return hipErrorInvalidValue;
+    if (p.head_rows < 0 || (p.head_rows > 0 && (p.rows_per_sample <= 0 || p.head_rows > p.rows_per_sample))) return hipErrorInvalidValue;
+    if (p.head_rows > 0) {
+        if (p.D <= 2048) hipLaunchKernelGGL((ln_mod_kernel<4, true>), dim3((p.M + 3) / 4), dim3(256), 0, stream, p);
+        else if (p.D <= 4096) hipLaunchKernelGGL((ln_mod_kernel<8, true>), dim3((p.M + 3) / 4), dim3(256), 0, stream, p);
+        else hipLaunchKernelGGL((ln_mod_kernel<12, true>), dim3((p.M + 3) / 4), dim3(256), 0, stream, p);
+        return hipGetLastError();
+    }
     if (p.D <= 2048) hipLaunchKernelGGL(ln_mod_kernel<4>, dim3((p.M + 3) / 4), dim3(256), 0, stream, p);
     else if (p.D <= 4096) hipLaunchKernelGGL(ln_mod_kernel<8>, dim3((p.M + 3) / 4), dim3(256), 0, stream, p);
     else hipLaunchKernelGGL(ln_mod_kernel<12>, dim3((p.M + 3) / 4), dim3(256), 0, stream, p);
@@ -191,6 +221,16 @@ hipError_t launch_patchify_cols(const void* lat, int dt, bf16_t* patches, int B,
         sched_trace_launch("patchify_cols", stream, {treg(lat, (size_t)B * C * h * w * (dt == DT_F32 ? 4 : 2))},
                            {treg(patches + col0, (size_t)((rows - 1) * ld + K) * 2)});
     hipLaunchKernelGGL(patchify_kernel, dim3(grid_for(rows * K, 256)), dim3(256), 0, stream, lat, dt, patches, B, rep, C, h, w, p, col0, ld);
+    return hipGetLastError();
+}
+
+hipError_t launch_patchify_head(const void* ff, int dt, bf16_t* patches, int B, int rep, int C, int h, int w, int p, int rps, hipStream_t stream) {
+    if (B < 1 || rep < 1 || C < 1 || p < 1 || h % p || w % p || rps < (h / p) * (w / p)) return hipErrorInvalidValue;
+    const int K = C * p * p, head = (h / p) * (w / p);
+    if (sched_trace_on())
+        sched_trace_launch("patchify_head", stream, {treg(ff, (size_t)B * C * h * w * (dt == DT_F32 ? 4 : 2))},
+                           {tregs(patches, (size_t)head * K * 2, (size_t)rps * K * 2, (size_t)B * rep)});
+    hipLaunchKernelGGL(patchify_head_kernel, dim3(grid_for((long)B * rep * head * K, 256)), dim3(256), 0, stream, ff, dt, patches, B, rep, C, h, w, p, rps);
     return hipGetLastError();
 }
 

@@ -1062,11 +1062,15 @@ extern "C" int mi355_op_linear_gate_res(void* stream, const void* A, const void*
 
 // Every fused epilogue of launch_epi as an operator (tests/test_gpu_gemm_epilogues.py): fills a GemmParams from plain arguments and calls
 // launch_gemm, nothing else.  Every argument is checked before any HIP call; the message names the operator and the argument.
-extern "C" int mi355_op_gemm_epi(void* stream, const void* A, int64_t lda, const void* W, int64_t ldw, int M, int N, int K, int epi, const float* bias,
-                                 void* out, int64_t ldo, const void* aux, int64_t ld_aux, int rows_per_sample, void* q, void* k, const float* nw_q,
-                                 const float* nw_k, int H, int S_pad, int s_off, float eps, int hd_shift, float q_scale, int hp, int wp, int patch,
-                                 int out_ch, void* stash, int64_t ld_stash, float* rstd_out) {
-#define GE_FAIL(...) return errorf("mi355_op_gemm_epi: " __VA_ARGS__)
+// (`who` = the public entry point, for the messages; head_rows > 0 = the two-group gate table of mi355_op_gemm_epi_split)
+static int op_gemm_epi(const char* who, void* stream, const void* A, int64_t lda, const void* W, int64_t ldw, int M, int N, int K, int epi, const float* bias,
+                       void* out, int64_t ldo, const void* aux, int64_t ld_aux, int rows_per_sample, void* q, void* k, const float* nw_q,
+                       const float* nw_k, int H, int S_pad, int s_off, float eps, int hd_shift, float q_scale, int hp, int wp, int patch,
+                       int out_ch, void* stash, int64_t ld_stash, float* rstd_out, int head_rows) {
+#define GE_FAIL(fmt, ...) return errorf("%s: " fmt, who, ##__VA_ARGS__)
+    if (head_rows < 0) GE_FAIL("head_rows = %d is negative", head_rows);
+    if (head_rows > 0 && epi != EPI_GATE_RES) GE_FAIL("head_rows = %d: only the gated-residual epilogue reads a two-group table", head_rows);
+    if (head_rows > rows_per_sample) GE_FAIL("head_rows = %d exceeds rows_per_sample = %d", head_rows, rows_per_sample);
     static_assert(EPI_GATE_RES == 5 && EPI_UNPATCH == 8 && EPI_DGELU == 12, "the MI355_EPI_* values of include/mi355_flow.h are GemmEpi's");
     const bool is_qk = epi == EPI_QK_NORM, is_vt = epi == EPI_VT, is_unp = epi == EPI_UNPATCH;
     const bool uses_aux = epi == EPI_POSADD || epi == EPI_ADDSRC_SILU || epi == EPI_GATE_RES || epi == EPI_DGELU;
@@ -1126,9 +1130,26 @@ extern "C" int mi355_op_gemm_epi(void* stream, const void* A, int64_t lda, const
     g.q = (bf16_t*)q; g.k = (bf16_t*)k; g.nw_q = nw_q; g.nw_k = nw_k; g.H = H; g.S_pad = S_pad; g.s_off = s_off; g.eps = eps;
     g.hd_shift = hd_shift; g.q_scale = q_scale;
     g.hp = hp; g.wp = wp; g.patch = patch; g.out_ch = out_ch;
-    g.stash = (bf16_t*)stash; g.ld_stash = (long)ld_stash; g.rstd_out = rstd_out;
+    g.stash = (bf16_t*)stash; g.ld_stash = (long)ld_stash; g.rstd_out = rstd_out; g.head_rows = head_rows;
     HIPCHK(launch_gemm(g, (hipStream_t)stream));
     return 0;
+}
+
+extern "C" int mi355_op_gemm_epi(void* stream, const void* A, int64_t lda, const void* W, int64_t ldw, int M, int N, int K, int epi, const float* bias,
+                                 void* out, int64_t ldo, const void* aux, int64_t ld_aux, int rows_per_sample, void* q, void* k, const float* nw_q,
+                                 const float* nw_k, int H, int S_pad, int s_off, float eps, int hd_shift, float q_scale, int hp, int wp, int patch,
+                                 int out_ch, void* stash, int64_t ld_stash, float* rstd_out) {
+    return op_gemm_epi("mi355_op_gemm_epi", stream, A, lda, W, ldw, M, N, K, epi, bias, out, ldo, aux, ld_aux, rows_per_sample, q, k, nw_q, nw_k, H, S_pad,
+                       s_off, eps, hd_shift, q_scale, hp, wp, patch, out_ch, stash, ld_stash, rstd_out, 0);
+}
+// the same with the two-group gate table of MI355_EPI_GATE_RES: head_rows > 0 = row m reads aux row 2 (m / rows_per_sample) + (m % rows_per_sample >=
+// head_rows); head_rows == 0 = mi355_op_gemm_epi
+extern "C" int mi355_op_gemm_epi_split(void* stream, const void* A, int64_t lda, const void* W, int64_t ldw, int M, int N, int K, int epi, const float* bias,
+                                       void* out, int64_t ldo, const void* aux, int64_t ld_aux, int rows_per_sample, void* q, void* k, const float* nw_q,
+                                       const float* nw_k, int H, int S_pad, int s_off, float eps, int hd_shift, float q_scale, int hp, int wp, int patch,
+                                       int out_ch, void* stash, int64_t ld_stash, float* rstd_out, int head_rows) {
+    return op_gemm_epi("mi355_op_gemm_epi_split", stream, A, lda, W, ldw, M, N, K, epi, bias, out, ldo, aux, ld_aux, rows_per_sample, q, k, nw_q, nw_k, H,
+                       S_pad, s_off, eps, hd_shift, q_scale, hp, wp, patch, out_ch, stash, ld_stash, rstd_out, head_rows);
 }
 
 // the kernel family the calling thread's last GEMM launch went to (GemmKernelId of kernels.h; MI355_GEMM_* of the public header)
@@ -1218,6 +1239,27 @@ extern "C" int mi355_op_ln_modulate(void* stream, const void* x, const void* shi
     if (delta < -2147483647L || delta > 2147483647L) return errorf("mi355_op_ln_modulate: shift/scale too far apart");
     l.scale_off = (int)delta;
     l.M = M; l.D = D; l.rows_per_sample = rows_per_sample; l.eps = eps;
+    HIPCHK(lnmod_p(l, (hipStream_t)stream));
+    return 0;
+}
+
+// two-group form: shift, scale [2 * nb][D] (row 2 b for the first head_rows rows of sample b, row 2 b + 1 for the others); head_rows == 0 = the
+// operator above on [nb][D].  Every argument is checked before any HIP call.
+extern "C" int mi355_op_ln_modulate_split(void* stream, const void* x, const void* shift, const void* scale, void* out, int M, int D,
+                                          int rows_per_sample, float eps, int head_rows) {
+    if (!x || !shift || !scale || !out) return errorf("mi355_op_ln_modulate_split: null argument");
+    if (M <= 0 || rows_per_sample <= 0) return errorf("mi355_op_ln_modulate_split: bad shape (M %d, rows_per_sample %d)", M, rows_per_sample);
+    if (D <= 0 || D % 8 || D > 6144) return errorf("mi355_op_ln_modulate_split: D = %d is not a positive multiple of 8 up to 6144", D);
+    if (head_rows < 0 || head_rows > rows_per_sample)
+        return errorf("mi355_op_ln_modulate_split: head_rows = %d outside [0, rows_per_sample = %d]", head_rows, rows_per_sample);
+    LnModParams l;
+    memset(&l, 0, sizeof(l));
+    l.x = (const bf16_t*)x; l.out = (bf16_t*)out; l.out2 = nullptr; l.mod = (const bf16_t*)shift; l.mod_ld = D;
+    l.shift_off = 0;
+    const long delta = (const bf16_t*)scale - (const bf16_t*)shift;
+    if (delta < -2147483647L || delta > 2147483647L) return errorf("mi355_op_ln_modulate_split: shift/scale too far apart");
+    l.scale_off = (int)delta;
+    l.M = M; l.D = D; l.rows_per_sample = rows_per_sample; l.eps = eps; l.head_rows = head_rows;
     HIPCHK(lnmod_p(l, (hipStream_t)stream));
     return 0;
 }

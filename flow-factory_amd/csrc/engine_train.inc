@@ -756,35 +756,64 @@ extern "C" int mi355_op_attention_fwd_bwd_ex(void* stream, const void* q, const 
 // An output that may be a bf16 gradient buffer carries a dtype: it is marked for the launch and un-marked after it.
 static int op_out_dtype_ok(int dt) { return dt == DT_F32 || dt == DT_BF16; }
 
-extern "C" int mi355_op_ln_mod_bwd(void* stream, const void* x, const void* dy, const void* dy2, void* dres, const void* mod, int64_t mod_ld,
-                                   int shift_off, int scale_off, int shift2_off, int scale2_off, int M, int D, int rows_per_sample, float eps,
-                                   int accumulate, float* dmod) {
-    if (!x || !dy || !dres || !mod) return errorf("mi355_op_ln_mod_bwd: null argument");
-    if (M <= 0 || rows_per_sample <= 0) return errorf("mi355_op_ln_mod_bwd: bad shape (M %d, rows_per_sample %d)", M, rows_per_sample);
-    if (D <= 0 || D % 8) return errorf("mi355_op_ln_mod_bwd: D = %d is not a positive multiple of 8", D);
-    if (D > (dmod ? 4096 : 6144)) return errorf("mi355_op_ln_mod_bwd: D = %d is wider than %d (%s modulation gradients)", D, dmod ? 4096 : 6144, dmod ? "with" : "without");
+static int op_ln_mod_bwd(const char* who, void* stream, const void* x, const void* dy, const void* dy2, void* dres, const void* mod, int64_t mod_ld,
+                         int shift_off, int scale_off, int shift2_off, int scale2_off, int M, int D, int rows_per_sample, float eps,
+                         int accumulate, float* dmod, int head_rows) {
+    if (!x || !dy || !dres || !mod) return errorf("%s: null argument", who);
+    if (M <= 0 || rows_per_sample <= 0) return errorf("%s: bad shape (M %d, rows_per_sample %d)", who, M, rows_per_sample);
+    if (D <= 0 || D % 8) return errorf("%s: D = %d is not a positive multiple of 8", who, D);
+    if (D > (dmod ? 4096 : 6144)) return errorf("%s: D = %d is wider than %d (%s modulation gradients)", who, D, dmod ? 4096 : 6144, dmod ? "with" : "without");
     if (scale_off < 0 || (dy2 && scale2_off < 0) || (dmod && (shift_off < 0 || (dy2 && shift2_off < 0))) || mod_ld < D)
-        return errorf("mi355_op_ln_mod_bwd: bad modulation layout (mod_ld %lld)", (long long)mod_ld);
+        return errorf("%s: bad modulation layout (mod_ld %lld)", who, (long long)mod_ld);
+    if (head_rows < 0 || head_rows > rows_per_sample) return errorf("%s: head_rows = %d outside [0, rows_per_sample = %d]", who, head_rows, rows_per_sample);
+    if (head_rows > 0 && dmod) return errorf("%s: modulation gradients (dmod) of a two-group table (head_rows = %d) are not implemented", who, head_rows);
     LnModBwdParams p{(const bf16_t*)x, (const bf16_t*)dy, (const bf16_t*)dy2, (bf16_t*)dres, (const bf16_t*)mod, (long)mod_ld, scale_off, scale2_off,
-                     M, D, rows_per_sample, eps, accumulate, dmod, shift_off, shift2_off};
+                     M, D, rows_per_sample, eps, accumulate, dmod, shift_off, shift2_off, head_rows};
     hipError_t err = launch_ln_mod_bwd(p, (hipStream_t)stream);
-    if (err != hipSuccess) return errorf("mi355_op_ln_mod_bwd: %s", hipGetErrorString(err));
+    if (err != hipSuccess) return errorf("%s: %s", who, hipGetErrorString(err));
     return 0;
 }
 
+extern "C" int mi355_op_ln_mod_bwd(void* stream, const void* x, const void* dy, const void* dy2, void* dres, const void* mod, int64_t mod_ld,
+                                   int shift_off, int scale_off, int shift2_off, int scale2_off, int M, int D, int rows_per_sample, float eps,
+                                   int accumulate, float* dmod) {
+    return op_ln_mod_bwd("mi355_op_ln_mod_bwd", stream, x, dy, dy2, dres, mod, mod_ld, shift_off, scale_off, shift2_off, scale2_off, M, D, rows_per_sample,
+                         eps, accumulate, dmod, 0);
+}
+// two-group table: head_rows > 0 = row m reads modulation row 2 (m / rows_per_sample) + (m % rows_per_sample >= head_rows); refused together with dmod
+extern "C" int mi355_op_ln_mod_bwd_split(void* stream, const void* x, const void* dy, const void* dy2, void* dres, const void* mod, int64_t mod_ld,
+                                         int shift_off, int scale_off, int shift2_off, int scale2_off, int M, int D, int rows_per_sample, float eps,
+                                         int accumulate, float* dmod, int head_rows) {
+    return op_ln_mod_bwd("mi355_op_ln_mod_bwd_split", stream, x, dy, dy2, dres, mod, mod_ld, shift_off, scale_off, shift2_off, scale2_off, M, D,
+                         rows_per_sample, eps, accumulate, dmod, head_rows);
+}
+
 // y == NULL && dgate == NULL: dy = gate * dx only (launch_gate_mul); both given: dgate += sum dx * y as well (launch_gate_bwd)
-extern "C" int mi355_op_gate_bwd(void* stream, const void* dx, const void* gate, int64_t gate_ld, const void* y, void* dy, float* dgate, int64_t dg_ld,
-                                 int64_t M, int D, int rows_per_sample) {
-    if (!dx || !gate || !dy) return errorf("mi355_op_gate_bwd: null argument");
-    if ((y == nullptr) != (dgate == nullptr)) return errorf("mi355_op_gate_bwd: y and dgate go together (both NULL: the product only)");
-    if (M <= 0 || rows_per_sample <= 0) return errorf("mi355_op_gate_bwd: bad shape (M %lld, rows_per_sample %d)", (long long)M, rows_per_sample);
-    if (D <= 0 || D % 8) return errorf("mi355_op_gate_bwd: D = %d is not a positive multiple of 8", D);
-    if (gate_ld < D || (dgate && dg_ld < D)) return errorf("mi355_op_gate_bwd: a row stride is below D = %d", D);
+static int op_gate_bwd(const char* who, void* stream, const void* dx, const void* gate, int64_t gate_ld, const void* y, void* dy, float* dgate, int64_t dg_ld,
+                       int64_t M, int D, int rows_per_sample, int head_rows) {
+    if (!dx || !gate || !dy) return errorf("%s: null argument", who);
+    if ((y == nullptr) != (dgate == nullptr)) return errorf("%s: y and dgate go together (both NULL: the product only)", who);
+    if (M <= 0 || rows_per_sample <= 0) return errorf("%s: bad shape (M %lld, rows_per_sample %d)", who, (long long)M, rows_per_sample);
+    if (D <= 0 || D % 8) return errorf("%s: D = %d is not a positive multiple of 8", who, D);
+    if (gate_ld < D || (dgate && dg_ld < D)) return errorf("%s: a row stride is below D = %d", who, D);
+    if (head_rows < 0 || head_rows > rows_per_sample) return errorf("%s: head_rows = %d outside [0, rows_per_sample = %d]", who, head_rows, rows_per_sample);
+    if (head_rows > 0 && dgate) return errorf("%s: the gate gradient (dgate) of a two-group table (head_rows = %d) is not implemented", who, head_rows);
     hipError_t err = y ? launch_gate_bwd((const bf16_t*)dx, (const bf16_t*)gate, (long)gate_ld, (const bf16_t*)y, (bf16_t*)dy, dgate, (long)dg_ld, (long)M, D,
                                          rows_per_sample, (hipStream_t)stream)
-                       : launch_gate_mul((const bf16_t*)dx, (const bf16_t*)gate, (long)gate_ld, (bf16_t*)dy, (long)M, D, rows_per_sample, (hipStream_t)stream);
-    if (err != hipSuccess) return errorf("mi355_op_gate_bwd: %s", hipGetErrorString(err));
+                       : launch_gate_mul((const bf16_t*)dx, (const bf16_t*)gate, (long)gate_ld, (bf16_t*)dy, (long)M, D, rows_per_sample, (hipStream_t)stream,
+                                         head_rows);
+    if (err != hipSuccess) return errorf("%s: %s", who, hipGetErrorString(err));
     return 0;
+}
+
+extern "C" int mi355_op_gate_bwd(void* stream, const void* dx, const void* gate, int64_t gate_ld, const void* y, void* dy, float* dgate, int64_t dg_ld,
+                                 int64_t M, int D, int rows_per_sample) {
+    return op_gate_bwd("mi355_op_gate_bwd", stream, dx, gate, gate_ld, y, dy, dgate, dg_ld, M, D, rows_per_sample, 0);
+}
+// two-group gate table: head_rows > 0 = row m reads gate row 2 (m / rows_per_sample) + (m % rows_per_sample >= head_rows); refused together with dgate
+extern "C" int mi355_op_gate_bwd_split(void* stream, const void* dx, const void* gate, int64_t gate_ld, const void* y, void* dy, float* dgate,
+                                       int64_t dg_ld, int64_t M, int D, int rows_per_sample, int head_rows) {
+    return op_gate_bwd("mi355_op_gate_bwd_split", stream, dx, gate, gate_ld, y, dy, dgate, dg_ld, M, D, rows_per_sample, head_rows);
 }
 
 extern "C" int mi355_op_silu_bwd(void* stream, const void* dy, const void* pre, void* dx, int64_t n) {

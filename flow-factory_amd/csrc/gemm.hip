@@ -22,6 +22,15 @@ namespace mi355 {
 namespace {
 
 constexpr bool is_qk_epi(int e) { return e == EPI_QK_NORM || e == EPI_QK_NORM_RSTD; }
+constexpr bool is_gate_epi(int e) { return e == EPI_GATE_RES || e == EPI_GATE_RES_SPLIT; }
+// row of the gate table that token row m reads: its sample's row, or with the two-group split (EPI_GATE_RES_SPLIT, head_rows > 0) row
+// 2 b for the first head_rows tokens of sample b and row 2 b + 1 for the others.  SPLIT is a compile-time flag: the unsplit kernels keep their code
+template <bool SPLIT>
+__device__ __forceinline__ long gate_row(const GemmParams& p, int m) {
+    const int bi = m / p.rows_per_sample;
+    if constexpr (SPLIT) return 2L * bi + ((m - bi * p.rows_per_sample) >= p.head_rows ? 1 : 0);
+    else return bi;
+}
 
 
 constexpr int BK = 64;
@@ -164,9 +173,8 @@ __device__ __forceinline__ void store_row8(const GemmParams& p, int m, int n, in
                     y[e] += bf2f(ap[e]);
                     if constexpr (EPI == EPI_ADDSRC_SILU) y[e] = silu_f(round_bf16(y[e]));
                 }
-        } else if constexpr (EPI == EPI_GATE_RES) {
-            const int bi = m / p.rows_per_sample;
-            const bf16_t* gp = p.aux + (long)bi * p.ld_aux + n;
+        } else if constexpr (is_gate_epi(EPI)) {
+            const bf16_t* gp = p.aux + gate_row<EPI == EPI_GATE_RES_SPLIT>(p, m) * p.ld_aux + n;
             if (vec) {
                 const uint4 g = *(const uint4*)gp;
                 const uint4 x = *(const uint4*)op;
@@ -212,7 +220,7 @@ __device__ __forceinline__ void epilogue_part(const GemmParams& p, const f32x4 (
     const bool cok = NJ == 4 || (lane & 7) < 2 * NJ;          // row-layout phase: this lane's 8 columns belong to the chunk
     float4 bcol[NJ];
     float4 nw[NJ];
-    if constexpr (EPI == EPI_BIAS_GELU || EPI == EPI_GATE_RES) {
+    if constexpr (EPI == EPI_BIAS_GELU || is_gate_epi(EPI)) {
         // training-mode forward: the pre-activation (GELU) / the un-gated projection (gated residual) goes to the stash first (same wave-private staging, LDS ops of a wave are in order)
         if (p.stash) {
 #pragma unroll
@@ -322,7 +330,7 @@ __device__ __forceinline__ void epilogue_part(const GemmParams& p, const f32x4 (
         }
     }
     // wave-private region: a wave's LDS operations execute in order, no barrier needed
-    if constexpr (FULL && EPI == EPI_GATE_RES) {
+    if constexpr (FULL && is_gate_epi(EPI)) {
         // x += gate * y in place.  All LDS reads, then all global loads (the residual rows and the gate vectors), then arithmetic + stores:
         // written as one loop the compiler keeps load -> store -> load order (a row's store may alias the next row's load for all it
         // knows), i.e. NR * 2 exposed L2 round trips per call with nothing else to run on a SIMD whose waves are all in their epilogue.
@@ -338,7 +346,7 @@ __device__ __forceinline__ void epilogue_part(const GemmParams& p, const f32x4 (
             const int m = m_base + it * 8 + (lane >> 3), n = n_base + c * 8;
             if (cok) {
                 xr[it] = *(const uint4*)(p.out + (long)m * p.ldo + n);
-                gr[it] = *(const uint4*)(p.aux + (long)(m / p.rows_per_sample) * p.ld_aux + n);
+                gr[it] = *(const uint4*)(p.aux + gate_row<EPI == EPI_GATE_RES_SPLIT>(p, m) * p.ld_aux + n);
             }
         }
 #pragma unroll
@@ -1384,7 +1392,7 @@ hipError_t launch_epi(const GemmParams& p, hipStream_t stream) {
             const double cost_w6 = 3.0 * (double)((t192 + 255) / 256) * g_w6_alpha;
             if (g_w6_mode == 2 || (big >= g_pp_min_tiles && cost_pp <= cost_128 && cost_w6 < cost_pp && t192 >= g_w6_min_tiles)) return launch_w6<EPI>(p, stream);
         }
-        const bool w4_default = p.K <= g_w4_max_k && p.N >= 3072 && EPI != EPI_VT && EPI != EPI_GATE_RES && big >= g_w4_min_tiles;
+        const bool w4_default = p.K <= g_w4_max_k && p.N >= 3072 && EPI != EPI_VT && !is_gate_epi(EPI) && big >= g_w4_min_tiles;
         if ((g_gemm_variant == 2 || (g_gemm_variant == 1 && w4_default)) && big >= g_pp_min_tiles && w4_ok<EPI>(p) && cost_pp <= cost_128) {
             if constexpr (EPI == EPI_BIAS) {      // ablation builds of the hand-scheduled loop (scripts/gemm_ab.py): 33 no loads, 34 no fragment reads, 35 MFMA only
                 switch (p.dbg_skip_prefetch) {
@@ -1467,7 +1475,9 @@ static void trace_gemm(const GemmParams& p, hipStream_t stream) {
     const int rps = p.rows_per_sample > 0 ? p.rows_per_sample : 1;
     switch (p.epi) {
         case EPI_GATE_RES: {
-            const TraceRegion gate = treg(p.aux, ((size_t)((p.M + rps - 1) / rps - 1) * p.ld_aux + p.N) * 2), out = treg(p.out, out_bytes);
+            // one gate row per sample, two with the two-group split (head_rows > 0)
+            const size_t gate_rows = (size_t)((p.M + rps - 1) / rps) * (p.head_rows > 0 ? 2 : 1);
+            const TraceRegion gate = treg(p.aux, ((gate_rows - 1) * p.ld_aux + p.N) * 2), out = treg(p.out, out_bytes);
             sched_trace_launch("gemm.gate_res", stream, {A, W, bias, gate, out}, {out, stash});
             break;
         }
@@ -1508,6 +1518,7 @@ hipError_t launch_gemm(const GemmParams& p_in, hipStream_t stream) {
     if (sched_trace_on()) trace_gemm(p, stream);
     if (p.K % BK != 0 || p.M <= 0 || p.N <= 0) return hipErrorInvalidValue;
     if (p.epi == EPI_QK_NORM && (p.H < 1 || p.N != 2 * p.H * 64)) return hipErrorInvalidValue;      // q | k, whole heads: the scatter relies on it
+    if (p.head_rows < 0 || (p.head_rows > 0 && (p.epi != EPI_GATE_RES || p.head_rows > p.rows_per_sample))) return hipErrorInvalidValue;
     if (p.conv_cin > 0) {
         const int ks = p.conv_ks ? p.conv_ks : 3, kt3 = p.conv_kt ? p.conv_kt : 1;
         if (p.conv_cin % BK != 0 || p.K != kt3 * ks * ks * p.conv_cin || !p.zero_page || p.M % (p.conv_h * p.conv_w) != 0 ||
@@ -1527,7 +1538,7 @@ hipError_t launch_gemm(const GemmParams& p_in, hipStream_t stream) {
         case EPI_BIAS_GELU: return launch_epi<EPI_BIAS_GELU>(p, stream);
         case EPI_POSADD: return launch_epi<EPI_POSADD>(p, stream);
         case EPI_ADDSRC_SILU: return launch_epi<EPI_ADDSRC_SILU>(p, stream);
-        case EPI_GATE_RES: return launch_epi<EPI_GATE_RES>(p, stream);
+        case EPI_GATE_RES: return p.head_rows > 0 ? launch_epi<EPI_GATE_RES_SPLIT>(p, stream) : launch_epi<EPI_GATE_RES>(p, stream);
         case EPI_QK_NORM: return p.rstd_out ? launch_epi<EPI_QK_NORM_RSTD>(p, stream) : launch_epi<EPI_QK_NORM>(p, stream);
         case EPI_VT: return launch_epi<EPI_VT>(p, stream);
         case EPI_UNPATCH: return launch_epi<EPI_UNPATCH>(p, stream);

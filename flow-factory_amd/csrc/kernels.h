@@ -31,6 +31,8 @@ enum GemmEpi : int {
     // ---- backward (engine_train.inc)
     EPI_DGELU,          // out[m][n] = bf16(bf16(pre) * gelu_tanh'(aux[m][n]))   (aux = stashed pre-activation, row stride ld_aux)
     EPI_QK_NORM_RSTD,   // EPI_QK_NORM that also stores the per-(row, head) 1/rms to rstd_out (training-mode forward; selected by launch_gemm)
+    EPI_GATE_RES_SPLIT, // EPI_GATE_RES with two gate rows per sample: row m reads gate[2 (m / rows_per_sample) + (m % rows_per_sample >= head_rows)]
+                        // (selected by launch_gemm when head_rows > 0; its own kind so that the unsplit kernels keep their code)
     EPI_COUNT
 };
 
@@ -76,6 +78,9 @@ struct GemmParams {
     // optional s_memtime trace (debug): per workgroup, per tile 4 stamps {tile start, main loop start, main loop end, epilogue end}
     long long* trace;
     int dbg_skip_prefetch;    // debug ablation: the K-loop prefetches are not issued (results are garbage)
+    // EPI_GATE_RES, two-group modulation (Wan2.2-TI2V image-to-video: timestep 0 on the tokens of frame 0): > 0 = the first head_rows rows of every
+    // sample read gate row 2 b, the others row 2 b + 1 (row stride ld_aux); 0 = one row per sample
+    int head_rows;
 };
 
 // weight-gradient GEMM on row-major operands (gemm_tn.hip): out[n][k] (fp32, + split * split_stride) = sum_m A[m][n] * B[m][k]
@@ -263,6 +268,9 @@ struct LnModParams {
     const bf16_t* mod; long mod_ld;
     int shift_off, scale_off, shift2_off, scale2_off;
     int M, D, rows_per_sample; float eps;
+    // two-group modulation (Wan2.2-TI2V image-to-video): > 0 = the first head_rows rows of every sample read modulation row 2 b, the others row
+    // 2 b + 1 (the table then holds two rows per sample, same mod_ld); 0 = one row per sample
+    int head_rows = 0;
 };
 hipError_t launch_ln_mod(const LnModParams& p, hipStream_t stream);
 
@@ -273,6 +281,9 @@ hipError_t launch_patchify(const void* lat, int dt, bf16_t* patches, int B, int 
 // the same into columns col0 .. col0 + C*p*p of rows of `ld` elements (a channel range of a wider patch row); the other columns are not written
 hipError_t launch_patchify_cols(const void* lat, int dt, bf16_t* patches, int B, int rep, int C, int h, int w, int p, int col0, int ld,
                                 hipStream_t stream);
+// first-frame merge: the patches of ff [B][C][h][w] (storage dtype) overwrite rows [0, (h/p)*(w/p)) of every sample's `rps` rows of the dense patch
+// matrix [B*rep*rps][C*p*p] (all `rep` replicas); the other rows are not written
+hipError_t launch_patchify_head(const void* ff, int dt, bf16_t* patches, int B, int rep, int C, int h, int w, int p, int rps, hipStream_t stream);
 // pos_embed buffer [max*max][D] bf16 -> centre crop [hp*wp][D]
 hipError_t launch_pos_crop(const bf16_t* pos, bf16_t* out, int max_size, int hp, int wp, int D, hipStream_t stream);
 // sinusoidal timestep projection (cos first): out[r][dim] bf16, t rounded to `t_round_dt` first
@@ -322,10 +333,12 @@ struct LnModBwdParams {
     // optional: gradients of the modulation vectors, ADDED (fp32 atomics) into dmod[b * mod_ld + {shift,scale}_off + d]:
     // dshift = sum_tokens dy, dscale = sum_tokens dy * xhat  (and the same for the second modulated copy)
     float* dmod; int shift_off, shift2_off;
+    // two-group modulation: > 0 = the first head_rows rows of every sample read scale row 2 b, the others row 2 b + 1; refused together with dmod
+    int head_rows = 0;
 };
 hipError_t launch_ln_mod_bwd(const LnModBwdParams& p, hipStream_t stream);
-// dy[m][:] = gate[m / rps][:] * dx[m][:]
-hipError_t launch_gate_mul(const bf16_t* dx, const bf16_t* gate, long gate_ld, bf16_t* dy, long M, int D, int rps, hipStream_t stream);
+// dy[m][:] = gate[m / rps][:] * dx[m][:]; head_rows > 0 (two-group modulation): gate row 2 (m / rps) + (m % rps >= head_rows)
+hipError_t launch_gate_mul(const bf16_t* dx, const bf16_t* gate, long gate_ld, bf16_t* dy, long M, int D, int rps, hipStream_t stream, int head_rows = 0);
 // the same plus dgate[b][n] += sum_{m in sample b} dx[m][n] * y[m][n]  (y = the stashed un-gated projection; fp32 atomics into dgate, row stride dg_ld)
 hipError_t launch_gate_bwd(const bf16_t* dx, const bf16_t* gate, long gate_ld, const bf16_t* y, bf16_t* dy, float* dgate, long dg_ld, long M, int D,
                            int rps, hipStream_t stream);

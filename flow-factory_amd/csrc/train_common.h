@@ -356,12 +356,14 @@ struct TrainChain {
     bf16_t *g1, *g2, *g3, *wide, *hid;
     bool side;
 };
-struct ModRows { const bf16_t* mod; long ld; float eps; };     // the step's modulation rows [B][ld] and the LayerNorm epsilon
+// the step's modulation rows [B][ld] and the LayerNorm epsilon; head_rows > 0: two rows per sample [2 B][ld], the first head_rows rows of a sample
+// read row 2 b, the others row 2 b + 1 (Wan2.2-TI2V image-to-video; no modulation gradients)
+struct ModRows { const bf16_t* mod; long ld; float eps; int head_rows = 0; };
 
 // d res (+)= LNmod'(x)(dy): backward of the modulated LayerNorm (shift / scale at columns shift_off / scale_off of the modulation rows)
 static inline int t_ln_back(const TrainChain& c, const ModRows& m, int D, const bf16_t* x, const bf16_t* dy, bf16_t* dres, int shift_off, int scale_off,
                             int accumulate) {
-    LnModBwdParams l{x, dy, nullptr, dres, m.mod, m.ld, scale_off, 0, c.M, D, c.rps, m.eps, accumulate, nullptr, shift_off, 0};
+    LnModBwdParams l{x, dy, nullptr, dres, m.mod, m.ld, scale_off, 0, c.M, D, c.rps, m.eps, accumulate, nullptr, shift_off, 0, m.head_rows};
     HIPCHK(launch_ln_mod_bwd(l, c.st));
     return 0;
 }
@@ -380,7 +382,7 @@ static inline int t_linear_back(TrainScratch& t, const TrainChain& c, const bf16
 static inline int t_mlp_back(TrainScratch& t, const TrainChain& c, const ModRows& m, int m0, int D, int F, bf16_t* dres, const bf16_t* x_mid,
                              const bf16_t* xn, const bf16_t* pre, const bf16_t* w1T, const bf16_t* w2T, LinGrad g1, LinGrad g2) {
     bf16_t* dpre = c.wide + (size_t)c.M * 3 * D;          // [M][F] behind the [M][3D] q|k|v gradient
-    HIPCHK(launch_gate_mul(dres, m.mod + m0 + 5 * D, m.ld, c.g1, c.M, D, c.rps, c.st));
+    HIPCHK(launch_gate_mul(dres, m.mod + m0 + 5 * D, m.ld, c.g1, c.M, D, c.rps, c.st, m.head_rows));
     if (g2.w) HIPCHK(launch_gelu_fwd(pre, c.hid, (long)c.M * F, c.st));
     CHK(t_linear_back(t, c, c.g1, D, D, c.hid, F, F, w2T, g2, dpre, F, pre, F));
     CHK(t_linear_back(t, c, dpre, F, F, xn, D, D, w1T, g1, c.g3, D));

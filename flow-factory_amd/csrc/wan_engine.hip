@@ -22,6 +22,13 @@
 // WanTransformer3DModel, parity unpinned): condition_embedder.image_embedder on the CLIP hidden states and every block's image K / V^T once
 // per call (prepare_image); per block the text cross-attention's queries attend to the image keys as well, and attn2.to_out.0 reads
 // bf16(bf16(o_text) + bf16(o_img)) -- the attention epilogue's optional addend in the rollout, separate outputs plus one add in training mode.
+//
+// First-frame image-to-video (Wan2.2-TI2V-5B, `expand_timesteps`; mi355_wan_plan_create_ff and the *_ff entry points; reference
+// models/wan/wan2_i2v.py:736-741): the transformer input is (1 - mask) * condition + mask * latents -- frame 0 replaced by the encoded image -- and
+// the timestep is per TOKEN: 0 on the tokens of frame 0, t elsewhere.  Patchify orders tokens (frame, y, x), so frame 0 is the first
+// head_rows = hp * wp rows of every sample: a two-group modulation.  The conditioning buffers hold two rows per sample (t_head, t_rest), and
+// ln_mod / the gated-residual epilogue pick row 2 b + (row % S >= head_rows) in the kernel (their split instantiations).  The merge is one small
+// kernel behind the per-step patchify (launch_patchify_head).  The scheduler step and the log-prob run over ALL latents, frame 0 included.
 #include <math.h>
 #include <algorithm>
 #include <stdio.h>
@@ -221,15 +228,30 @@ struct mi355_wan_plan {
     int Ni = 0, Ni_pad = 0;             // image branch: CLIP image tokens per sample (0 = none), padded to 64
     bf16_t *ie_n = nullptr, *ie_h = nullptr, *ie_o = nullptr, *ictx = nullptr, *kvbuf3 = nullptr, *ki = nullptr, *vTi = nullptr;
     PlanTrain* train = nullptr;         // training workspace (wan_train.inc: mi355_wan_train), created by the first training-mode forward
+    // first-frame plan (mi355_wan_plan_create_ff): head_rows = hp * wp tokens of frame 0 per sample, groups = 2 modulation rows per sample (1 otherwise)
+    int head_rows = 0, groups = 1;
+    char* io_ff = nullptr;              // the rollout's staged first frame [B][C][1][h][w] (up to fp32)
+    const void* ff = nullptr;           // the first frame the current call merges into the patch rows, and its dtype
+    int ff_dt = 0;
 };
 
 static int wan_plan_create(mi355_wan* e, int batch, int n_cfg, int latent_t, int latent_h, int latent_w, int n_text, int n_image, int max_steps,
-                           mi355_wan_plan** out);
+                           mi355_wan_plan** out, bool first_frame = false);
 
 extern "C" int mi355_wan_plan_create(mi355_wan* e, int batch, int n_cfg, int latent_t, int latent_h, int latent_w, int n_text,
                                      int max_steps, mi355_wan_plan** out) {
     if (e && e->Cc) return errorf("mi355_wan_plan_create: image-to-video engine (mi355_wan_create_i2v): use mi355_wan_plan_create_i2v");
     return wan_plan_create(e, batch, n_cfg, latent_t, latent_h, latent_w, n_text, 0, max_steps, out);
+}
+
+// first-frame plan of a text-to-video engine (cond_channels == 0, no image branch): frame 0 of the transformer input is the encoded image and
+// carries its own timestep; served by the *_ff entry points only
+extern "C" int mi355_wan_plan_create_ff(mi355_wan* e, int batch, int n_cfg, int latent_t, int latent_h, int latent_w, int n_text, int max_steps,
+                                        mi355_wan_plan** out) {
+    if (e && (e->Cc || e->Di))
+        return errorf("mi355_wan_plan_create_ff: image-to-video engine (mi355_wan_create_i2v): the first-frame mode needs an engine of mi355_wan_create; "
+                      "use mi355_wan_plan_create_i2v");
+    return wan_plan_create(e, batch, n_cfg, latent_t, latent_h, latent_w, n_text, 0, max_steps, out, true);
 }
 
 // n_image: CLIP image tokens per sample of the image cross-attention branch (257); 0 = none (the only value on an engine with image_dim == 0)
@@ -243,7 +265,7 @@ extern "C" int mi355_wan_plan_create_i2v(mi355_wan* e, int batch, int n_cfg, int
 }
 
 static int wan_plan_create(mi355_wan* e, int batch, int n_cfg, int latent_t, int latent_h, int latent_w, int n_text, int n_image, int max_steps,
-                           mi355_wan_plan** out) {
+                           mi355_wan_plan** out, bool first_frame) {
     if (!e || !out) return errorf("mi355_wan_plan_create: null argument");
     if (batch < 1 || (n_cfg != 1 && n_cfg != 2) || latent_t < 1 || latent_h < 2 || latent_w < 2 || ((latent_h | latent_w) & 1) ||
         n_text < 1 || max_steps < 1)
@@ -254,10 +276,11 @@ static int wan_plan_create(mi355_wan* e, int batch, int n_cfg, int latent_t, int
     p->Nt = n_text; p->Nt_pad = (n_text + 63) / 64 * 64; p->M = p->Bp * p->S; p->Mc = p->Bp * n_text; p->max_steps = max_steps;
     p->n_lat = (int64_t)e->cfg.in_channels * latent_t * latent_h * latent_w;
     p->Ni = n_image; p->Ni_pad = (n_image + 63) / 64 * 64;
+    if (first_frame) { p->head_rows = p->hp * p->wp; p->groups = 2; }
     if ((int64_t)p->Bp * p->S > 0x7fffffffLL / 2) { delete p; return errorf("mi355_wan_plan_create: too many tokens"); }
     const int D = e->D, F = e->F;
     p->mod_cols = e->L * 6 * D + 2 * D;
-    const int64_t rows_cond = (int64_t)max_steps * p->Bp;
+    const int64_t rows_cond = (int64_t)max_steps * p->Bp * p->groups;
     const int64_t qk_el = (int64_t)p->Bp * e->H * p->S_pad * 128;
     const int64_t kx_el = (int64_t)p->Bp * e->H * p->Nt_pad * 128;
     const int64_t nl = (int64_t)batch * p->n_lat;
@@ -278,6 +301,7 @@ static int wan_plan_create(mi355_wan* e, int batch, int n_cfg, int latent_t, int
         c.take(p->ie_n, ri * e->Di); c.take(p->ie_h, ri * e->Di); c.take(p->ie_o, ri * D); c.take(p->ictx, ri * D); c.take(p->kvbuf3, ri * D);
         c.take(p->ki, ki_el * e->L); c.take(p->vTi, ki_el * e->L);
     }
+    if (first_frame) c.take(p->io_ff, (int64_t)batch * e->cfg.in_channels * latent_h * latent_w * 4);
     c.take(p->max2, (int64_t)2 * p->Bp * e->H); c.take(p->max2_part, (int64_t)p->Bp * norm_rope_parts(p->S) * e->H);
     // zeroed: the padded key rows / columns of q, k, vT, kx, vTx must stay finite; image-to-video: the padding columns KPr .. KP of `patches` stay zero
     if (c.alloc(&p->ws, &p->ws_bytes, true, "mi355_wan_plan_create") != 0) { delete p; return 1; }
@@ -356,12 +380,13 @@ int refresh_derived(mi355_wan* e, hipStream_t st) {
     return 0;
 }
 
+// head_rows: the plan's for the step's modulation table (two rows per sample on a first-frame plan), 0 for a LayerNorm's own affine rows
 int ln_mod(mi355_wan_plan* p, hipStream_t st, const bf16_t* x, bf16_t* out, const bf16_t* mod, long mod_ld, int M, int rps, int shift_off,
-           int scale_off) {
+           int scale_off, int head_rows = 0) {
     LnModParams l;
     memset(&l, 0, sizeof(l));
     l.x = x; l.out = out; l.mod = mod; l.mod_ld = mod_ld; l.shift_off = shift_off; l.scale_off = scale_off;
-    l.M = M; l.D = p->e->D; l.rows_per_sample = rps; l.eps = p->e->cfg.eps;
+    l.M = M; l.D = p->e->D; l.rows_per_sample = rps; l.eps = p->e->cfg.eps; l.head_rows = head_rows;
     HIPCHK(launch_ln_mod(l, st));
     return 0;
 }
@@ -388,7 +413,7 @@ int vt_proj(mi355_wan_plan* p, hipStream_t st, const bf16_t* w_v, const float* b
 int gate_res(mi355_wan_plan* p, hipStream_t st, const bf16_t* A, int K, const bf16_t* W, const float* bias, bf16_t* x, int M, int rps,
              const bf16_t* mod, int gate_off) {
     GemmParams g = make_gemm(A, K, W, K, M, p->e->D, K, EPI_GATE_RES, bias, x, p->e->D);
-    g.aux = mod + gate_off; g.ld_aux = p->mod_cols; g.rows_per_sample = rps;
+    g.aux = mod + gate_off; g.ld_aux = p->mod_cols; g.rows_per_sample = rps; g.head_rows = p->head_rows;
     HIPCHK(launch_gemm(g, st));
     return 0;
 }
@@ -456,7 +481,7 @@ int prepare_image(mi355_wan_plan* p, hipStream_t st, const void* image_embeds) {
 int prepare_conditioning(mi355_wan_plan* p, hipStream_t st, int nsteps) {
     mi355_wan* e = p->e;
     const int D = e->D, T = e->cfg.freq_dim;
-    const int rows = nsteps * p->Bp;
+    const int rows = nsteps * p->Bp * p->groups;       // first-frame plan: (t_head, t_rest) per sample
     HIPCHK(launch_time_proj(p->t_dev, rows, T, DT_F32, p->tproj_in, st));
     GemmParams g1 = make_gemm(p->tproj_in, T, e->w_t1, T, rows, D, T, EPI_BIAS_SILU, e->b_t1, p->h1, D);
     HIPCHK(launch_gemm(g1, st));
@@ -490,6 +515,8 @@ int forward_core(mi355_wan_plan* p, hipStream_t st, const void* latents, int lat
         HIPCHK(launch_patchify_cols(latents, lat_dt, p->patches, p->B, p->ncfg, e->cfg.in_channels, p->T * p->h, p->w, 2, 0, e->KP, st));
     else
         HIPCHK(launch_patchify(latents, lat_dt, p->patches, p->B, p->ncfg, e->cfg.in_channels, p->T * p->h, p->w, 2, st));
+    if (p->head_rows)     // first-frame plan: (1 - mask) * condition + mask * latents, done on the patch rows of frame 0
+        HIPCHK(launch_patchify_head(p->ff, p->ff_dt, p->patches, p->B, p->ncfg, e->cfg.in_channels, p->h, p->w, 2, S, st));
     GemmParams g0 = make_gemm(p->patches, e->KP, e->w_patch, e->KP, M, D, e->KP, EPI_BIAS, e->b_patch, p->x, D);
     HIPCHK(launch_gemm(g0, st));
     for (int i = 0; i < e->L; ++i) {
@@ -499,7 +526,7 @@ int forward_core(mi355_wan_plan* p, hipStream_t st, const void* latents, int lat
         // ---- self-attention
         bf16_t* xn1 = k ? k->xn1 : p->xn;
         if (k) HIPCHK(copy_d2d(k->x_in, p->x, x_b, st));
-        CHK(ln_mod(p, st, p->x, xn1, mod, p->mod_cols, M, S, m0, m0 + D));
+        CHK(ln_mod(p, st, p->x, xn1, mod, p->mod_cols, M, S, m0, m0 + D, p->head_rows));
         GemmParams gq = make_gemm(xn1, D, b.w_qk, D, M, 2 * D, D, EPI_BIAS, b.b_qk, p->qkbuf, 2 * D);
         HIPCHK(launch_gemm(gq, st));
         // self-attention score bound from the data (the weights prove none: RMSNorm across heads): largest stored row norm per (b, h)
@@ -559,7 +586,7 @@ int forward_core(mi355_wan_plan* p, hipStream_t st, const void* latents, int lat
         // ---- feed-forward
         bf16_t* xn3 = k ? k->xn3 : p->xn;
         if (k) HIPCHK(copy_d2d(k->x_mid2, p->x, x_b, st));
-        CHK(ln_mod(p, st, p->x, xn3, mod, p->mod_cols, M, S, m0 + 3 * D, m0 + 4 * D));
+        CHK(ln_mod(p, st, p->x, xn3, mod, p->mod_cols, M, S, m0 + 3 * D, m0 + 4 * D, p->head_rows));
         GemmParams f1 = make_gemm(xn3, D, b.w_ff1, D, M, F, D, EPI_BIAS_GELU, b.b_ff1, p->hid, F);
         if (k) { f1.stash = k->pre; f1.ld_stash = F; }
         HIPCHK(launch_gemm(f1, st));
@@ -567,7 +594,7 @@ int forward_core(mi355_wan_plan* p, hipStream_t st, const void* latents, int lat
     }
     if (x_final) HIPCHK(copy_d2d(x_final, p->x, x_b, st));
     const int mo = e->L * 6 * D;         // output modulation: shift, scale
-    CHK(ln_mod(p, st, p->x, p->xn, mod, p->mod_cols, M, S, mo, mo + D));
+    CHK(ln_mod(p, st, p->x, p->xn, mod, p->mod_cols, M, S, mo, mo + D, p->head_rows));
     GemmParams g = make_gemm(p->xn, D, e->w_proj, D, M, e->NO, D, EPI_UNPATCH, e->b_proj, v_out, 0);
     g.hp = p->T * p->hp; g.wp = p->wp; g.patch = 2; g.out_ch = e->cfg.out_channels;
     HIPCHK(launch_gemm(g, st));
@@ -575,8 +602,17 @@ int forward_core(mi355_wan_plan* p, hipStream_t st, const void* latents, int lat
 }
 
 // which entry points serve which plan, and the image-to-video arguments: checks only, nothing is launched
-int check_kind(mi355_wan_plan* p, const char* who, bool i2v, const void* condition, int cond_dt, const void* image_embeds) {
+int check_kind(mi355_wan_plan* p, const char* who, bool i2v, const void* condition, int cond_dt, const void* image_embeds, bool ff = false,
+               const void* first_frame = nullptr, int ff_dt = 0) {
     mi355_wan* e = p->e;
+    if (ff) {
+        if (e->Cc) return errorf("%s_ff: image-to-video plan: use %s_i2v (the transformer input has %d condition channels)", who, who, e->Cc);
+        if (!p->head_rows) return errorf("%s_ff: text-to-video plan: use %s (or create the plan with mi355_wan_plan_create_ff)", who, who);
+        if (!first_frame) return errorf("%s_ff: first_frame is NULL", who);
+        if (ff_dt < 0 || ff_dt > 2) return errorf("%s_ff: bad first_frame dtype %d", who, ff_dt);
+        return 0;
+    }
+    if (p->head_rows) return errorf("%s%s: first-frame plan (mi355_wan_plan_create_ff): use %s_ff", who, i2v ? "_i2v" : "", who);
     if (!i2v) {
         if (e->Cc) return errorf("%s: image-to-video plan: use %s_i2v (the transformer input has %d condition channels)", who, who, e->Cc);
         return 0;
@@ -607,15 +643,18 @@ namespace mi355 { void set_wan_data_bound(int v) { g_wan_data_bound = v != 0; } 
 // transformer only (tests / replay): t[Bp] device fp32 = the timestep values the network embeds; enc_b == NULL when n_cfg == 1.
 // With n_cfg == 2 the forward batch is [enc_a (negative), enc_b (positive)] on replicated latents, v_out holds both halves.
 static int wan_forward(mi355_wan_plan* p, void* stream, const void* latents, int lat_dtype, const float* t, const void* enc_a, const void* enc_b,
-                       void* v_out, bool i2v, const void* condition, int cond_dtype, const void* image_embeds) {
-    if (!p || !latents || !t || !enc_a || !v_out) return errorf("mi355_wan_forward: null argument");
-    if (lat_dtype < 0 || lat_dtype > 2) return errorf("mi355_wan_forward: bad latent dtype %d", lat_dtype);
+                       void* v_out, bool i2v, const void* condition, int cond_dtype, const void* image_embeds, bool ff = false,
+                       const void* first_frame = nullptr, int ff_dtype = 0) {
+    const char* who = ff ? "mi355_wan_forward_ff" : "mi355_wan_forward";      // the entry point the messages name
+    if (!p || !latents || !t || !enc_a || !v_out) return errorf("%s: null argument", who);
+    if (lat_dtype < 0 || lat_dtype > 2) return errorf("%s: bad latent dtype %d", who, lat_dtype);
     hipStream_t st = (hipStream_t)stream;
-    CHK(check_kind(p, "mi355_wan_forward", i2v, condition, cond_dtype, image_embeds));
+    CHK(check_kind(p, "mi355_wan_forward", i2v, condition, cond_dtype, image_embeds, ff, first_frame, ff_dtype));
     CHK(mi355_wan_weights_ready(p->e));
     CHK(refresh_derived(p->e, st));
     CHK(write_i2v_inputs(p, st, condition, cond_dtype, image_embeds));
-    HIPCHK(hipMemcpyAsync(p->t_dev, t, (size_t)p->Bp * 4, hipMemcpyDeviceToDevice, st));
+    p->ff = first_frame; p->ff_dt = ff_dtype;
+    HIPCHK(hipMemcpyAsync(p->t_dev, t, (size_t)p->Bp * p->groups * 4, hipMemcpyDeviceToDevice, st));
     CHK(prepare_prompt(p, st, enc_a, enc_b));
     CHK(prepare_conditioning(p, st, 1));
     return forward_core(p, st, latents, lat_dtype, p->mod_all, (bf16_t*)v_out);
@@ -630,6 +669,12 @@ extern "C" int mi355_wan_forward_i2v(mi355_wan_plan* p, void* stream, const void
                                      const void* enc_b, const void* condition, int cond_dtype, const void* image_embeds, void* v_out) {
     return wan_forward(p, stream, latents, lat_dtype, t, enc_a, enc_b, v_out, true, condition, cond_dtype, image_embeds);
 }
+// first-frame plan: t [batch*n_cfg][2] = (t_head, t_rest) per forward sample -- the timestep of the tokens of frame 0 and of all others (the
+// reference passes (0, t)); first_frame [batch][in_channels][1][h][w] (ff_dtype: MI355_F32 / BF16 / F16) replaces frame 0 of the transformer input
+extern "C" int mi355_wan_forward_ff(mi355_wan_plan* p, void* stream, const void* latents, int lat_dtype, const float* t, const void* enc_a,
+                                    const void* enc_b, const void* first_frame, int ff_dtype, void* v_out) {
+    return wan_forward(p, stream, latents, lat_dtype, t, enc_a, enc_b, v_out, false, nullptr, 0, nullptr, true, first_frame, ff_dtype);
+}
 
 // The loop runs as eager launches: replaying it as ONE hipGraph (the SD3.5 / FLUX.1 / Qwen-Image engines do) was measured in round 3 at the
 // reference's example shape (240 x 240 x 5 frames, B = 1, CFG) and at 480 x 832 x 17 -- bit-identical, -0.1 % / -0.3 %
@@ -641,26 +686,34 @@ static int wan_rollout(mi355_wan_plan* p, void* stream, int n_steps, const float
                        const float* noise_levels_host, int dynamics, float guidance, const void* init_latents, int init_dtype,
                        int storage_dtype, const float* step_noise, const void* prompt_embeds, const void* neg_embeds,
                        const int32_t* keep_slot_host, void* out_latents, float* out_log_probs, void* out_final,
-                       int compute_log_prob, bool i2v, const void* condition, int cond_dtype, const void* image_embeds) {
+                       int compute_log_prob, bool i2v, const void* condition, int cond_dtype, const void* image_embeds, bool ff = false,
+                       const void* first_frame = nullptr, int ff_dtype = 0) {
+    const char* who = ff ? "mi355_wan_rollout_ff" : "mi355_wan_rollout";      // the entry point the messages name
     if (!p || !timesteps_host || !sigmas_host || !noise_levels_host || !init_latents || !prompt_embeds)
-        return errorf("mi355_wan_rollout: null argument");
-    CHK(check_kind(p, "mi355_wan_rollout", i2v, condition, cond_dtype, image_embeds));
-    if (n_steps < 1 || n_steps > p->max_steps) return errorf("mi355_wan_rollout: n_steps %d exceeds the plan's max_steps %d", n_steps, p->max_steps);
-    if (storage_dtype < 0 || storage_dtype > 2 || init_dtype < 0 || init_dtype > 2) return errorf("mi355_wan_rollout: bad dtype");
-    if (p->ncfg == 2 && !neg_embeds) return errorf("mi355_wan_rollout: plan has n_cfg == 2 but no negative prompt embeddings");
-    if (!step_noise && dynamics != MI355_ODE) return errorf("mi355_wan_rollout: step_noise is NULL");
-    if (dynamics < 0 || dynamics > 3) return errorf("mi355_wan_rollout: unknown dynamics %d", dynamics);
+        return errorf("%s: null argument", who);
+    CHK(check_kind(p, "mi355_wan_rollout", i2v, condition, cond_dtype, image_embeds, ff, first_frame, ff_dtype));
+    if (n_steps < 1 || n_steps > p->max_steps) return errorf("%s: n_steps %d exceeds the plan's max_steps %d", who, n_steps, p->max_steps);
+    if (storage_dtype < 0 || storage_dtype > 2 || init_dtype < 0 || init_dtype > 2) return errorf("%s: bad dtype", who);
+    if (p->ncfg == 2 && !neg_embeds) return errorf("%s: plan has n_cfg == 2 but no negative prompt embeddings", who);
+    if (!step_noise && dynamics != MI355_ODE) return errorf("%s: step_noise is NULL", who);
+    if (dynamics < 0 || dynamics > 3) return errorf("%s: unknown dynamics %d", who, dynamics);
     hipStream_t st = (hipStream_t)stream;
     CHK(mi355_wan_weights_ready(p->e));
     CHK(refresh_derived(p->e, st));
     CHK(write_i2v_inputs(p, st, condition, cond_dtype, image_embeds));      // once per rollout, not once per step
-    const int B = p->B, Bp = p->Bp;
+    const int B = p->B, Bp = p->Bp, G = p->groups;
     std::vector<float>& tt = p->host_t;
     std::vector<float>& sc = p->host_sc;
-    tt.assign((size_t)n_steps * Bp, 0.f);
+    tt.assign((size_t)n_steps * Bp * G, 0.f);
     sc.assign(3 * (size_t)p->max_steps, 0.f);
+    if (ff) {      // staged once per rollout; every step merges it into the patch rows of frame 0
+        HIPCHK(hipMemcpyAsync(p->io_ff, first_frame, (size_t)B * p->e->cfg.in_channels * p->h * p->w * (ff_dtype == MI355_F32 ? 4 : 2),
+                              hipMemcpyDeviceToDevice, st));
+        p->ff = p->io_ff; p->ff_dt = ff_dtype;
+    }
     for (int i = 0; i < n_steps; ++i) {
-        for (int j = 0; j < Bp; ++j) tt[(size_t)i * Bp + j] = timesteps_host[i];     // timestep = t.expand(B) (wan2_t2v.py:499)
+        // timestep = t.expand(B) (wan2_t2v.py:499); first-frame plan: first_frame_mask * t = (0, t) per sample (wan2_i2v.py:740-741)
+        for (int j = 0; j < Bp * G; ++j) tt[(size_t)i * Bp * G + j] = (G == 2 && !(j & 1)) ? 0.f : timesteps_host[i];
         const float t_next = (i + 1 < n_steps) ? timesteps_host[i + 1] : 0.0f;
         sc[i] = timesteps_host[i] / 1000.0f;
         sc[p->max_steps + i] = t_next / 1000.0f;
@@ -686,7 +739,7 @@ static int wan_rollout(mi355_wan_plan* p, void* stream, int n_steps, const float
         CHK(prepare_conditioning(p, sx, n_steps));
         HIPCHK(launch_convert(p->io_init, init_dtype, p->io_traj, storage_dtype, (long)nl, sx));      // cast_latents(init)
         for (int i = 0; i < n_steps; ++i) {
-            const bf16_t* mod = p->mod_all + (int64_t)i * Bp * p->mod_cols;
+            const bf16_t* mod = p->mod_all + (int64_t)i * Bp * G * p->mod_cols;
             char* cur = p->io_traj + (size_t)i * lat_bytes;
             char* nxt = p->io_traj + (size_t)(i + 1) * lat_bytes;
             CHK(forward_core(p, sx, cur, storage_dtype, mod, p->v));
@@ -735,6 +788,17 @@ extern "C" int mi355_wan_rollout_i2v(mi355_wan_plan* p, void* stream, int n_step
     return wan_rollout(p, stream, n_steps, timesteps_host, sigmas_host, noise_levels_host, dynamics, guidance, init_latents, init_dtype, storage_dtype,
                        step_noise, prompt_embeds, neg_embeds, keep_slot_host, out_latents, out_log_probs, out_final, compute_log_prob, true, condition,
                        cond_dtype, image_embeds);
+}
+// first-frame plan: the fused N-step loop with first_frame [batch][in_channels][1][h][w] staged once; per step the network sees frame 0 replaced
+// and the timesteps (0, t_i); the scheduler step and the log-prob run over all latents (frame 0 included), on the unmerged latents
+extern "C" int mi355_wan_rollout_ff(mi355_wan_plan* p, void* stream, int n_steps, const float* timesteps_host, const float* sigmas_host,
+                                    const float* noise_levels_host, int dynamics, float guidance, const void* init_latents, int init_dtype,
+                                    int storage_dtype, const float* step_noise, const void* prompt_embeds, const void* neg_embeds,
+                                    const int32_t* keep_slot_host, void* out_latents, float* out_log_probs, void* out_final,
+                                    int compute_log_prob, const void* first_frame, int ff_dtype) {
+    return wan_rollout(p, stream, n_steps, timesteps_host, sigmas_host, noise_levels_host, dynamics, guidance, init_latents, init_dtype, storage_dtype,
+                       step_noise, prompt_embeds, neg_embeds, keep_slot_host, out_latents, out_log_probs, out_final, compute_log_prob, false, nullptr, 0,
+                       nullptr, true, first_frame, ff_dtype);
 }
 
 #include "wan_train.inc"

@@ -109,7 +109,7 @@ static int wan_train_of(mi355_wan_plan* p, mi355_wan_train** out) {
         if (p->Ni) { c.take(k.o3, (int64_t)M * D); c.take(k.o23, (int64_t)M * D); c.take(k.lse3, bhs); }
     }
     if (p->Ni) { c.take(t->ki, ki_el * L); c.take(t->vTi, ki_el * L); c.take(t->dq_img, qk_el); }
-    c.take(t->x_final, (int64_t)M * D); c.take(t->mod, (int64_t)p->Bp * p->mod_cols);
+    c.take(t->x_final, (int64_t)M * D); c.take(t->mod, (int64_t)p->Bp * p->groups * p->mod_cols);
     c.take(t->kx, kx_el * L); c.take(t->vTx, kx_el * L); c.take(t->ctx, (int64_t)Mc * D); c.take(t->rstd_kx, (int64_t)L * Mc);
     c.take(t->dx, (int64_t)M * D); c.take(t->dproj, (int64_t)M * NO); c.take(t->widec, (int64_t)Mc * 2 * D);
     c.take(sc.g1, (int64_t)M * D); c.take(sc.g2, (int64_t)M * D); c.take(sc.g3, (int64_t)M * D);
@@ -132,22 +132,25 @@ static int wan_train_of(mi355_wan_plan* p, mi355_wan_train** out) {
 
 // arguments as mi355_wan_forward; v_out [Bp][C][T][h][w] bf16 (both CFG halves)
 static int wan_forward_train(mi355_wan_plan* p, void* stream, const void* latents, int lat_dtype, const float* t_in, const void* enc_a,
-                             const void* enc_b, void* v_out, bool i2v, const void* condition, int cond_dtype, const void* image_embeds) {
-    if (!p || !latents || !t_in || !enc_a || !v_out) return errorf("mi355_wan_forward_train: null argument");
-    if (lat_dtype < 0 || lat_dtype > 2) return errorf("mi355_wan_forward_train: bad latent dtype %d", lat_dtype);
+                             const void* enc_b, void* v_out, bool i2v, const void* condition, int cond_dtype, const void* image_embeds, bool ff = false,
+                             const void* first_frame = nullptr, int ff_dtype = 0) {
+    const char* who = ff ? "mi355_wan_forward_train_ff" : "mi355_wan_forward_train";      // the entry point the messages name
+    if (!p || !latents || !t_in || !enc_a || !v_out) return errorf("%s: null argument", who);
+    if (lat_dtype < 0 || lat_dtype > 2) return errorf("%s: bad latent dtype %d", who, lat_dtype);
     hipStream_t st = (hipStream_t)stream;
     // (image-to-video: the backward reads nothing below blocks.0 -- the patch embedder is frozen and block 0's input is stashed -- so the
     //  condition columns of the plan's patch buffer need no copy in the training stash, a deliberate difference from the image K / V^T below,
     //  which the backward does read: a later no-grad forward may overwrite the plan's patch buffer freely)
-    CHK(check_kind(p, "mi355_wan_forward_train", i2v, condition, cond_dtype, image_embeds));
+    CHK(check_kind(p, "mi355_wan_forward_train", i2v, condition, cond_dtype, image_embeds, ff, first_frame, ff_dtype));
     CHK(mi355_wan_weights_ready(p->e));
     CHK(refresh_derived(p->e, st));
     mi355_wan_train* t = nullptr;
     CHK(wan_train_of(p, &t));
     mi355_wan* e = p->e;
     const int64_t kx_el = (int64_t)p->Bp * e->H * p->Nt_pad * 128;
-    HIPCHK(hipMemcpyAsync(p->t_dev, t_in, (size_t)p->Bp * 4, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(p->t_dev, t_in, (size_t)p->Bp * p->groups * 4, hipMemcpyDeviceToDevice, st));
     CHK(write_i2v_inputs(p, st, condition, cond_dtype, image_embeds));
+    p->ff = first_frame; p->ff_dt = ff_dtype;      // (first-frame plan: like the condition columns, the merged patch rows need no copy in the stash)
     CHK(prepare_prompt(p, st, enc_a, enc_b, t->rstd_kx));
     CHK(prepare_conditioning(p, st, 1));
     // this step's cross-attention k / v, text context and modulation rows: the plan's own copies may be overwritten by a no-grad forward on other
@@ -155,7 +158,7 @@ static int wan_forward_train(mi355_wan_plan* p, void* stream, const void* latent
     HIPCHK(copy_d2d(t->kx, p->kx, (size_t)kx_el * e->L * 2, st));
     HIPCHK(copy_d2d(t->vTx, p->vTx, (size_t)kx_el * e->L * 2, st));
     HIPCHK(copy_d2d(t->ctx, p->ctx, (size_t)p->Mc * e->D * 2, st));
-    HIPCHK(copy_d2d(t->mod, p->mod_all, (size_t)p->Bp * p->mod_cols * 2, st));
+    HIPCHK(copy_d2d(t->mod, p->mod_all, (size_t)p->Bp * p->groups * p->mod_cols * 2, st));
     if (p->Ni) {
         const size_t ki_b = (size_t)p->Bp * e->H * p->Ni_pad * 128 * e->L * 2;
         HIPCHK(copy_d2d(t->ki, p->ki, ki_b, st));
@@ -174,6 +177,11 @@ extern "C" int mi355_wan_forward_train(mi355_wan_plan* p, void* stream, const vo
 extern "C" int mi355_wan_forward_train_i2v(mi355_wan_plan* p, void* stream, const void* latents, int lat_dtype, const float* t_in, const void* enc_a,
                                            const void* enc_b, const void* condition, int cond_dtype, const void* image_embeds, void* v_out) {
     return wan_forward_train(p, stream, latents, lat_dtype, t_in, enc_a, enc_b, v_out, true, condition, cond_dtype, image_embeds);
+}
+// arguments as mi355_wan_forward_ff; mi355_wan_backward reads the plan's head_rows (the stashed modulation table holds two rows per sample)
+extern "C" int mi355_wan_forward_train_ff(mi355_wan_plan* p, void* stream, const void* latents, int lat_dtype, const float* t_in, const void* enc_a,
+                                          const void* enc_b, const void* first_frame, int ff_dtype, void* v_out) {
+    return wan_forward_train(p, stream, latents, lat_dtype, t_in, enc_a, enc_b, v_out, false, nullptr, 0, nullptr, true, first_frame, ff_dtype);
 }
 
 // d loss / d weights from dv = d loss / d v_out [Bp][C][T][h][w] fp32 (v_out = the prediction of the LAST mi355_wan_forward_train on this plan)
@@ -194,7 +202,7 @@ extern "C" int mi355_wan_backward(mi355_wan_plan* p, void* stream, const float* 
     const AttnGeom ag_cross{p->Bp, e->H, D, S, p->S_pad, nullptr, nullptr, p->Nt, p->Nt_pad};
     const AttnGeom ag_img{p->Bp, e->H, D, S, p->S_pad, nullptr, nullptr, p->Ni, p->Ni_pad};
     const int64_t ki_el = (int64_t)p->Bp * e->H * p->Ni_pad * 128, qk_el = (int64_t)p->Bp * e->H * p->S_pad * 128;
-    const ModRows mr{mod, mld, e->cfg.eps};
+    const ModRows mr{mod, mld, e->cfg.eps, p->head_rows};
     const TrainChain ch{st, M, t->M_pad, S, sc.g1, sc.g2, sc.g3, sc.wide, sc.hid, false};
     auto G = [&](int i, const char* layer) { return ts->grads.linear("blocks." + std::to_string(i) + layer); };
     auto norm_back = [&](const bf16_t* y, const bf16_t* dy, const float* w_, const float* rstd, bool rope, float scale, bf16_t* out, long ld, int col, int rows,
@@ -238,7 +246,7 @@ extern "C" int mi355_wan_backward(mi355_wan_plan* p, void* stream, const float* 
             CHK(t_wgrad_group(sc, st, t->widec, 2 * D, sg, 2, &xc, 1, Mc, t->Mc_pad));
         }
         // ---- self-attention (gated residual)
-        HIPCHK(launch_gate_mul(t->dx, mod + m0 + 2 * D, mld, sc.g1, M, D, S, st));
+        HIPCHK(launch_gate_mul(t->dx, mod + m0 + 2 * D, mld, sc.g1, M, D, S, st, p->head_rows));
         CHK(t_linear_back(sc, ch, sc.g1, D, D, k.o1, D, D, w.o, G(i, ".attn1.to_out.0"), sc.g2, D));
         CHK(t_attention128_backward(sc, ag_self, st, k.q, k.k, k.vT, k.lse1, k.o1, nullptr, sc.g2, nullptr, S));
         HIPCHK(norm_back(k.q, sc.dq, b.nq, k.rstd_q, true, kScale, sc.wide, 3 * D, 0, M, S, p->S_pad));

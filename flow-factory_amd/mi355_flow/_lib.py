@@ -117,6 +117,11 @@ SIGNATURES = {
     "mi355_clock_probe": (_I, [_P, _P, _I, _I]),
     "mi355_op_ln_mod_bwd": (_I, [_P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _F, _I, _P]),
     "mi355_op_gate_bwd": (_I, [_P, _P, _P, _L, _P, _P, _P, _L, _L, _I, _I]),
+    "mi355_op_ln_mod_bwd_split": (_I, [_P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _F, _I, _P, _I]),
+    "mi355_op_gate_bwd_split": (_I, [_P, _P, _P, _L, _P, _P, _P, _L, _L, _I, _I, _I]),
+    "mi355_op_gemm_epi_split": (_I, [_P, _P, _L, _P, _L, _I, _I, _I, _I, _P, _P, _L, _P, _L, _I, _P, _P, _P, _P, _I, _I, _I, _F, _I, _F, _I, _I, _I, _I, _P, _L,
+                                     _P, _I]),
+    "mi355_op_ln_modulate_split": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _F, _I]),
     "mi355_op_silu_bwd": (_I, [_P, _P, _P, _P, _L]),
     "mi355_op_gelu_fwd": (_I, [_P, _P, _P, _L]),
     "mi355_op_transpose": (_I, [_P, _P, _L, _L, _P, _L, _L, _I, _I, _I, _I, _P, _P, _I, _I]),
@@ -197,6 +202,11 @@ SIGNATURES = {
     "mi355_wan_rollout_i2v": (_I, [_P, _P, _I, C.POINTER(_F), C.POINTER(_F), C.POINTER(_F), _I, _F, _P, _I, _I, _P, _P, _P,
                                    C.POINTER(C.c_int32), _P, _P, _P, _I, _P, _I, _P]),
     "mi355_wan_forward_train_i2v": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P]),
+    "mi355_wan_plan_create_ff": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_P)]),
+    "mi355_wan_forward_ff": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _I, _P]),
+    "mi355_wan_rollout_ff": (_I, [_P, _P, _I, C.POINTER(_F), C.POINTER(_F), C.POINTER(_F), _I, _F, _P, _I, _I, _P, _P, _P,
+                                  C.POINTER(C.c_int32), _P, _P, _P, _I, _P, _I]),
+    "mi355_wan_forward_train_ff": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _I, _P]),
     "mi355_qwen_create": (_I, [C.POINTER(QwenCfg), C.POINTER(_P)]),
     "mi355_qwen_destroy": (_I, [_P]),
     "mi355_qwen_bind_weight": (_I, [_P, C.c_char_p, _P, _I, _I, C.POINTER(_L), _P]),

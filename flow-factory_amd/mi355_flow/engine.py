@@ -564,6 +564,19 @@ def op_gemm_epi(epi: int, a, lda: int, w, ldw: int, M: int, N: int, K: int, bias
     return GEMM_KERNELS[lib.mi355_gemm_last_kernel()]
 
 
+def op_gemm_epi_split(epi: int, a, lda: int, w, ldw: int, M: int, N: int, K: int, bias, head_rows: int, out=None, ldo: int = 0, aux=None,
+                      ld_aux: int = 0, rows_per_sample: int = 1, q=None, k=None, nw_q=None, nw_k=None, H: int = 0, S_pad: int = 0, s_off: int = 0,
+                      eps: float = 1e-6, hd_shift: int = 0, q_scale: float = 0.0, hp: int = 0, wp: int = 0, patch: int = 0, out_ch: int = 0,
+                      stash=None, ld_stash: int = 0, rstd_out=None) -> str:
+    """`op_gemm_epi` with the two-group gate table of the gated-residual epilogue (mi355_op_gemm_epi_split): `aux` holds two rows per sample,
+    the first `head_rows` rows of a sample read the first; head_rows == 0 is `op_gemm_epi`."""
+    lib = _lib.load()
+    _lib.check(lib.mi355_op_gemm_epi_split(_stream(), _dp(a), lda, _dp(w), ldw, M, N, K, epi, _dp(bias), _dp(out), ldo, _dp(aux), ld_aux,
+                                           rows_per_sample, _dp(q), _dp(k), _dp(nw_q), _dp(nw_k), H, S_pad, s_off, eps, hd_shift, q_scale, hp, wp,
+                                           patch, out_ch, _dp(stash), ld_stash, _dp(rstd_out), head_rows), "op_gemm_epi_split")
+    return GEMM_KERNELS[lib.mi355_gemm_last_kernel()]
+
+
 def op_wgrad(dy: torch.Tensor, x: torch.Tensor, k_split: int = 1, variant: int = 1, want_colsum: bool = False):
     """Weight-gradient partial sums [k_split, N, K] (fp32) of dW = dy^T @ x over `k_split` slices of the M rows; dy [M, N] and x [M, K] bf16
     row-major (rows may be strided views: the row stride is passed; any M: a ragged last 64-row tile reads zeros).  variant 1 = the
@@ -605,6 +618,21 @@ def op_gate_bwd(dx, gate, gate_ld: int, y, dy, dgate, dg_ld: int, M: int, D: int
     """y is None and dgate is None: dy = gate * dx only."""
     lib = _lib.load()
     _lib.check(lib.mi355_op_gate_bwd(_stream(), _dp(dx), _dp(gate), gate_ld, _dp(y), _dp(dy), _dp(dgate), dg_ld, M, D, rows_per_sample), "op_gate_bwd")
+
+
+def op_ln_mod_bwd_split(x, dy, dy2, dres, mod, mod_ld: int, shift_off: int, scale_off: int, shift2_off: int, scale2_off: int, M: int, D: int,
+                        rows_per_sample: int, eps: float, accumulate: bool, head_rows: int, dmod=None) -> None:
+    """`op_ln_mod_bwd` on a two-group modulation table (two rows per sample; the first `head_rows` rows of a sample read the first)."""
+    lib = _lib.load()
+    _lib.check(lib.mi355_op_ln_mod_bwd_split(_stream(), _dp(x), _dp(dy), _dp(dy2), _dp(dres), _dp(mod), mod_ld, shift_off, scale_off, shift2_off,
+                                             scale2_off, M, D, rows_per_sample, eps, int(accumulate), _dp(dmod), head_rows), "op_ln_mod_bwd_split")
+
+
+def op_gate_bwd_split(dx, gate, gate_ld: int, y, dy, dgate, dg_ld: int, M: int, D: int, rows_per_sample: int, head_rows: int) -> None:
+    """`op_gate_bwd` on a two-group gate table; y / dgate are refused when head_rows > 0."""
+    lib = _lib.load()
+    _lib.check(lib.mi355_op_gate_bwd_split(_stream(), _dp(dx), _dp(gate), gate_ld, _dp(y), _dp(dy), _dp(dgate), dg_ld, M, D, rows_per_sample,
+                                           head_rows), "op_gate_bwd_split")
 
 
 def op_silu_bwd(dy, pre, dx, n: int) -> None:
@@ -717,3 +745,11 @@ def op_ln_modulate(x: torch.Tensor, shift: torch.Tensor, scale: torch.Tensor, ro
     _lib.check(lib.mi355_op_ln_modulate(_stream(), _ptr(_bf16c(x)), _ptr(mod[0]), _ptr(mod[1]), _ptr(out), M, D,
                                         rows_per_sample, eps), "op_ln_modulate")
     return out
+
+
+def op_ln_modulate_split(x, shift, scale, out, M: int, D: int, rows_per_sample: int, eps: float, head_rows: int) -> None:
+    """Two-group LayerNorm-modulate on caller-owned buffers (mi355_op_ln_modulate_split): shift, scale [2 * nb][D] bf16, `scale` within 2^31
+    elements of `shift`; the first `head_rows` rows of sample b read row 2 b, the others row 2 b + 1.  Nothing is allocated or copied."""
+    lib = _lib.load()
+    _lib.check(lib.mi355_op_ln_modulate_split(_stream(), _dp(x), _dp(shift), _dp(scale), _dp(out), M, D, rows_per_sample, eps, head_rows),
+               "op_ln_modulate_split")

@@ -493,6 +493,67 @@ if _RefAdapter is not None:
                     self._warned_ref_grad = True
                 return self._replay_on_reference(_RefWanI2V.forward, WanI2VRolloutMixin._forward_nograd, (), kwargs)
 
+        from .wan import WanTI2VRolloutMixin
+
+        class Wan2TI2VNativeAdapter(_LiveBinding, WanTI2VRolloutMixin, _RefWanI2V):
+            """`Wan2_I2V_Adapter` for pipelines with `config.expand_timesteps` (Wan2.2-TI2V-5B in image-to-video use; reference
+            models/wan/wan2_i2v.py:547-652, :736-741) with the rollout on a text-to-video engine and first-frame plans: frame 0 of the transformer
+            input is the encoded image, its tokens embed timestep 0.  The reference's own `prepare_latents` (VAE encode of the first frame on the
+            pipeline's torch modules, the mask) produces `(latents, condition, first_frame_mask)` once per rollout; the samples are the
+            reference's `WanI2VSample`; the final merge runs before decode, and decode is the reference's own `decode_latents` (the TI2V
+            residual VAE is not native).  Refused at construction: pipelines WITHOUT `expand_timesteps` (condition channels:
+            `Wan2I2VNativeAdapter`) and two-expert pipelines."""
+
+            _sample_cls = _RefWanI2VSample
+            _output_cls = _RefOutput
+
+            def __init__(self, config, accelerator):
+                _RefWanI2V.__init__(self, config, accelerator)
+                if not bool(getattr(self.pipeline.config, "expand_timesteps", False)):
+                    raise NotImplementedError("mi355_flow: Wan2TI2VNativeAdapter serves `expand_timesteps` pipelines (Wan2.2-TI2V-5B: the first "
+                                              "frame replaced, one timestep per token); this pipeline concatenates condition channels: use "
+                                              "Wan2I2VNativeAdapter")
+                self.vae_scale_temporal = int(getattr(self.pipeline, "vae_scale_factor_temporal", 4))
+                self.vae_scale_spatial = int(getattr(self.pipeline, "vae_scale_factor_spatial", 16))
+                _wan_bind_experts(self, WanConfig.from_hf)
+                if self.engine_2 is not None or self.engine.cfg.cond_channels or self.engine.cfg.image_dim:
+                    raise NotImplementedError("mi355_flow: Wan2TI2VNativeAdapter needs ONE text-to-video transformer (in_channels == out_channels, "
+                                              "no image_dim, no transformer_2): a first frame together with two experts or condition channels is "
+                                              "not implemented")
+
+            def _prepare_i2v(self, images, last_image, image_embeds, B, T, h, w, height, width, num_frames, generator):
+                # wan2_i2v.py:484, :524-549 -- the reference's own steps, in its order: `prepare_latents` draws the fp32 latents, then encodes
+                device = self.device
+                if last_image is not None:
+                    raise NotImplementedError("mi355_flow: last-frame conditioning of an `expand_timesteps` pipeline is not implemented")
+                images = self._standardize_image_input(images, output_type="pil")
+                images = self.pipeline.video_processor.preprocess(images, height=height, width=width).to(device, dtype=torch.float32)
+                latents, condition, first_frame_mask = self.prepare_latents(
+                    image=images, batch_size=B, num_channels_latents=self.pipeline.vae.config.z_dim, height=height, width=width, num_frames=num_frames,
+                    dtype=torch.float32, device=device, generator=generator, latents=None, last_image=None)
+                return latents, condition, first_frame_mask, images
+
+            def _eval_inference(self, **kwargs):          # MI355_WAN_EVAL_REFERENCE=1 only: the reference's own evaluation loop
+                return _RefWanI2V.inference(self, **kwargs)
+
+            def decode_latents(self, latents, output_type="pil"):
+                return _RefWanI2V.decode_latents(self, latents, output_type=output_type)
+
+            @functools.wraps(WanTI2VRolloutMixin.forward)
+            def forward(self, *args, **kwargs):
+                if bool(getattr(self.scheduler, "is_eval", False)):
+                    return _RefWanI2V.forward(self, *args, **kwargs)
+                if torch.is_grad_enabled() and not WanEngine.native_backward_enabled:
+                    return self._replay_on_reference(_RefWanI2V.forward, WanTI2VRolloutMixin.forward, args, kwargs)     # (called under no_grad)
+                return WanTI2VRolloutMixin.forward(self, *args, **kwargs)
+
+            def _grad_fallback(self, why, kwargs):
+                _require_reference_autograd("Wan TI2V", why)
+                if not getattr(self, "_warned_ref_grad", False):
+                    logger.warning("mi355_flow: grad-mode forward() differentiates through the reference path (%s); values stay the engine's", why)
+                    self._warned_ref_grad = True
+                return self._replay_on_reference(_RefWanI2V.forward, WanTI2VRolloutMixin._forward_nograd, (), kwargs)
+
     try:
         from flow_factory.models.qwen_image.qwen_image import QwenImageAdapter as _RefQwen, QwenImageSample as _RefQwenSample
     except Exception:  # noqa: BLE001
@@ -560,4 +621,5 @@ else:
     Flux1KontextNativeAdapter = _unavailable("Flux1KontextNativeAdapter", "mi355_flow.flux.Flux1KontextNativeAdapter")
     Wan2T2VNativeAdapter = _unavailable("Wan2T2VNativeAdapter", "mi355_flow.wan.Wan2T2VNativeAdapter")
     Wan2I2VNativeAdapter = _unavailable("Wan2I2VNativeAdapter", "mi355_flow.wan.Wan2I2VNativeAdapter")
+    Wan2TI2VNativeAdapter = _unavailable("Wan2TI2VNativeAdapter", "mi355_flow.wan.Wan2TI2VNativeAdapter")
     QwenImageNativeAdapter = _unavailable("QwenImageNativeAdapter", "mi355_flow.qwen.QwenImageNativeAdapter")

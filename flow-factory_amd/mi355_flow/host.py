@@ -67,11 +67,12 @@ class RolloutMixinBase:
 
     # -------------------------------------------------------------- inference(): from the schedule to the collectors
     def _rollout_and_collect(self, plan, timesteps, N, guidance, latents, storage, step_noise, cond: tuple, compute_log_prob,
-                             extra_call_back_kwargs, trajectory_indices, sampler=None, **sampler_kw):
+                             extra_call_back_kwargs, trajectory_indices, sampler=None, rollout_kw=None, **sampler_kw):
         """The tail of every `inference()`: the schedule as host lists (one D2H before the loop, none inside), the fused rollout (one C call)
         or -- when per-step callback tensors are asked for, or the family forces a `sampler` of `_rollout_stepwise`'s signature -- per-step
         engine calls (still all-HIP), then exactly the reference's collector bookkeeping (sd3_5.py:265-304) over the engine outputs.
-        `cond`: the family's conditioning arguments, as its `plan.rollout` and `_rollout_stepwise` take them.  Returns (trajectory, final)."""
+        `cond`: the family's conditioning arguments, as its `plan.rollout` and `_rollout_stepwise` take them; `rollout_kw`: further keywords
+        of the fused `plan.rollout` alone.  Returns (trajectory, final)."""
         sched = self.scheduler
         ts_host = [float(t) for t in timesteps.tolist()]
         sig_host = [float(s) for s in sched.sigmas.tolist()]
@@ -84,7 +85,7 @@ class RolloutMixinBase:
         step_outputs = None
         if sampler is None:
             lat_kept, log_probs, final = plan.rollout(ts_host, sig_host, eta_host, dyn, guidance, latents, storage, step_noise, *cond,
-                                                      keep_positions=keep_positions, compute_log_prob=compute_log_prob)
+                                                      keep_positions=keep_positions, compute_log_prob=compute_log_prob, **(rollout_kw or {}))
             pos_to_slot = {p: s for s, p in enumerate(keep_positions)}
         else:
             lat_kept, log_probs, step_outputs = sampler(plan, ts_host, sig_host, eta_host, guidance, latents, storage, step_noise, *cond,

@@ -228,6 +228,13 @@ int mi355_op_gemm_epi(void* stream, const void* A, int64_t lda, const void* W, i
                       void* out, int64_t ldo, const void* aux, int64_t ld_aux, int rows_per_sample, void* q, void* k, const float* nw_q,
                       const float* nw_k, int H, int S_pad, int s_off, float eps, int hd_shift, float q_scale, int hp, int wp, int patch,
                       int out_ch, void* stash, int64_t ld_stash, float* rstd_out);
+/* mi355_op_gemm_epi with a two-group gate table for MI355_EPI_GATE_RES: head_rows > 0 = row m reads aux row
+ * 2 * (m / rows_per_sample) + (m % rows_per_sample >= head_rows) (aux then holds two rows per sample, row stride ld_aux); head_rows == 0 =
+ * mi355_op_gemm_epi.  head_rows > 0 with any other epilogue, or above rows_per_sample, is an error.  Checked before any HIP call. */
+int mi355_op_gemm_epi_split(void* stream, const void* A, int64_t lda, const void* W, int64_t ldw, int M, int N, int K, int epi, const float* bias,
+                            void* out, int64_t ldo, const void* aux, int64_t ld_aux, int rows_per_sample, void* q, void* k, const float* nw_q,
+                            const float* nw_k, int H, int S_pad, int s_off, float eps, int hd_shift, float q_scale, int hp, int wp, int patch,
+                            int out_ch, void* stash, int64_t ld_stash, float* rstd_out, int head_rows);
 /* The kernel family that the calling thread's last GEMM launch went to (a host-side record; the dispatch picks by grid size and the
  * mi355_tune_set keys 0, 3, 19, 31, 32, 34, 37, 40) */
 enum { MI355_GEMM_NONE = 0, MI355_GEMM_SIMPLE_128 = 1, MI355_GEMM_SIMPLE_256 = 2, MI355_GEMM_PINGPONG = 3, MI355_GEMM_W4 = 4, MI355_GEMM_256x192 = 5,
@@ -262,6 +269,10 @@ int mi355_op_attention_ex(void* stream, const void* q, const void* k, const void
 /* out = LayerNorm(x)*(1+scale[b]) + shift[b]; x,out [M][D] bf16; shift,scale [M/rows_per_sample][D] bf16 */
 int mi355_op_ln_modulate(void* stream, const void* x, const void* shift, const void* scale, void* out, int M, int D,
                          int rows_per_sample, float eps);
+/* two-group modulation: shift, scale [2 * M/rows_per_sample][D]; the first head_rows rows of sample b read row 2 b, the others row 2 b + 1.
+ * head_rows == 0: mi355_op_ln_modulate.  Arguments are checked before any HIP call. */
+int mi355_op_ln_modulate_split(void* stream, const void* x, const void* shift, const void* scale, void* out, int M, int D,
+                               int rows_per_sample, float eps, int head_rows);
 
 /* ---- operators of the backward's streaming / reduction kernels (csrc/backward.hip; tests/test_gpu_backward_ops.py) ----
  * One per launcher family.  Arguments are checked before any HIP call (non-zero return, mi355_last_error() names the operator); the launch
@@ -273,10 +284,20 @@ int mi355_op_ln_modulate(void* stream, const void* x, const void* shift, const v
 int mi355_op_ln_mod_bwd(void* stream, const void* x, const void* dy, const void* dy2, void* dres, const void* mod, int64_t mod_ld,
                         int shift_off, int scale_off, int shift2_off, int scale2_off, int M, int D, int rows_per_sample, float eps,
                         int accumulate, float* dmod);
+/* mi355_op_ln_mod_bwd on a two-group table: head_rows > 0 = row m reads the scale of modulation row 2 * (m / rows_per_sample) +
+ * (m % rows_per_sample >= head_rows); head_rows == 0 = mi355_op_ln_mod_bwd.  head_rows > 0 together with dmod is an error (modulation
+ * gradients of a split table are not implemented). */
+int mi355_op_ln_mod_bwd_split(void* stream, const void* x, const void* dy, const void* dy2, void* dres, const void* mod, int64_t mod_ld,
+                              int shift_off, int scale_off, int shift2_off, int scale2_off, int M, int D, int rows_per_sample, float eps,
+                              int accumulate, float* dmod, int head_rows);
 /* dy[m][:] = gate[m / rows_per_sample][:] * dx[m][:]; with y and dgate (both or neither): dgate[b][:] (fp32, row stride dg_ld) += sum over the
  * sample's rows of dx * y */
 int mi355_op_gate_bwd(void* stream, const void* dx, const void* gate, int64_t gate_ld, const void* y, void* dy, float* dgate, int64_t dg_ld,
                       int64_t M, int D, int rows_per_sample);
+/* the same on a two-group gate table (gate row 2 * (m / rows_per_sample) + (m % rows_per_sample >= head_rows)); head_rows > 0 together with
+ * y / dgate is an error; head_rows == 0 = mi355_op_gate_bwd */
+int mi355_op_gate_bwd_split(void* stream, const void* dx, const void* gate, int64_t gate_ld, const void* y, void* dy, float* dgate, int64_t dg_ld,
+                            int64_t M, int D, int rows_per_sample, int head_rows);
 /* dx = dy * silu'(pre);  out = gelu_tanh(pre);  n % 8 == 0 */
 int mi355_op_silu_bwd(void* stream, const void* dy, const void* pre, void* dx, int64_t n);
 int mi355_op_gelu_fwd(void* stream, const void* pre, void* out, int64_t n);
@@ -512,6 +533,31 @@ int mi355_wan_rollout_i2v(mi355_wan_plan* plan, void* stream, int n_steps, const
                           const void* condition, int cond_dtype, const void* image_embeds);
 int mi355_wan_forward_train_i2v(mi355_wan_plan* plan, void* stream, const void* latents, int lat_dtype, const float* t, const void* enc_a,
                                 const void* enc_b, const void* condition, int cond_dtype, const void* image_embeds, void* v_out);
+
+/* ---- Wan2.2-TI2V-5B image-to-video: first frame replaced, per-token timesteps (`expand_timesteps`) ---------------------------------------
+ * Replaces the transformer passes of Wan2_I2V_Adapter for pipelines with config.expand_timesteps (reference models/wan/wan2_i2v.py:736-741): the
+ * transformer reads (1 - first_frame_mask) * condition + first_frame_mask * latents -- frame 0 is the encoded image -- and one timestep per
+ * token, first_frame_mask * t: 0 on the tokens of frame 0, t on all others.  Tokens are ordered (frame, y, x), so frame 0 is the first
+ * head_rows = (h/2) * (w/2) rows of every sample: the modulation tables hold two rows per sample and the LayerNorm-modulate / gated-residual
+ * kernels pick row 2 b + (token >= head_rows).  The engine is a text-to-video one (mi355_wan_create; no condition channels, no image branch);
+ * a first-frame plan is served by the _ff entry points only, a text-to-video plan not by them (an error that names the right entry point, nothing
+ * runs).  first_frame: [batch][in_channels][1][h][w], ff_dtype MI355_F32 / BF16 / F16, read by both CFG halves, no gradient flows to it.
+ *   mi355_wan_forward_ff       t [batch*n_cfg][2] device fp32 = (t_head, t_rest) per forward sample ((0, t) in the reference's use; equal values
+ *                              and the latents' own frame 0 as first_frame reproduce mi355_wan_forward bit for bit)
+ *   mi355_wan_rollout_ff       mi355_wan_rollout with the first frame staged once; step i embeds (0, t_i); the scheduler step and the log-prob
+ *                              run over ALL latents (frame 0 included) on the unmerged latents, as the reference's do
+ *   mi355_wan_forward_train_ff mi355_wan_forward_train for such a plan; mi355_wan_backward serves it unchanged (block linears only) */
+int mi355_wan_plan_create_ff(mi355_wan* e, int batch, int n_cfg, int latent_t, int latent_h, int latent_w, int n_text, int max_steps,
+                             mi355_wan_plan** out);
+int mi355_wan_forward_ff(mi355_wan_plan* plan, void* stream, const void* latents, int lat_dtype, const float* t, const void* enc_a,
+                         const void* enc_b, const void* first_frame, int ff_dtype, void* v_out);
+int mi355_wan_rollout_ff(mi355_wan_plan* plan, void* stream, int n_steps, const float* timesteps_host, const float* sigmas_host,
+                         const float* noise_levels_host, int dynamics, float guidance, const void* init_latents, int init_dtype,
+                         int storage_dtype, const float* step_noise, const void* prompt_embeds, const void* neg_embeds,
+                         const int32_t* keep_slot_host, void* out_latents, float* out_log_probs, void* out_final, int compute_log_prob,
+                         const void* first_frame, int ff_dtype);
+int mi355_wan_forward_train_ff(mi355_wan_plan* plan, void* stream, const void* latents, int lat_dtype, const float* t, const void* enc_a,
+                               const void* enc_b, const void* first_frame, int ff_dtype, void* v_out);
 
 /* ---- Wan2.1 / Wan2.2 T2V `optimize()` replay with gradients (SURVEY.md 8(f) N1 over N4) ----------------------------------------
  * Replaces the grad-mode `Wan2_T2V_Adapter.forward(...)` + `accelerator.backward(loss)` (trainers/grpo.py:263, :326-330 over
