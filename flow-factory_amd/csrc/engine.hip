@@ -1028,6 +1028,7 @@ extern "C" int mi355_tune_set(int key, int value) {
         set_attn_bwd_pipe(value); return 0;
     }         if (key == 44) { set_attn128_bwd_pipe(value); return 0; }  // head_dim-128 attention backward: 1 (default) = software-pipelined passes (gen_attn_bwd.py 128), 0 = the round-4 kernels
     if (key == 45) { set_attn64_w4(value); return 0; }         // head_dim-64 attention forward: 1 (default) = the 4-wave hand-scheduled kernel for static-softmax launches (gen_attn64_w4.py), 0 = attn_kernel, 2 = as 1 at one workgroup per CU
+    if (key == 46) { set_epi_fast(value != 0); return 0; }     // fused GEMM epilogues of the 256x256 kernels: 1 (default) tile-uniform addressing where every tile lies in one sample, 0 the general code
     if (key == 40) { set_w6_mode(value); return 0; }           // 256x192-tile GEMM kernel (round 6): 0 off (default: measured slower inside the two-stream forward), 1 cost rule, 2 wherever it applies
     if (key == 41) { set_w6_alpha_percent(value); return 0; }  // margin of that rule in percent (default 105)
     if (key == 42) { set_w6_min_tiles(value); return 0; }      // smallest grid of its tiles (default 200)
@@ -1154,6 +1155,7 @@ extern "C" int mi355_op_gemm_epi_split(void* stream, const void* A, int64_t lda,
 
 // the kernel family the calling thread's last GEMM launch went to (GemmKernelId of kernels.h; MI355_GEMM_* of the public header)
 extern "C" int mi355_gemm_last_kernel(void) { return gemm_last_kernel(); }
+extern "C" int mi355_gemm_last_epilogue_tile_uniform(void) { return gemm_last_epilogue_tile_uniform(); }
 
 // weight-gradient product as an operator (unit tests / A/B scripts): variant 1 = gemm_tn.hip on the row-major operands, variant 0 = the
 // transposed-copy path (launch_transpose x 2 + the K-contiguous EPI_F32 GEMM).  Output: k_split fp32 partial slabs [N][K].

@@ -34,6 +34,7 @@ __device__ __forceinline__ long gate_row(const GemmParams& p, int m) {
 
 
 constexpr int BK = 64;
+thread_local int g_last_fast = 0;      // ... and whether it was a tile-uniform epilogue build (gemm_last_epilogue_tile_uniform())
 thread_local int g_last_kernel = GEMM_KERNEL_NONE;      // family of this thread's last launch (gemm_last_kernel(): the operator tests assert the dispatch)
 int g_raster_gm = 6;          // tile rows per raster band (0 = plain row-major order); mi355_tune_set(7, v)
 int g_pp_min_tiles = 128;     // smallest 256x256-tile grid for gemm_pp_kernel
@@ -209,13 +210,108 @@ __device__ __forceinline__ void store_row8(const GemmParams& p, int m, int n, in
 //       cannot hoist these loads out of the per-chunk calls itself (the chunks' global stores may alias p.bias for all it knows), and each
 //       call then pays one L2 round trip before its first arithmetic
 struct BiasPre { float4 v[4]; };      // by value: a pointer to a caller's array keeps that array in scratch memory
+// ---- tile-uniform epilogue path (FAST; mi355_tune_set key 46).  The row-layout phase of the general path rebuilds a full 64-bit address per lane
+// and row, (long)m * ld + n with m and n in vector registers (slow-rate v_mul_lo_u32 / v_mad_u64_u32), and divides every row by rows_per_sample.
+// Here the lane's 32-bit byte offsets inside a 32x64 chunk are formed ONCE per output tile (EpiTile), every chunk's base pointer is a wave-uniform
+// value (SGPR pair: scalar-base global loads / stores), row groups are stepped with scalar adds, and the sample index -- the gate row, the batch
+// index of the q / k / V^T scatters -- is one per-tile scalar: the launcher selects these kernels only when every tile lies inside one sample
+// (epi_fast_ok).  Values, rounding points, the staging layout and the k-order are the general path's: outputs are bit-identical.
+// MI355_EPI_ABLATE (measurement builds only, -D on the hipcc line; every value gives the same bits): bit 0 = the tile-uniform q / k path keeps
+// the __shfl_xor row sum, bit 1 = it loads the norm weights per chunk as the general path does (DESIGN.md section 19 has the figures)
+#ifndef MI355_EPI_ABLATE
+#define MI355_EPI_ABLATE 0
+#endif
+constexpr bool epi_has_fast(int e) {
+    return e == EPI_BIAS || e == EPI_BIAS_SILU || e == EPI_BIAS_GELU || e == EPI_GATE_RES || is_qk_epi(e) || e == EPI_VT;
+}
+// ... on the 4-wave kernel only where the epilogue looks at the sample: its bias / SiLU / GELU builds lost 7-9 % of their instructions and no
+// time at all (measured and dropped), so those launches keep the general kernel
+constexpr bool epi_has_fast_w4(int e) { return e == EPI_GATE_RES || is_qk_epi(e) || e == EPI_VT; }
+struct EpiTile {
+    unsigned off_out[4];   // this lane's 16 bytes of a 32x64 row-layout chunk, row 8 it + (lane >> 3), columns 8 (lane & 7) ..., in out / x (V^T: rows of
+                           // S_pad tokens; q, k: [..][64] rows, 128 bytes apart: [0] alone, the row groups are immediate offsets)
+    unsigned off_stash[4]; // the same in the stash
+    unsigned off_rstd;     // EPI_QK_NORM_RSTD: row lane & 15 of rstd_out
+    int bi;                // the sample that all rows (EPI_VT: all token columns) of the tile belong to
+};
+struct NwPre { float4 v[4]; };        // q / k RMSNorm weights of this lane's columns, q_scale folded in: loaded once per tile and column half
+// a pointer the caller knows to be wave-uniform, as an SGPR pair in the GLOBAL address space (a pointer rebuilt from integers would otherwise
+// be a flat one: flat_load / flat_store with a 64-bit vector add each, and arrays of loaded values kept in scratch beside their registers)
+typedef __attribute__((address_space(1))) char* gchar_t;
+typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
+template <typename T>
+__device__ __forceinline__ gchar_t uniform_ptr(T* ptr) {
+    const unsigned long long v = (unsigned long long)ptr;
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+    return (gchar_t)(((unsigned long long)hi << 32) | lo);
+}
+// 16 bytes at scalar base + 32-bit lane offset (global_load / global_store_dwordx4 v_off, v_data, s[base:base+1])
+__device__ __forceinline__ void st16(gchar_t base, unsigned off, uint4 v) {
+    *(__attribute__((address_space(1))) u32x4_t*)(base + off) = (u32x4_t){v.x, v.y, v.z, v.w};
+}
+__device__ __forceinline__ uint4 ld16(gchar_t base, unsigned off) {
+    const u32x4_t v = *(const __attribute__((address_space(1))) u32x4_t*)(base + off);
+    return make_uint4(v[0], v[1], v[2], v[3]);
+}
+template <int EPI>
+__device__ __forceinline__ EpiTile epi_tile(const GemmParams& p, int lane, int m0, int n0) {
+    EpiTile t;            // (no zero-initialisation: the fields an epilogue does not use are never read)
+    const unsigned r = (unsigned)lane >> 3, cb = ((unsigned)lane & 7u) * 16u;
+    if constexpr (is_qk_epi(EPI)) {
+        t.off_out[0] = (unsigned)lane * 16u;
+        t.off_rstd = ((unsigned)lane & 15u) * (unsigned)(2 * p.H) * 4u;
+        t.bi = m0 / p.rows_per_sample;
+    } else if constexpr (EPI == EPI_VT) {
+        t.off_out[0] = r * (unsigned)p.S_pad * 2u + cb;
+#pragma unroll
+        for (int it = 1; it < 4; ++it) t.off_out[it] = t.off_out[it - 1] + (unsigned)p.S_pad * 16u;
+        t.bi = n0 / p.rows_per_sample;
+    } else {
+        t.off_out[0] = r * (unsigned)p.ldo * 2u + cb;
+#pragma unroll
+        for (int it = 1; it < 4; ++it) t.off_out[it] = t.off_out[it - 1] + (unsigned)p.ldo * 16u;
+        if constexpr (EPI == EPI_BIAS_GELU || is_gate_epi(EPI)) {
+            t.off_stash[0] = r * (unsigned)p.ld_stash * 2u + cb;
+#pragma unroll
+            for (int it = 1; it < 4; ++it) t.off_stash[it] = t.off_stash[it - 1] + (unsigned)p.ld_stash * 16u;
+        }
+        if constexpr (is_gate_epi(EPI)) t.bi = m0 / p.rows_per_sample;
+    }
+    return t;
+}
+template <int EPI>
+__device__ __forceinline__ NwPre nw_pre(const GemmParams& p, int lane, int n_base) {
+    NwPre w;
+    const bool is_k = n_base >= p.H * 64;           // uniform: the pointer select is scalar
+    const float* wp = is_k ? p.nw_k : p.nw_q;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        w.v[j] = *(const float4*)(wp + j * 16 + 4 * (lane >> 4));
+        if (!is_k && p.q_scale != 0.f) { w.v[j].x *= p.q_scale; w.v[j].y *= p.q_scale; w.v[j].z *= p.q_scale; w.v[j].w *= p.q_scale; }
+    }
+    return w;
+}
+// x[l] + x[l ^ 16], then that + its [l ^ 32]: the two-step tree of the general path's __shfl_xor pair, on the VALU (v_permlane16_swap /
+// v_permlane32_swap exchange 16-lane rows / wave halves between two registers) instead of two dependent ds_bpermute round trips through LDS.
+// Every lane adds the same two numbers as there (one of each pair with the operands swapped: fp32 add commutes), so every lane gets the same bits.
+__device__ __forceinline__ float sum_rows4(float ss) {
+    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+    unsigned u = __float_as_uint(ss);
+    u32x2 r = __builtin_amdgcn_permlane16_swap(u, u, false, false);
+    ss = __uint_as_float(r[0]) + __uint_as_float(r[1]);
+    u = __float_as_uint(ss);
+    r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
 // NJ (round 6): 16-column blocks of the chunk (4 = the 64-column chunk every kernel used so far; 2 = the 32-column tail of the mid-size
 //       kernel's 96-column wave tile).  The staging rows stay 128 bytes; with NJ < 4 only the first 2 NJ 16-byte slots of a row carry data and
 //       the row-layout phase masks the lanes of the others (they would touch the NEIGHBOURING wave's columns).
-template <int EPI, int NR, bool FULL = false, bool PRE = false, int NJ = 4>
+// FAST: the tile-uniform path above (implies FULL, PRE for the epilogues with a column bias, NJ = 4); et / nwp: the caller's per-tile / per-column-half state
+template <int EPI, int NR, bool FULL = false, bool PRE = false, int NJ = 4, bool FAST = false>
 __device__ __forceinline__ void epilogue_part(const GemmParams& p, const f32x4 (&acc)[NR][NJ], int m_base, int n_base,
-                                              char* stg, int lane, BiasPre bpre = BiasPre()) {
+                                              char* stg, int lane, BiasPre bpre = BiasPre(), EpiTile et = EpiTile(), NwPre nwp = NwPre()) {
     static_assert(NJ == 4 || (NJ == 2 && !is_qk_epi(EPI)), "a q/k head is one whole 64-column chunk");
+    static_assert(!FAST || (FULL && NJ == 4 && NR == 2 && epi_has_fast(EPI)), "the tile-uniform path has no guards and 32x64 chunks");
     const int frow = lane & 15, fkg = lane >> 4;
     const bool cok = NJ == 4 || (lane & 7) < 2 * NJ;          // row-layout phase: this lane's 8 columns belong to the chunk
     float4 bcol[NJ];
@@ -223,6 +319,8 @@ __device__ __forceinline__ void epilogue_part(const GemmParams& p, const f32x4 (
     if constexpr (EPI == EPI_BIAS_GELU || is_gate_epi(EPI)) {
         // training-mode forward: the pre-activation (GELU) / the un-gated projection (gated residual) goes to the stash first (same wave-private staging, LDS ops of a wave are in order)
         if (p.stash) {
+            gchar_t sb = nullptr;          // (tile-uniform path) the chunk's first stash element: one scalar base for its four row groups
+            if constexpr (FAST) sb = uniform_ptr(p.stash + (long)m_base * p.ld_stash + n_base);
 #pragma unroll
             for (int i = 0; i < NR; ++i) {
                 const int r = i * 16 + frow;
@@ -241,6 +339,9 @@ __device__ __forceinline__ void epilogue_part(const GemmParams& p, const f32x4 (
                 const int r = it * 8 + (lane >> 3), c = lane & 7;
                 const uint4 val = *(const uint4*)(stg + r * 128 + ((c ^ (r & 7)) << 4));
                 const int m = m_base + r, n = n_base + c * 8;
+                if constexpr (FAST) {
+                    st16(sb, et.off_stash[it], val);
+                } else
                 if (cok && (FULL || m < p.M)) {
                     bf16_t* sp = p.stash + (long)m * p.ld_stash + n;
                     if (FULL || (n + 8 <= p.N && (p.ld_stash & 7) == 0)) *(uint4*)sp = val;
@@ -261,7 +362,8 @@ __device__ __forceinline__ void epilogue_part(const GemmParams& p, const f32x4 (
             if constexpr (PRE) bcol[j] = bpre.v[j];
             else if (FULL || n < p.N) bcol[j] = *(const float4*)(p.bias + n);
         }
-        if constexpr (is_qk_epi(EPI)) {
+        if constexpr (is_qk_epi(EPI) && FAST && !(MI355_EPI_ABLATE & 2)) nw[j] = nwp.v[j];
+        else if constexpr (is_qk_epi(EPI)) {
             const bool is_k = n_base >= p.H * 64;
             nw[j] = *(const float4*)((is_k ? p.nw_k : p.nw_q) + j * 16 + 4 * fkg);
             if (!is_k && p.q_scale != 0.f) { nw[j].x *= p.q_scale; nw[j].y *= p.q_scale; nw[j].z *= p.q_scale; nw[j].w *= p.q_scale; }
@@ -296,13 +398,20 @@ __device__ __forceinline__ void epilogue_part(const GemmParams& p, const f32x4 (
                 for (int j = 0; j < 4; ++j)
                     sj[j] = __builtin_fmaf(y[j][3], y[j][3], __builtin_fmaf(y[j][2], y[j][2], __builtin_fmaf(y[j][1], y[j][1], y[j][0] * y[j][0])));
                 float ss = (sj[0] + sj[1]) + (sj[2] + sj[3]);
-                ss += __shfl_xor(ss, 16, 64);
-                ss += __shfl_xor(ss, 32, 64);
+                if constexpr (FAST && !(MI355_EPI_ABLATE & 1)) ss = sum_rows4(ss);
+                else {
+                    ss += __shfl_xor(ss, 16, 64);
+                    ss += __shfl_xor(ss, 32, 64);
+                }
                 rstd = rsqrtf(__builtin_fmaf(ss, 1.0f / 64.0f, p.eps));
             }
             if constexpr (EPI == EPI_QK_NORM_RSTD) {      // training-mode forward: 1/rms of this (row, head) for the RMSNorm backward
                 // (its own epilogue kind: as a runtime branch it cost the rollout kernel 13 spilled VGPRs)
                 const int m = m_base + r;
+                if constexpr (FAST) {
+                    const gchar_t rb = uniform_ptr(p.rstd_out + ((long)m_base + i * 16) * (2 * p.H) + (n_base >> 6));
+                    if (fkg == 0) *(__attribute__((address_space(1))) float*)(rb + et.off_rstd) = rstd;
+                } else
                 if (fkg == 0 && (FULL || m < p.M)) p.rstd_out[(long)m * (2 * p.H) + (n_base >> 6)] = rstd;
             }
 #pragma unroll
@@ -330,7 +439,52 @@ __device__ __forceinline__ void epilogue_part(const GemmParams& p, const f32x4 (
         }
     }
     // wave-private region: a wave's LDS operations execute in order, no barrier needed
-    if constexpr (FULL && is_gate_epi(EPI)) {
+    if constexpr (FAST) {
+        // all LDS reads, then all global loads, then arithmetic + stores (as the general guard-free paths below); addresses = scalar base + et offset
+        uint4 val[NR * 2];
+#pragma unroll
+        for (int it = 0; it < NR * 2; ++it) {
+            const int r = it * 8 + (lane >> 3), c = lane & 7;
+            val[it] = *(const uint4*)(stg + r * 128 + ((c ^ (r & 7)) << 4));
+        }
+        if constexpr (is_qk_epi(EPI)) {
+            const int D = p.H * 64;
+            const bool is_k = n_base >= D;
+            const int h = (is_k ? n_base - D : n_base) >> 6;
+            const int s0 = m_base - et.bi * p.rows_per_sample + p.s_off;
+            const gchar_t db = uniform_ptr((is_k ? p.k : p.q) + (((long)et.bi * p.H + h) * p.S_pad + s0) * 64);
+#pragma unroll
+            for (int it = 0; it < NR * 2; ++it) st16(db + it * 1024, et.off_out[0], val[it]);
+        } else if constexpr (EPI == EPI_VT) {
+            // row m = feature (h, d) = m >> hs, m & (2^hs - 1): ((bi H + h) << hs) + d = (bi H << hs) + m
+            const int hs = p.hd_shift ? p.hd_shift : 6;
+            const int s0 = n_base - et.bi * p.rows_per_sample + p.s_off;
+            const gchar_t db = uniform_ptr(p.q + ((((long)et.bi * p.H) << hs) + m_base) * p.S_pad + s0);
+#pragma unroll
+            for (int it = 0; it < NR * 2; ++it) st16(db, et.off_out[it], val[it]);
+        } else if constexpr (is_gate_epi(EPI)) {
+            uint4 xr[NR * 2];
+            const gchar_t ob = uniform_ptr(p.out + (long)m_base * p.ldo + n_base);
+            const uint4 g = ld16(uniform_ptr(p.aux + (long)et.bi * p.ld_aux + n_base), (unsigned)(lane & 7) * 16u);      // one gate row for the whole tile
+#pragma unroll
+            for (int it = 0; it < NR * 2; ++it) xr[it] = ld16(ob, et.off_out[it]);
+#pragma unroll
+            for (int it = 0; it < NR * 2; ++it) {
+                const uint4 v = val[it], x = xr[it];
+                // (same operations, in the same order, as store_row8's vector path)
+                const float y0 = __builtin_fmaf(bf_lo(g.x), bf_lo(v.x), bf_lo(x.x)), y1 = __builtin_fmaf(bf_hi(g.x), bf_hi(v.x), bf_hi(x.x));
+                const float y2 = __builtin_fmaf(bf_lo(g.y), bf_lo(v.y), bf_lo(x.y)), y3 = __builtin_fmaf(bf_hi(g.y), bf_hi(v.y), bf_hi(x.y));
+                const float y4 = __builtin_fmaf(bf_lo(g.z), bf_lo(v.z), bf_lo(x.z)), y5 = __builtin_fmaf(bf_hi(g.z), bf_hi(v.z), bf_hi(x.z));
+                const float y6 = __builtin_fmaf(bf_lo(g.w), bf_lo(v.w), bf_lo(x.w)), y7 = __builtin_fmaf(bf_hi(g.w), bf_hi(v.w), bf_hi(x.w));
+                st16(ob, et.off_out[it],
+                     make_uint4(pack_bf16(y0, y1), pack_bf16(y2, y3), pack_bf16(y4, y5), pack_bf16(y6, y7)));
+            }
+        } else {      // bias / bias + SiLU / bias + GELU: the staged bf16 values are the output
+            const gchar_t ob = uniform_ptr(p.out + (long)m_base * p.ldo + n_base);
+#pragma unroll
+            for (int it = 0; it < NR * 2; ++it) st16(ob, et.off_out[it], val[it]);
+        }
+    } else if constexpr (FULL && is_gate_epi(EPI)) {
         // x += gate * y in place.  All LDS reads, then all global loads (the residual rows and the gate vectors), then arithmetic + stores:
         // written as one loop the compiler keeps load -> store -> load order (a row's store may alias the next row's load for all it
         // knows), i.e. NR * 2 exposed L2 round trips per call with nothing else to run on a SIMD whose waves are all in their epilogue.
@@ -787,7 +941,7 @@ hipError_t launch_mid(const GemmParams& p, hipStream_t stream) {
 //   P3: (1,0) reads nothing;  prefetch order for tile t+1: U0, U2, U3, U1.
 // DBG (ablation builds only, EPI_BIAS, results are garbage): bit 0 no K-loop prefetch, bit 1 no LDS fragment reads after the first K-tile,
 // bit 2 no epilogue at all (accumulators just reset), bit 3 epilogue without its global stores; bit 4 (alone): the trace build (valid results)
-template <int EPI, int DBG = 0>
+template <int EPI, int DBG = 0, bool FAST = false>
 __global__ __launch_bounds__(512) void gemm_pp_kernel(GemmParams p) {
     constexpr int BM = 256, BN = 256, TM = 128, TN = 64;
     constexpr int A_BYTES = BM * BK * 2, STAGE = 2 * A_BYTES;
@@ -916,6 +1070,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(GemmParams p) {
     // slot 15 of the trace: s_memrealtime (100 MHz, one time base for the whole device) at WG start / end; addressed from p.trace at the
     // two use sites (a second per-lane pointer held across the main loop costs VGPRs the epilogues do not have)
     if (trc) { trc[0] = __builtin_amdgcn_s_memtime(); trc[1] = trc[0]; trc[15 * 8] = __builtin_amdgcn_s_memrealtime(); }
+    constexpr bool PP_PRE = FAST && EPI != EPI_VT && EPI != EPI_BIAS_ROW;
 #define PP_EPILOGUE(SB)                                                                                        \
     do {                                                                                                          \
         /* no wave has an LDS read of this stage pending here (P3 reads nothing; every wave's P2 reads were  */  \
@@ -927,6 +1082,16 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(GemmParams p) {
         char* stg = smem + 2 * STAGE + stg_off; (void)(SB);                                                       \
         const bool full_tile = (em0 + BM <= p.M) && (en0 + BN <= p.N) && ((p.ldo & 7) == 0 || is_qk_epi(EPI) || EPI == EPI_VT) && \
                                (EPI != EPI_VT || ((p.rows_per_sample | p.s_off) & 7) == 0);                       \
+        /* tile-uniform path (the launcher guarantees whole tiles inside one sample): per-tile lane offsets from an opaque lane copy, */ \
+        /* so that none of it is kept alive across the main loop; bias and norm weights once per tile (a wave's four chunks share columns) */ \
+        int lane_e = lane; EpiTile et; BiasPre bpre; NwPre nwp;     /* set below and read under FAST only */    \
+        if constexpr (FAST) {                                                                                     \
+            asm volatile("" : "+v"(lane_e));                                                                      \
+            et = epi_tile<EPI>(p, lane_e, em0, en0);                                                              \
+            if constexpr (PP_PRE)                                                                                 \
+                _Pragma("unroll") for (int j = 0; j < 4; ++j) bpre.v[j] = *(const float4*)(p.bias + en0 + wn * TN + j * 16 + 4 * (lane_e >> 4)); \
+            if constexpr (is_qk_epi(EPI)) nwp = nw_pre<EPI>(p, lane_e, en0 + wn * TN);                            \
+        }                                                                                                         \
         _Pragma("unroll") for (int qq = 0; qq < 4; ++qq) {                                                        \
             f32x4 a2[2][4];                                                                                       \
             _Pragma("unroll") for (int i = 0; i < 2; ++i) _Pragma("unroll") for (int j = 0; j < 4; ++j) {          \
@@ -939,6 +1104,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(GemmParams p) {
                 if (sink == 12345.678f) p.out[lane] = 1; }                                                                    \
             else if constexpr ((DBG & 8) != 0) { GemmParams pd = p; pd.M = 0; pd.N = 0;                                        \
                 epilogue_part<EPI, 2, false>(pd, a2, em0 + grp * TM + qq * 32, en0 + wn * TN, stg, lane); }                    \
+            else if constexpr (FAST) epilogue_part<EPI, 2, true, PP_PRE, 4, true>(p, a2, em0 + grp * TM + qq * 32, en0 + wn * TN, stg, lane_e, bpre, et, nwp); \
             else if (full_tile) epilogue_part<EPI, 2, true>(p, a2, em0 + grp * TM + qq * 32, en0 + wn * TN, stg, lane); \
             else epilogue_part<EPI, 2, false>(p, a2, em0 + grp * TM + qq * 32, en0 + wn * TN, stg, lane);          \
             __builtin_amdgcn_sched_barrier(0);                                                                    \
@@ -1018,9 +1184,9 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(GemmParams p) {
 #undef PP_MFMA
 }
 
-template <int EPI, int DBG = 0>
+template <int EPI, int DBG = 0, bool FAST = false>
 hipError_t launch_pp(const GemmParams& p, hipStream_t stream) {
-    auto kern = gemm_pp_kernel<EPI, DBG>;
+    auto kern = gemm_pp_kernel<EPI, DBG, FAST>;
     constexpr int smem = 2 * 2 * 256 * BK * 2 + 8 * 4096;   // operand ring + epilogue staging = 160 KiB
     static bool attr_set = false;
     if (!attr_set) {
@@ -1033,6 +1199,7 @@ hipError_t launch_pp(const GemmParams& p, hipStream_t stream) {
     if (grid > 256) grid = 256;            // one 512-thread workgroup (128 KiB LDS) per CU, persistent
     grid = (grid + 7) / 8 * 8;             // whole XCD rounds (surplus workgroups exit at once)
     g_last_kernel = GEMM_KERNEL_PP;
+    g_last_fast = FAST;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), smem, stream, p);
     return hipGetLastError();
 }
@@ -1050,7 +1217,7 @@ hipError_t launch_pp(const GemmParams& p, hipStream_t stream) {
 // Requirements (launcher): M % 256 == 0, N % 256 == 0, K % 128 == 0.  ABL: ablation builds for the microbenchmark only (results garbage).
 #include "gemm_w4_asm.inc"
 
-template <int EPI, int ABL = 0>
+template <int EPI, int ABL = 0, bool FAST = false>
 __global__ __launch_bounds__(256) void gemm_w4_kernel(GemmParams p) {
     constexpr int BM = 256, BN = 256;
     constexpr int STAGE = 65536;
@@ -1139,7 +1306,8 @@ __global__ __launch_bounds__(256) void gemm_w4_kernel(GemmParams p) {
             f32x4 a2[2][4];                                                                                    \
             W4_READ_CHUNK_##Q##_##C(a2)                                                                        \
             const int mb = m0 + wm * 128 + Q * 32, nb = n0 + wn * 128 + C * 64;                                \
-            epilogue_part<EPI, 2, true, HAS_COLB>(p, a2, mb, nb, stg, lane_e, bpre);                         \
+            if constexpr (FAST) epilogue_part<EPI, 2, true, HAS_COLB, 4, true>(p, a2, mb, nb, stg, lane_e, bpre, et, nwp); \
+            else epilogue_part<EPI, 2, true, HAS_COLB>(p, a2, mb, nb, stg, lane_e, bpre);                    \
         }
         if constexpr (ABL == 0 || ABL >= 4) {
             // Everything the epilogue derives from the lane id is recomputed per tile from an OPAQUE copy of it: hipcc would otherwise hoist
@@ -1149,12 +1317,16 @@ __global__ __launch_bounds__(256) void gemm_w4_kernel(GemmParams p) {
             int lane_e = lane;
             asm volatile("" : "+v"(lane_e));
             constexpr bool HAS_COLB = EPI != EPI_VT && EPI != EPI_BIAS_ROW;
+            EpiTile et;                 // tile-uniform path: the lane's offsets inside a chunk and the tile's sample, once per tile (set and read under FAST only)
+            if constexpr (FAST) et = epi_tile<EPI>(p, lane_e, m0, n0);
 #define W4_COLUMN_HALF(C)                                                                                                \
             {                                                                                                            \
                 BiasPre bpre;           /* one bias load per tile and column half: its four row chunks share it */       \
+                NwPre nwp;              /* (tile-uniform q / k path: set and read there only) one load of the norm weights */ \
                 if constexpr (HAS_COLB)                                                                                   \
                     _Pragma("unroll") for (int j = 0; j < 4; ++j)                                                         \
                         bpre.v[j] = *(const float4*)(p.bias + n0 + wn * 128 + C * 64 + j * 16 + 4 * (lane_e >> 4));        \
+                if constexpr (FAST && is_qk_epi(EPI)) nwp = nw_pre<EPI>(p, lane_e, n0 + wn * 128 + C * 64);               \
                 W4_CHUNK(0, C) W4_CHUNK(1, C) W4_CHUNK(2, C) W4_CHUNK(3, C)                                              \
             }
             W4_COLUMN_HALF(0) W4_COLUMN_HALF(1)
@@ -1165,9 +1337,9 @@ __global__ __launch_bounds__(256) void gemm_w4_kernel(GemmParams p) {
     }
 }
 
-template <int EPI, int ABL = 0>
+template <int EPI, int ABL = 0, bool FAST = false>
 hipError_t launch_w4(const GemmParams& p, hipStream_t stream) {
-    auto kern = gemm_w4_kernel<EPI, ABL>;
+    auto kern = gemm_w4_kernel<EPI, ABL, FAST>;
     constexpr int smem = 2 * 65536 + 4 * 8192;            // operand stages + epilogue staging = 160 KiB
     static bool attr_set = false;
     if (!attr_set) {
@@ -1179,8 +1351,23 @@ hipError_t launch_w4(const GemmParams& p, hipStream_t stream) {
     if (grid > 256) grid = 256;
     grid = (grid + 7) / 8 * 8;
     g_last_kernel = GEMM_KERNEL_W4;
+    g_last_fast = FAST;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, stream, p);
     return hipGetLastError();
+}
+// The tile-uniform epilogue kernels (FAST) of the two 256x256 families: whole tiles only, 16-byte rows, and every tile inside one sample where
+// the epilogue looks at the sample (rows for the gate and the q / k scatter, token columns for V^T).  Any other launch -- text rows such as 333,
+// a sample edge inside a tile, the two-group gate table -- runs the general kernels unchanged.
+int g_epi_fast = 1;           // mi355_tune_set(46, v): 0 = the general epilogues everywhere
+template <int EPI>
+inline bool epi_fast_ok(const GemmParams& p) {
+    if (!g_epi_fast || !epi_has_fast(EPI)) return false;
+    if (p.M % 256 != 0 || p.N % 256 != 0) return false;
+    if (p.ldo >= (1L << 26) || p.ld_stash >= (1L << 26) || p.S_pad >= (1 << 26)) return false;      // 32-bit byte offsets inside a 32-row chunk
+    if constexpr (is_qk_epi(EPI)) return p.rows_per_sample > 0 && p.rows_per_sample % 256 == 0;
+    else if constexpr (EPI == EPI_VT) return p.rows_per_sample > 0 && p.rows_per_sample % 256 == 0 && (p.s_off & 7) == 0 && (p.S_pad & 7) == 0;
+    else if constexpr (EPI == EPI_GATE_RES) return p.rows_per_sample > 0 && p.rows_per_sample % 256 == 0 && (p.ldo & 7) == 0 && (p.ld_aux & 7) == 0 && (!p.stash || (p.ld_stash & 7) == 0);
+    else return (p.ldo & 7) == 0 && (!p.stash || (p.ld_stash & 7) == 0);
 }
 template <int EPI>
 inline bool w4_ok(const GemmParams& p) {      // whole tiles only (the kernel has the guard-free epilogue path alone)
@@ -1404,6 +1591,7 @@ hipError_t launch_epi(const GemmParams& p, hipStream_t stream) {
                     default: break;
                 }
             }
+            if constexpr (epi_has_fast_w4(EPI)) { if (epi_fast_ok<EPI>(p)) return launch_w4<EPI, 0, true>(p, stream); }
             return launch_w4<EPI>(p, stream);
         }
         if (big >= g_pp_min_tiles && fits32 && cost_pp <= cost_128 && n256_ok) {
@@ -1416,10 +1604,11 @@ hipError_t launch_epi(const GemmParams& p, hipStream_t stream) {
                     case 4: return launch_pp<EPI, 4>(p, stream);
                     case 7: return launch_pp<EPI, 7>(p, stream);
                     case 8: return launch_pp<EPI, 8>(p, stream);
-                    case 16: return launch_pp<EPI, 16>(p, stream);      // s_memtime / s_memrealtime trace build
+                    case 16: return epi_fast_ok<EPI>(p) ? launch_pp<EPI, 16, true>(p, stream) : launch_pp<EPI, 16>(p, stream);      // s_memtime / s_memrealtime trace build
                     default: return hipErrorInvalidValue;
                 }
             }
+            if constexpr (epi_has_fast(EPI)) { if (epi_fast_ok<EPI>(p)) return launch_pp<EPI, 0, true>(p, stream); }
             return launch_pp<EPI>(p, stream);
         }
         if (big >= 200 && !fits32 && n256_ok) return launch_cfg<256, 256, 2, 4, EPI>(p, stream);    // > 4 GiB operand (FLUX modulation table)
@@ -1447,6 +1636,7 @@ hipError_t launch_simple(const GemmParams& p, hipStream_t stream) {
 }  // namespace
 
 int gemm_last_kernel() { return g_last_kernel; }
+int gemm_last_epilogue_tile_uniform() { return g_last_fast; }
 void set_conv_cfg(int v) { g_conv_cfg = v; }
 void set_gemm_variant(int v) { g_gemm_variant = v; }
 void set_w4_max_k(int v) { g_w4_max_k = v; }
@@ -1463,6 +1653,7 @@ void set_mid_plan_hint(int v) { g_mid_plan_hint = v; }
 int get_gemm_variant() { return g_gemm_variant; }
 
 void set_raster_gm(int v) { g_raster_gm = v; }
+void set_epi_fast(int v) { g_epi_fast = v; }
 
 // regions of one GEMM launch for the schedule trace (sched_trace.hip)
 static void trace_gemm(const GemmParams& p, hipStream_t stream) {
@@ -1514,6 +1705,7 @@ static void trace_gemm(const GemmParams& p, hipStream_t stream) {
 
 hipError_t launch_gemm(const GemmParams& p_in, hipStream_t stream) {
     GemmParams p = p_in;
+    g_last_fast = 0;
     p.raster_gm = g_raster_gm;
     if (sched_trace_on()) trace_gemm(p, stream);
     if (p.K % BK != 0 || p.M <= 0 || p.N <= 0) return hipErrorInvalidValue;

@@ -132,6 +132,7 @@ enum GemmKernelId : int {
     GEMM_KERNEL_SIMPLE_OTHER,    // 2-stage kernel, the convolutions' 256x128 / 512x128 tiles
 };
 int gemm_last_kernel();
+int gemm_last_epilogue_tile_uniform();      // 1 if that launch ran a tile-uniform epilogue build (tune key 46), else 0
 void set_gemm_variant(int v);
 void set_w4_max_k(int k);      // largest K that the default dispatch gives to the 4-wave hand-scheduled kernel (mi355_tune_set(19, k))
 int get_gemm_variant();
@@ -145,6 +146,7 @@ void set_mid_alpha_percent(int v);
 void set_mid_min_tiles(int v);
 void set_mid_max_tiles(int v);
 void set_mid_plan_hint(int v);      // engine.hip forward_core: whether this plan takes the mid-size GEMM kernel at all
+void set_epi_fast(int v);       // fused GEMM epilogues: 1 (default) tile-uniform addressing kernels where they apply, 0 the general epilogues
 void set_raster_gm(int v);      // GEMM tile raster: tile rows per band (0 = row-major)
 void set_conv_cfg(int v);       // VAE conv tile shape A/B knob (0 auto)
 void set_attn_variant(int v);  // 0 = plain online softmax, 1 = deferred-rescale (default)

@@ -113,6 +113,7 @@ SIGNATURES = {
     "mi355_op_linear_gate_res": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I]),
     "mi355_op_gemm_epi": (_I, [_P, _P, _L, _P, _L, _I, _I, _I, _I, _P, _P, _L, _P, _L, _I, _P, _P, _P, _P, _I, _I, _I, _F, _I, _F, _I, _I, _I, _I, _P, _L, _P]),
     "mi355_gemm_last_kernel": (_I, []),
+    "mi355_gemm_last_epilogue_tile_uniform": (_I, []),
     "mi355_op_wgrad": (_I, [_P, _P, C.c_int64, _P, C.c_int64, _P, _I, _I, _I, _I, _I, _P, _P]),
     "mi355_clock_probe": (_I, [_P, _P, _I, _I]),
     "mi355_op_ln_mod_bwd": (_I, [_P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _F, _I, _P]),

@@ -240,6 +240,8 @@ int mi355_op_gemm_epi_split(void* stream, const void* A, int64_t lda, const void
 enum { MI355_GEMM_NONE = 0, MI355_GEMM_SIMPLE_128 = 1, MI355_GEMM_SIMPLE_256 = 2, MI355_GEMM_PINGPONG = 3, MI355_GEMM_W4 = 4, MI355_GEMM_256x192 = 5,
        MI355_GEMM_MID_128x192 = 6, MI355_GEMM_MID_192x128 = 7, MI355_GEMM_SIMPLE_OTHER = 8 };
 int mi355_gemm_last_kernel(void);
+/* 1 if that launch ran a tile-uniform epilogue build of the ping-pong / 4-wave kernel (mi355_tune_set key 46), else 0 */
+int mi355_gemm_last_epilogue_tile_uniform(void);
 /* Weight-gradient product on ROW-MAJOR operands (round 6, csrc/gemm_tn.hip): out[s][n][k] (fp32, [k_split][N][K]) = sum over the s-th slice of
  * the M rows of dY[m][n] * X[m][k]; dY [M][ld_dy] and X [M][ld_x] bf16 as the backward leaves them in HBM -- no transposed copies (reference: the
  * weight gradients `accelerator.backward(loss)` produces for the trainable linear layers, trainers/grpo.py:326-330).  N % 128, K % 128 must be
@@ -766,6 +768,11 @@ int mi355_profile_enable(int on);
  *         training-mode forward of the SD3.5 engine) runs the 4-wave kernel with the hand-scheduled two-chain key loop (csrc/gen_attn64_w4.py),
  *         whatever key 1 says; 0 = the compiler-scheduled kernels as before; 2 = as 1 at one workgroup per CU (A/B).  Row sums are fp32 sums
  *         of the exponentials there: results agree with key 45 = 0 to the operator bounds, not bit for bit.
+ *  46     fused GEMM epilogues of the two persistent 256x256 kernels (gemm_pp_kernel, gemm_w4_kernel): 1 (default) = launches of whole tiles
+ *         whose tiles each lie inside one sample (rows_per_sample % 256 == 0 where the epilogue looks at the sample: gated residual, q / k
+ *         scatter, V^T token columns; not the two-group gate table) run kernels with tile-uniform epilogue addressing -- scalar base pointers,
+ *         per-tile lane offsets, the sample index once per tile, the q / k RMSNorm row sum on v_permlane swaps, norm weights once per column
+ *         half; 0 = the general epilogues everywhere.  Bit-identical (tests/test_gpu_gemm_epilogue_fastpath.py).
  * The environment variable MI355_TUNE="key=value,..." applies these settings when the Python binding loads the library. */
 int mi355_tune_set(int key, int value);
 int mi355_profile_collect(double* ms_out, int64_t* count_out);

@@ -38,12 +38,13 @@ def short(name):
             m6 = re.search(r"gemm_w6_kernel<(\d+)>", name)
             if m6:
                 return f"gemm_w6<256x192,{epi[int(m6.group(1))]}>"
-            m4 = re.search(r"gemm_w4_kernel<(\d+)(?:, \d+)?>", name)
+            # (a third template argument `true`: the tile-uniform epilogue build, tune key 46)
+            m4 = re.search(r"gemm_w4_kernel<(\d+)(?:, \d+)?(, true|, false)?>", name)
             if m4:
-                return f"gemm_w4<256x256,{epi[int(m4.group(1))]}>"
-            mp = re.search(r"gemm_pp_kernel<(\d+)(?:, \d+)?>", name)
+                return f"gemm_w4<256x256,{epi[int(m4.group(1))]}{',tu' if m4.group(2) == ', true' else ''}>"
+            mp = re.search(r"gemm_pp_kernel<(\d+)(?:, \d+)?(, true|, false)?>", name)
             if mp:
-                return f"gemm_pp<256x256,{epi[int(mp.group(1))]}>"
+                return f"gemm_pp<256x256,{epi[int(mp.group(1))]}{',tu' if mp.group(2) == ', true' else ''}>"
             m = re.search(r"gemm_kernelILi(\d+)ELi(\d+)ELi\d+ELi\d+ELi(\d+)E", name) or \
                 re.search(r"gemm_kernel<(\d+), (\d+), \d+, \d+, (\d+)", name)
             conv = "conv" if ("true>" in name or "ELb1EE" in name) else "gemm"
