@@ -781,6 +781,17 @@ static int sde_call(hipStream_t st, int batch, int64_t n, const void* v_text, co
     if (dynamics < 0 || dynamics > 3) return errorf("mi355_sde_step: unknown dynamics %d", dynamics);
     if (lat_dtype < 0 || lat_dtype > 2) return errorf("mi355_sde_step: bad latent dtype %d", lat_dtype);
     if (v_dtype < 0 || v_dtype > 2) return errorf("mi355_sde_step: bad noise_pred dtype %d", v_dtype);
+    if (batch <= 0) return errorf("mi355_sde_step: batch must be positive (got %d)", batch);
+    if (n <= 0) return errorf("mi355_sde_step: n must be positive (got %lld)", (long long)n);
+    // one slot of the log-prob scratch ring holds the partial sums and tickets of SDE_STEP_MAX_BATCH samples (MAX_B of sde_step.hip)
+    constexpr int SDE_STEP_MAX_BATCH = 4096;
+    if (batch > SDE_STEP_MAX_BATCH)
+        return errorf("mi355_sde_step: batch %d exceeds the scratch ring's per-slot limit of %d samples", batch, SDE_STEP_MAX_BATCH);
+    if (scalar_stride != 0 && scalar_stride != 1)
+        return errorf("mi355_sde_step: scalar_stride must be 0 (one value for the batch) or 1 (per sample), got %d", scalar_stride);
+    if (next_in && (next_in_dtype < 0 || next_in_dtype > 2)) return errorf("mi355_sde_step: bad next_in_dtype %d", next_in_dtype);
+    if (compute_log_prob < 0 || compute_log_prob > 2)
+        return errorf("mi355_sde_step: compute_log_prob must be 0, 1 or 2 (got %d)", compute_log_prob);
     SdeStepParams s;
     memset(&s, 0, sizeof(s));
     s.v_text = (const bf16_t*)v_text; s.v_uncond = (const bf16_t*)v_uncond; s.v_dt = v_dtype; s.guidance = guidance;
@@ -814,6 +825,8 @@ extern "C" int mi355_unipc_convert(void* stream, const void* v_text, const void*
                                    int sample_dtype, float sigma, float* x0_out, int64_t n) {
     if (!v_text || !sample || !x0_out) return errorf("mi355_unipc_convert: null argument");
     if (n <= 0 || (n & 3)) return errorf("mi355_unipc_convert: n must be a positive multiple of 4 (got %lld)", (long long)n);
+    if (v_dtype < 0 || v_dtype > 2) return errorf("mi355_unipc_convert: bad v_dtype %d", v_dtype);
+    if (sample_dtype < 0 || sample_dtype > 2) return errorf("mi355_unipc_convert: bad sample_dtype %d", sample_dtype);
     HIPCHK(launch_unipc_convert(v_text, v_uncond, v_dtype, guidance, sample, sample_dtype, sigma, x0_out, (long)n, (hipStream_t)stream));
     return 0;
 }
@@ -822,6 +835,11 @@ extern "C" int mi355_op_lincomb(void* stream, int n_terms, const void* const* te
     if (!tensors || !dtypes || !coefs || !out) return errorf("mi355_op_lincomb: null argument");
     if (n_terms < 1 || n_terms > 5) return errorf("mi355_op_lincomb: 1..5 terms (got %d)", n_terms);
     if (n <= 0 || (n & 3)) return errorf("mi355_op_lincomb: n must be a positive multiple of 4 (got %lld)", (long long)n);
+    if (out_dtype < 0 || out_dtype > 2) return errorf("mi355_op_lincomb: bad out_dtype %d", out_dtype);
+    for (int k = 0; k < n_terms; ++k) {
+        if (!tensors[k]) return errorf("mi355_op_lincomb: tensors[%d] is NULL", k);
+        if (dtypes[k] < 0 || dtypes[k] > 2) return errorf("mi355_op_lincomb: bad dtypes[%d] = %d", k, dtypes[k]);
+    }
     HIPCHK(launch_lincomb(n_terms, tensors, dtypes, coefs, out, out_dtype, (long)n, (hipStream_t)stream));
     return 0;
 }
@@ -833,6 +851,11 @@ extern "C" int mi355_sde_step_bwd(void* stream, int batch, int64_t n, const void
     if (!v_text || !latents || !next_in || !sigma || !sigma_next || !eta || !dv) return errorf("mi355_sde_step_bwd: null argument");
     if (dynamics < 0 || dynamics > 3) return errorf("mi355_sde_step_bwd: unknown dynamics %d", dynamics);
     if (lat_dtype < 0 || lat_dtype > 2 || next_in_dtype < 0 || next_in_dtype > 2) return errorf("mi355_sde_step_bwd: bad dtype");
+    if (batch <= 0) return errorf("mi355_sde_step_bwd: batch must be positive (got %d)", batch);
+    if (n <= 0) return errorf("mi355_sde_step_bwd: n must be positive (got %lld)", (long long)n);
+    if (batch > 65535) return errorf("mi355_sde_step_bwd: batch %d exceeds the grid's y limit of 65535", batch);   // gridDim.y = batch
+    if (scalar_stride != 0 && scalar_stride != 1)
+        return errorf("mi355_sde_step_bwd: scalar_stride must be 0 (one value for the batch) or 1 (per sample), got %d", scalar_stride);
     SdeBwdParams s;
     memset(&s, 0, sizeof(s));
     s.v_text = (const bf16_t*)v_text; s.v_uncond = (const bf16_t*)v_uncond; s.guidance = guidance;

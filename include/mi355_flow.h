@@ -99,7 +99,10 @@ int mi355_transformer_forward(mi355_plan* p, void* stream, const void* latents, 
  * sigma/sigma_next/eta : device fp32, one value (scalar_stride 0) or one per sample (stride 1).
  * outputs (any may be NULL): next_out (storage dtype `lat_dtype`), next_f32 (value-rounded fp32,
  * what the reference's step() returns), mean_out fp32, noise_pred_out fp32 (CFG-combined),
- * log_prob/std_dev_t/dt [batch] fp32. */
+ * log_prob/std_dev_t/dt [batch] fp32.
+ * compute_log_prob: 0 = never, 1 = always, 2 = only where eta > 0 (decided on the device: the captured rollout's mode).
+ * Refused before any launch: batch or n <= 0, batch > 4096 (one slot of the log-prob scratch ring), scalar_stride other than 0 / 1,
+ * a dtype code out of range, compute_log_prob outside {0, 1, 2}.  At most 16 steps may be in flight on different streams at once. */
 int mi355_sde_step(void* stream, int batch, int64_t n, const void* v_text, const void* v_uncond, int v_dtype, float guidance,
                    const void* latents, int lat_dtype, const float* noise, const void* next_in, int next_in_dtype,
                    const float* sigma, const float* sigma_next, const float* eta, int scalar_stride, float sigma_max,
